@@ -1,8 +1,14 @@
 """Benchmark: CEM planning throughput (candidate-timesteps/s) on the BASELINE.json workload.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 3]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 3] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run does only what the headline figure needs: set-up, W warm-up plans, the K timed plans,
+the outputs of the last timed plan written to DIR (`--dump-outputs`), the JSON line. Everything
+else this file measures (parity, variants, strong, strong_headline, projection_8gpu, train,
+cpu_baseline, cpu_baseline_torch: runs of their own) is behind `--full`, where the `--no-*`
+options still drop single parts.
 
 `--gpus N` without a launcher (no WORLD_SIZE in the environment) starts the N rank processes itself
 (one per GPU, RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set, 127.0.0.1) before this process touches
@@ -17,20 +23,23 @@ all-gather of returns per CEM iteration. `--strong` splits the config's N over t
 (e.g. `--config 4 --strong`: walker N=16384 over 8 GPUs, BASELINE.json configs[3]);
 `--candidates` overrides N (per GPU, or in total with --strong).
 
-Extra objects on the JSON line:
+Extra objects on the JSON line (from the timed plans themselves):
   roofline     -- the rollout kernel (dominant): algorithmic MLP FLOP per launch / average launch
                   time from fence-free HIP events recorded on the launch stream around the rollout
                   launch of CEM iteration MEASURED_IT in every timed plan (each record idles the GPU
                   ~4 us, so not all five); peak = fp32 MFMA dense 157.3 TFLOP/s (MI355X_MICROARCH.md).
+  plan_gpu_ms  -- mean device span of a timed plan: fence-free HIP events recorded on the plan's stream
+                  just before and just after the C call that enqueues it (so from the enqueue of its
+                  first launch to the end of its last kernel); host_ms_per_plan = ms_per_step minus it:
+                  the host's turn per plan (Python around the call, the result sync and copy-out).
+  outputs      -- with --dump-outputs DIR: the files written (float32 .npy: states, actions, mu, sigma
+                  of the last timed plan, as CEMPlanner.plan_detailed returned them to the caller).
+With --full, from runs of their own:
   cpu_baseline -- the CPU oracle (NumPy restatement of the reference rollout + CEM refit), rank 0,
                   N=1 only, on a bounded sample; a reported baseline, not the target.
   cpu_baseline_torch -- the reference's own CPU arrangement beside it: torch on the host with
                   autograd on (planners.py:199-210), NumPy refit; same conditions.
   parity       -- iteration-0 returns of 256 sampled candidates re-computed by the CPU oracle.
-  plan_gpu_ms  -- mean device span of a timed plan: fence-free HIP events recorded on the plan's stream
-                  just before and just after the C call that enqueues it (so from the enqueue of its
-                  first launch to the end of its last kernel); host_ms_per_plan = ms_per_step minus it:
-                  the host's turn per plan (Python around the call, the result sync and copy-out).
   strong       -- BASELINE.json configs[3]: walker-walk N=16384 H=30 split over the ranks (strong
                   scaling, N/G candidates per GPU), same timing rules; at N=1 the single-GPU plan the
                   split is measured against.
@@ -82,7 +91,31 @@ def parse():
                     help="skip the strong-scaling walker object (BASELINE.json configs[3])")
     ap.add_argument("--no-train", action="store_true",
                     help="skip the model-training object (SURVEY.md §8f rank 2)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: parity, variants, strong, strong_headline, "
+                         "projection_8gpu, train, cpu_baseline, cpu_baseline_torch (each subject to its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed plan returned (states, actions, mu, sigma) as DIR/<name>.npy, float32")
+    args = ap.parse_args()
+    if not args.full:
+        args.no_cpu_baseline = args.no_variants = args.no_strong = args.no_train = True
+    return args
+
+
+DUMPED = ("states", "actions", "mu", "sigma")
+
+
+def dump_outputs(directory, res):
+    """The arrays a caller of the timed path receives (CEMPlanner.plan_detailed's dict), one float32
+    .npy each: a few KB in all. The problem, the start state and the Philox seed are functions of
+    --config alone, so the same arguments give the same files from run to run."""
+    os.makedirs(directory, exist_ok=True)
+    written = {}
+    for name in DUMPED:
+        arr = np.ascontiguousarray(torch.as_tensor(res[name]).detach().cpu().numpy(), dtype=np.float32)
+        np.save(os.path.join(directory, name + ".npy"), arr)
+        written[name + ".npy"] = list(arr.shape)
+    return written
 
 
 def _free_port():
@@ -495,15 +528,17 @@ def main():
                 gc_acc[1] += 1
         gc.callbacks.append(gc_cb)
         stamps = [0.0] * (args.steps + 1)
+        last = first
         t0 = time.perf_counter()
         for k in range(args.steps):
             stamps[k] = time.perf_counter()
-            plan(rollout_events=events[k], plan_events=spans[k])
+            last = plan(rollout_events=events[k], plan_events=spans[k])
         stamps[args.steps] = time.perf_counter()
         barrier()
         elapsed = time.perf_counter() - t0
         gc.callbacks.remove(gc_cb)
         timed.gc = dict(ms=gc_acc[0] * 1e3, collections=gc_acc[1])
+        timed.last = last               # what the last timed plan handed back (--dump-outputs)
         walls = np.diff(np.array(stamps)) * 1e3     # host wall time of each timed plan call
         timed.walls = dict(median=float(np.median(walls)), p90=float(np.percentile(walls, 90)),
                            max=float(walls.max()), min=float(walls.min()))
@@ -526,6 +561,7 @@ def main():
     plan_gpu_ms = timed.plan_gpu_ms
     gc_stats = timed.gc
     wall_stats = timed.walls
+    dumped = dump_outputs(args.dump_outputs, timed.last) if args.dump_outputs and rank == 0 else None
     cand_steps = ITERATIONS * N * H * args.steps
     value = cand_steps / elapsed
     flop_launch = n_local * H * synthetic.flop_per_candidate_step(cfg)
@@ -571,6 +607,8 @@ def main():
     built, same = _lib.build_info()
     out["build"] = {"library": "mujoco-mbrl_amd/mbrl_amd/libmbrl_cem.so", "source_digest": built,
                     "matches_tree": same}
+    if dumped is not None:
+        out["outputs"] = {"dir": args.dump_outputs, "files": dumped}
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["parity"] = parity_sample(prob, first)
     if not args.no_variants:

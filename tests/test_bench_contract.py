@@ -1,6 +1,7 @@
 """bench.py's JSON line keeps the driver's contract (one line; metric/value/unit/n_gpus/steps/
 warmup/ms_per_step/higher_is_better/scaling/vs_baseline/dtype/data/config) plus the roofline,
-cpu_baseline and parity objects. Runs bench.py as a child process on the GPU at a tiny step count."""
+cpu_baseline and parity objects of a `--full` run; a plain run carries the headline alone and can dump
+the last timed plan's outputs. Runs bench.py as a child process on the GPU at a tiny step count."""
 import json
 import os
 import subprocess
@@ -13,7 +14,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.mark.gpu
 def test_bench_json_line_contract():
-    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "2", "--warmup", "1",
+    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--full", "--steps", "2", "--warmup", "1",
                           "--cpu-budget", "2"], capture_output=True, text=True, timeout=110, cwd=REPO)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -34,6 +35,76 @@ def test_bench_json_line_contract():
     assert ct["autograd"] is True and ct["value"] > 0 and ct["cores"] >= 1
     assert d["parity"]["return_max_rel_err"] < 1e-5
     assert [v["precision"] for v in d["variants"]] == ["f16x6", "f16x3"]
+
+
+FULL_ONLY = ("parity", "variants", "strong", "strong_headline", "projection_8gpu", "train", "cpu_baseline",
+             "cpu_baseline_torch")
+
+
+def test_full_is_off_by_default(monkeypatch):
+    """Without --full every part that takes a run of its own is off; with it the --no-* options decide."""
+    sys.path.insert(0, REPO)
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert not a.full and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    assert a.no_cpu_baseline and a.no_variants and a.no_strong and a.no_train
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-train", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "d" and a.no_train
+    assert not (a.no_cpu_baseline or a.no_variants or a.no_strong)
+
+
+def test_dump_outputs_writes_float32_npy(tmp_path):
+    sys.path.insert(0, REPO)
+    import numpy as np
+    import torch
+
+    import bench
+    res = {k: torch.arange(6, dtype=torch.float64).reshape(2, 3) + i for i, k in enumerate(bench.DUMPED)}
+    res["returns"] = torch.zeros(4)          # diagnostics are not part of what plan() hands back
+    target = tmp_path / "new" / "dir"
+    written = bench.dump_outputs(str(target), res)
+    assert sorted(os.listdir(target)) == sorted(k + ".npy" for k in bench.DUMPED) == sorted(written)
+    for i, k in enumerate(bench.DUMPED):
+        arr = np.load(target / (k + ".npy"))
+        assert arr.dtype == np.float32 and written[k + ".npy"] == [2, 3]
+        assert np.array_equal(arr, np.arange(6, dtype=np.float32).reshape(2, 3) + i)
+
+
+@pytest.mark.gpu
+def test_plain_bench_is_headline_only_and_dumps_the_last_plan(tmp_path):
+    """A plain run: the contract fields, none of the --full objects, and with --dump-outputs the
+    states / actions / mu / sigma of the last timed plan -- bit for bit what the same plan made in
+    this process returns (the inputs are a function of the arguments alone)."""
+    import numpy as np
+    import torch
+    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                          "--dump-outputs", str(tmp_path / "o")], capture_output=True, text=True, timeout=110,
+                         cwd=str(tmp_path))
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert not [k for k in FULL_ONLY if k in d]
+    assert d["n_gpus"] == 1 and d["steps"] == 3 and d["warmup"] == 1 and d["higher_is_better"] is True
+    assert d["unit"] == "candidate-timesteps/s" and d["dtype"] == "f32" and d["ms_per_step"] > 0
+    assert abs(d["value"] - 5 * 4096 * 30 / (d["ms_per_step"] * 1e-3)) <= 1e-9 * d["value"]
+    assert 0 < d["roofline"]["frac"] < 1 and d["plan_gpu_ms"] > 0
+    assert sorted(d["outputs"]["files"]) == ["actions.npy", "mu.npy", "sigma.npy", "states.npy"]
+
+    from mbrl_amd import CEMPlanner, synthetic
+    prob = synthetic.make_problem(3)
+    res = CEMPlanner.plan_detailed(prob["s0"], prob["model"], prob["cost"], prob["sample_action"], prob["cfg"]["H"],
+                                   num_candidates=4096, num_elites=409, num_iterations=5, alpha=0.1,
+                                   seed=prob["rng_seed"], device=torch.device("cuda", 0))
+    total = 0
+    for name in ("states", "actions", "mu", "sigma"):
+        arr = np.load(tmp_path / "o" / (name + ".npy"))
+        total += arr.nbytes
+        assert arr.dtype == np.float32 and np.isfinite(arr).all()
+        assert np.array_equal(arr, res[name].cpu().numpy()), name
+    assert total <= 64 << 20
 
 
 def test_launch_ranks_starts_one_process_per_rank(tmp_path):
@@ -61,7 +132,7 @@ def test_bench_gpus_2_launches_two_ranks():
     it); the line reports n_gpus 2, the process-group world size, and the strong walker split."""
     env = dict(os.environ, MBRL_DIST_BACKEND="gloo")
     env.pop("WORLD_SIZE", None)
-    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "2",
+    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--full", "--steps", "2",
                           "--warmup", "1", "--no-variants", "--no-cpu-baseline"], capture_output=True, text=True,
                          timeout=110, cwd=REPO, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
@@ -80,7 +151,7 @@ def test_bench_gpus_8_launches_eight_ranks():
     4096 candidates per rank, the walker split at 2048 and the headline split at 512 per rank)."""
     env = dict(os.environ, MBRL_DIST_BACKEND="gloo")
     env.pop("WORLD_SIZE", None)
-    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "8", "--steps", "2",
+    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "8", "--full", "--steps", "2",
                           "--warmup", "1", "--no-variants", "--no-cpu-baseline"], capture_output=True, text=True,
                          timeout=280, cwd=REPO, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
