@@ -28,6 +28,9 @@
 extern "C" {
 #endif
 
+/* v13 also carries the MPPI calls (mbrl_mppi_update, mbrl_mppi_workspace_bytes, mbrl_mppi_plan and
+ * mbrl_mppi_params): they were added within v13, purely additively -- no existing entry point, struct
+ * or option changed, so the version did not move. */
 #define MBRL_ABI_VERSION 13
 
 typedef struct ihipStream_t* mbrl_stream_t; /* == hipStream_t */
@@ -140,6 +143,17 @@ typedef struct {
     int32_t _pad;
     uint64_t seed;
 } mbrl_cem_params;
+
+/* MPPI plan settings (added within ABI v13: the MPPI calls are purely additive). */
+typedef struct {
+    int32_t N, H, iterations, update_sigma; /* candidates, horizon, I, 1: refit sigma too (0: classic MPPI) */
+    float temperature;     /* lambda > 0 */
+    float alpha;           /* smoothing, as mbrl_cem_params.alpha */
+    float lo, hi;          /* action bounds */
+    float init_mu;         /* used when init_mu_rows == NULL */
+    float init_sigma;
+    uint64_t seed;
+} mbrl_mppi_params;
 
 int mbrl_abi_version(void);
 /* "src=<16 hex digits> arch=gfx950": the sha256 prefix of the sources the library was built from
@@ -353,6 +367,51 @@ int mbrl_cem_plan_batch(const mbrl_mlp_shape* shape, const void* packed, const m
 int mbrl_cem_update(const float* costs, int32_t E, int32_t N, int32_t K, const mbrl_sampler* sampler, int32_t H,
                     int32_t a, float alpha, int64_t* elite_idx, float* returns_out, float* mu_out, float* sigma_out,
                     float* next_actions, int32_t draw_offset, int32_t draw_count, mbrl_stream_t stream);
+
+/* ---- MPPI (model-predictive path integral control, the information-theoretic update; not in the
+ * reference; added within ABI v13). Where CEM refits on a hard top-K, MPPI weights EVERY candidate:
+ *   r_n  = member-mean return (as mbrl_select_elites forms it); valid iff finite
+ *   beta = min over valid r_n (a zero of either sign counts as +0.0)
+ *   w_n  = expf(-((r_n - beta) / temperature)) for valid n, else 0;   eta = sum_n w_n  (>= 1)
+ *   m[t][d] = sum_n (w_n a[t][n][d]) / eta;   with update_sigma: v[t][d] = sum_n w_n (a[t][n][d] - m[t][d])^2 / eta
+ *   mu' = alpha mu + (1 - alpha) m;   sigma' = sqrt(alpha sigma^2 + (1 - alpha) v) (correctly rounded), or
+ *   sigma' = sigma without update_sigma (classic MPPI). No valid candidate: mu' = mu, sigma' = sigma, bit for bit.
+ * Every sum over n runs in one fixed order that depends on N alone (DESIGN.md "MPPI"): chunks of 32
+ * consecutive candidates summed sequentially, the chunk partials again in groups of 32, then the
+ * group partials; at most 93 dependent additions. fp32, round to nearest, no contraction.
+ *
+ * mbrl_mppi_update: one iteration's update as ONE launch (mppi_update_kernel), no workspace.
+ * costs: [E][N]; actions: [H][N][a], the proposals the rollout consumed; sampler: this iteration's mu,
+ * sigma, lo, hi, seed, iteration; mu_out / sigma_out: [H][a] (not the sampler's buffers).
+ * Optional (NULL = off): weights_out [N]; returns_out [N]; stats_out [2] = (beta, eta), (NaN, 0) when no
+ * candidate is valid; next_actions [H][draw_count][a]: iteration sampler->iteration + 1's proposals for
+ * candidates [draw_offset, draw_offset + draw_count) drawn from mu_out / sigma_out, bit-identical to
+ * mbrl_sample_actions with n_offset = draw_offset (a buffer other than `actions`, which the launch is
+ * still reading). MBRL_EUNSUPPORTED when N > 32768 or a > 64; MBRL_EINVAL for NULL arguments, sizes
+ * < 1, a temperature that is not finite and > 0, or a draw range outside [0, N) -- all before any launch. */
+int mbrl_mppi_update(const float* costs, int32_t E, int32_t N, const float* actions, const mbrl_sampler* sampler,
+                     int32_t H, int32_t a, float temperature, float alpha, int32_t update_sigma, float* mu_out,
+                     float* sigma_out, float* weights_out, float* returns_out, float* stats_out, float* next_actions,
+                     int32_t draw_offset, int32_t draw_count, mbrl_stream_t stream);
+
+/* ---- whole single-GPU MPPI plan, the analogue of mbrl_cem_plan: I x (rollout -> mbrl_mppi_update), then
+ * the final mean's trajectory (member mean). Proposals are drawn exactly as CEM's (the same counter
+ * space: a plan is one or the other).
+ * init_mu_rows: [H][a] device, or NULL. The warm start: row t of the initial mean is init_mu_rows[t]
+ * clipped to [lo, hi] instead of params->init_mu (e.g. the previous plan shifted by one step).
+ * mu / sigma (optional), actions_out = clip(mu, lo, hi), states_out: as mbrl_cem_plan; they and s0 may be
+ * mapped host memory from mbrl_host_alloc.
+ * Optional records (NULL = off): cost_hist [I][E][N]; weight_hist [I][N]; mu_hist / sigma_hist
+ * [I + 1][H][a], row 0 the initial distribution and row i + 1 the result of iteration i; rollout_events
+ * as mbrl_cem_plan's. mbrl_mppi_workspace_bytes returns 0 for a bad shape or bad params.
+ * MBRL_EINVAL before any launch for NULL pointers, N / H / iterations < 1, a temperature that is not
+ * finite and > 0, or a workspace that is too small; MBRL_EUNSUPPORTED for N > 32768. */
+size_t mbrl_mppi_workspace_bytes(const mbrl_mlp_shape* shape, const mbrl_mppi_params* params);
+int mbrl_mppi_plan(const mbrl_mlp_shape* shape, const void* packed, const mbrl_norm* norm, const mbrl_cost* cost,
+                   const float* s0, const mbrl_mppi_params* params, const float* init_mu_rows, float* mu,
+                   float* sigma, float* actions_out, float* states_out, float* cost_hist, float* weight_hist,
+                   float* mu_hist, float* sigma_hist, mbrl_event_t* rollout_events, void* workspace,
+                   size_t ws_bytes, mbrl_stream_t stream);
 
 /* ---- gradient-descent planner: replaces GradientDescentPlanner's
  * _optimize_trajectory (planners.py:103-137) -- Adam(lr) on the action sequence through the dynamics

@@ -22,6 +22,7 @@
 #include "mbrl_internal.h"
 #include <rccl/rccl.h>
 #include "mbrl_rng.h"
+#include "mbrl_wave.h"
 
 namespace mbrl {
 
@@ -333,62 +334,8 @@ __global__ void pack_bias_kernel(const float* __restrict__ b, int n_real, int n_
 // ------------------------------------------------------------------------------------------------
 // Block scan helper (exclusive), blockDim.x multiple of 64, <= 1024
 // ------------------------------------------------------------------------------------------------
-// Cross-lane moves as DPP operand modifiers (VALU, no LDS round trip as __shfl's ds_bpermute takes).
-// Lanes whose source is outside the row, or whose row is not in ROWS, read 0.
-template <int CTRL, int ROWS = 0xF>
-__device__ __forceinline__ uint32_t dpp_u32(uint32_t x) {
-    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, CTRL, ROWS, 0xF, false);
-}
-
-// Inclusive prefix sum over the wave: in-row shifts by 1, 2, 4, 8, then the row broadcasts.
-__device__ __forceinline__ uint32_t wave_inclusive_scan(uint32_t x) {
-    x += dpp_u32<0x111>(x);        // row_shr:1
-    x += dpp_u32<0x112>(x);        // row_shr:2
-    x += dpp_u32<0x114>(x);        // row_shr:4
-    x += dpp_u32<0x118>(x);        // row_shr:8
-    x += dpp_u32<0x142, 0xA>(x);   // row_bcast:15 (rows 1 and 3)
-    x += dpp_u32<0x143, 0xC>(x);   // row_bcast:31 (rows 2 and 3)
-    return x;
-}
-
-// Wave minimum / maximum: every lane of a row gets the row's (quad swaps, half mirror, mirror), then the
-// four rows' through readlane.
-__device__ __forceinline__ uint32_t wave_min_u32(uint32_t x) {
-    x = min(x, dpp_u32<0xB1>(x));
-    x = min(x, dpp_u32<0x4E>(x));
-    x = min(x, dpp_u32<0x141>(x));
-    x = min(x, dpp_u32<0x140>(x));
-    return min(min((uint32_t)__builtin_amdgcn_readlane((int)x, 0), (uint32_t)__builtin_amdgcn_readlane((int)x, 16)),
-               min((uint32_t)__builtin_amdgcn_readlane((int)x, 32), (uint32_t)__builtin_amdgcn_readlane((int)x, 48)));
-}
-__device__ __forceinline__ uint32_t wave_max_u32(uint32_t x) {
-    x = max(x, dpp_u32<0xB1>(x));
-    x = max(x, dpp_u32<0x4E>(x));
-    x = max(x, dpp_u32<0x141>(x));
-    x = max(x, dpp_u32<0x140>(x));
-    return max(max((uint32_t)__builtin_amdgcn_readlane((int)x, 0), (uint32_t)__builtin_amdgcn_readlane((int)x, 16)),
-               max((uint32_t)__builtin_amdgcn_readlane((int)x, 32), (uint32_t)__builtin_amdgcn_readlane((int)x, 48)));
-}
-
-// The lanes' predicate as a 64-bit mask straight from the compare (HIP's __ballot goes through a
-// select and a second compare).
-__device__ __forceinline__ uint64_t wave_ballot(bool p) { return __builtin_amdgcn_ballot_w64(p); }
-
-__device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t v, uint32_t* lds_waves, uint32_t* total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    const uint32_t x = wave_inclusive_scan(v);
-    if (lane == 63) lds_waves[wave] = x;
-    __syncthreads();
-    uint32_t before = 0, all = 0;   // every wave sums the wave totals itself (broadcast reads)
-    for (int w = 0; w < nw; ++w) {
-        const uint32_t t = lds_waves[w];
-        before += w < wave ? t : 0u;
-        all += t;
-    }
-    *total = all;
-    __syncthreads();
-    return before + x - v;
-}
+// (The wave64 cross-lane helpers -- dpp_u32, wave_inclusive_scan, wave_min_u32 / wave_max_u32,
+// wave_ballot, block_exclusive_scan -- and ELITE_CHUNK live in mbrl_wave.h, shared with mppi.hip.)
 
 // ------------------------------------------------------------------------------------------------
 // Elite selection: returns -> order keys -> radix select of the K-th key -> stable tie break by
@@ -924,7 +871,6 @@ static size_t select_reg_lds(int KPT) { return 4 * (size_t)sel_words(KPT); }
 // refit: canonical chunked sums (ELITE_CHUNK = 32, oracle/cem.py:chunked_sum) -> mean, population
 // variance -> alpha-smoothed mu / sigma. All float ops correctly rounded, no contraction.
 // ------------------------------------------------------------------------------------------------
-constexpr int ELITE_CHUNK = 32;
 
 __global__ void gather_elites_kernel(uint64_t seed, int iteration, const float* __restrict__ mu,
                                      const float* __restrict__ sigma, float lo, float hi, int a,
@@ -1347,11 +1293,15 @@ struct InitZero {
     size_t words[2];
 };
 
+// ROWS (the MPPI plan's warm start, single problem): the initial mean of row t is mu_rows[t][.] clipped
+// to [lo, hi] instead of init_mu. ROWS = false compiles to the kernel without the argument.
+template <bool ROWS>
 __global__ void __launch_bounds__(1024) cem_init_kernel(uint64_t seed, float init_mu, float init_sigma, float lo,
                                                         float hi, int H, int a, int N, float* __restrict__ mu,
                                                         float* __restrict__ sigma, float* __restrict__ actions,
                                                         const float* __restrict__ s0_src, int s,
-                                                        float* __restrict__ s0_dst, int draw_off, InitZero zero) {
+                                                        float* __restrict__ s0_dst, int draw_off, InitZero zero,
+                                                        const float* __restrict__ mu_rows) {
     const int S = gridDim.x / H;
     const int t = blockIdx.x / S, j = blockIdx.x - (blockIdx.x / S) * S, b = blockIdx.y;
     const size_t ro = ((size_t)b * H + t) * a;
@@ -1365,7 +1315,12 @@ __global__ void __launch_bounds__(1024) cem_init_kernel(uint64_t seed, float ini
     if (s0_src && blockIdx.x == 0 && b == 0)
         for (int d = threadIdx.x; d < s; d += blockDim.x) s0_dst[d] = s0_src[d];
     if (j == 0)
-        for (int d = threadIdx.x; d < a; d += blockDim.x) { mu[ro + d] = init_mu; sigma[ro + d] = init_sigma; }
+        for (int d = threadIdx.x; d < a; d += blockDim.x) {
+            float m0 = init_mu;
+            if (ROWS) m0 = fminf(fmaxf(mu_rows[ro + d], lo), hi);
+            mu[ro + d] = m0;
+            sigma[ro + d] = init_sigma;
+        }
     if (!actions) return;
     const int G = (a + 3) >> 2;
     const size_t BN = (size_t)gridDim.y * N;
@@ -1378,7 +1333,11 @@ __global__ void __launch_bounds__(1024) cem_init_kernel(uint64_t seed, float ini
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int d = 4 * g + j;
-            if (d < a) actions[((size_t)t * BN + nbase + n) * a + d] = cem_action(init_mu, init_sigma, z[j], lo, hi);
+            if (d < a) {
+                float m0 = init_mu;
+                if (ROWS) m0 = fminf(fmaxf(mu_rows[ro + d], lo), hi);
+                actions[((size_t)t * BN + nbase + n) * a + d] = cem_action(m0, init_sigma, z[j], lo, hi);
+            }
         }
     }
 }
@@ -2399,9 +2358,9 @@ int mbrl_cem_plan(const mbrl_mlp_shape* shape, const void* packed, const mbrl_no
     // fuses the draw), and the plan's hand-off words zeroed (no memset before the pair / trajectory
     // launches)
     const InitZero z = plan_zero(g, p->N, w.pair, w.xchg, w.xchg_bytes, w.status);
-    hipLaunchKernelGGL(cem_init_kernel, dim3(p->H * (fuse_draw ? draw_slices(p->H, 1, p->N, g.a) : 1), 1), dim3(1024), 0,
+    hipLaunchKernelGGL(cem_init_kernel<false>, dim3(p->H * (fuse_draw ? draw_slices(p->H, 1, p->N, g.a) : 1), 1), dim3(1024), 0,
                        stream, p->seed, p->init_mu, p->init_sigma, p->lo, p->hi, p->H, g.a, p->N, w.mu[0], w.sigma[0],
-                       fuse_draw ? w.actions : nullptr, s0_in, g.s, w.s0, 0, z);
+                       fuse_draw ? w.actions : nullptr, s0_in, g.s, w.s0, 0, z, nullptr);
     unsigned pair_epoch = 0;
     const float* s0 = w.s0;   // the workspace copy (s0_in may be mapped host memory)
     int cur = 0;
@@ -2444,6 +2403,180 @@ int mbrl_cem_plan(const mbrl_mlp_shape* shape, const void* packed, const mbrl_no
         }
         if (rc) return rc;
         cur ^= 1;
+    }
+    // final mean's rollout -> predicted states [E][H][s] (E == 1: straight into states_out), member mean
+    float* per_member = g.E == 1 ? states_out : w.states;
+    rc = traj_impl(g, packed, norm, s0, actions_out, p->H, per_member, w.xchg, w.xchg_bytes, w.status, stream,
+                   z.ptr[1] != nullptr);
+    if (rc) return rc;
+    if (g.E > 1) {
+        const int Hs = p->H * g.s;
+        hipLaunchKernelGGL(member_mean_kernel, dim3((Hs + 255) / 256), dim3(256), 0, stream, w.states, g.E, Hs,
+                           states_out);
+    }
+    return hip_check(hipGetLastError(), "plan launch");
+}
+
+// ---- MPPI (ABI v13, additive): the softmax-weighted update (mppi.hip) and the plan around it. The
+// plan loop sits here because rollout_impl, traj_impl, plan_zero and Geometry are static to this file.
+static int mppi_temperature_check(float temperature) {
+    if (!(temperature > 0.0f) || temperature > 3.402823466e+38f)
+        return fail(MBRL_EINVAL, "mppi: temperature %g must be finite and > 0", (double)temperature);
+    return MBRL_OK;
+}
+
+static int mppi_range_check(int N, int a) {
+    if (N > MPPI_MAX_N || a > MPPI_MAX_A)
+        return fail(MBRL_EUNSUPPORTED, "mppi: N=%d a=%d exceeds the update kernel (N <= %d, a <= %d)", N, a, MPPI_MAX_N,
+                    MPPI_MAX_A);
+    return MBRL_OK;
+}
+
+int mbrl_mppi_update(const float* costs, int32_t E, int32_t N, const float* actions, const mbrl_sampler* sampler,
+                     int32_t H, int32_t a, float temperature, float alpha, int32_t update_sigma, float* mu_out,
+                     float* sigma_out, float* weights_out, float* returns_out, float* stats_out, float* next_actions,
+                     int32_t draw_offset, int32_t draw_count, mbrl_stream_t stream) {
+    if (!costs || !actions || !sampler || !sampler->mu || !sampler->sigma || !mu_out || !sigma_out)
+        return fail(MBRL_EINVAL, "mppi_update: NULL argument");
+    if (N < 1 || E < 1 || H < 1 || a < 1) return fail(MBRL_EINVAL, "mppi_update: need N (%d), E, H, a >= 1", N);
+    if (int rc = mppi_temperature_check(temperature)) return rc;
+    if (next_actions && (draw_count < 1 || draw_offset < 0 || (int64_t)draw_offset + draw_count > N))
+        return fail(MBRL_EINVAL, "mppi_update: draw range [%d, %d + %d) outside [0, %d)", draw_offset, draw_offset,
+                    draw_count, N);
+    if (next_actions == actions)
+        return fail(MBRL_EINVAL, "mppi_update: next_actions must not be the actions buffer (other workgroups still read it)");
+    if (int rc = mppi_range_check(N, a)) return rc;
+    MppiArgs U{};
+    U.costs = costs; U.E = E; U.N = N; U.H = H; U.a = a; U.actions = actions;
+    U.seed = sampler->seed; U.iteration = sampler->iteration; U.mu = sampler->mu; U.sigma = sampler->sigma;
+    U.lo = sampler->lo; U.hi = sampler->hi; U.alpha = alpha; U.oma = 1.0f - alpha; U.temperature = temperature;
+    U.update_sigma = update_sigma != 0;
+    U.mu_out = mu_out; U.sigma_out = sigma_out;
+    U.weights_out = weights_out; U.returns_out = returns_out; U.stats_out = stats_out;
+    U.next_actions = next_actions; U.draw_off = next_actions ? draw_offset : 0; U.draw_n = next_actions ? draw_count : N;
+    const int S = next_actions ? draw_slices(H, 1, draw_count, a) : 1;
+    return hip_check(launch_mppi_update(U, S, reinterpret_cast<hipStream_t>(stream)), "mppi update launch");
+}
+
+// Workspace layout for mbrl_mppi_plan (PlanWs without the selection's and the elites' scratch).
+struct MppiWs {
+    float *costs, *mu[2], *sigma[2], *states, *actions[2], *s0;
+    void* pair;
+    unsigned long long* xchg;
+    unsigned* status;
+    size_t xchg_bytes, bytes;
+};
+
+// actions[2]: where the update draws the next proposals (update_samples) they go to the other buffer --
+// the row's other workgroups are still streaming the proposals the rollout consumed.
+static MppiWs mppi_ws(const Geometry& g, const mbrl_mppi_params* p, void* base) {
+    MppiWs w{};
+    char* b = static_cast<char*>(base);
+    size_t o = 0;
+    auto take = [&](size_t n) { void* r = b ? b + o : nullptr; o += align256(n); return r; };
+    const size_t Ha = (size_t)p->H * g.a;
+    w.costs = (float*)take((size_t)g.E * p->N * 4);
+    w.actions[0] = (float*)take((size_t)p->H * p->N * g.a * 4);
+    w.actions[1] = update_samples(p->N, g.a) ? (float*)take((size_t)p->H * p->N * g.a * 4) : w.actions[0];
+    w.mu[0] = (float*)take(Ha * 4); w.mu[1] = (float*)take(Ha * 4);
+    w.sigma[0] = (float*)take(Ha * 4); w.sigma[1] = (float*)take(Ha * 4);
+    w.states = (float*)take((size_t)g.E * p->H * g.s * 4);
+    w.xchg_bytes = (size_t)g.E * 2 * g.Wpad * 8;
+    w.xchg = (unsigned long long*)take(w.xchg_bytes);
+    w.status = (unsigned*)take(16);
+    w.s0 = (float*)take((size_t)g.s * 4);
+    w.pair = take(pair_area_bytes(g, p->N));
+    w.bytes = o;
+    return w;
+}
+
+static int mppi_params_check(const mbrl_mppi_params* p) {
+    if (!p) return fail(MBRL_EINVAL, "mppi: params is NULL");
+    if (p->N < 1 || p->H < 1 || p->iterations < 1)
+        return fail(MBRL_EINVAL, "bad MPPI params N=%d H=%d I=%d", p->N, p->H, p->iterations);
+    return mppi_temperature_check(p->temperature);
+}
+
+size_t mbrl_mppi_workspace_bytes(const mbrl_mlp_shape* shape, const mbrl_mppi_params* params) {
+    Geometry g;
+    if (shape_geometry(shape, &g) != MBRL_OK || mppi_params_check(params) != MBRL_OK) return 0;
+    return mppi_ws(g, params, nullptr).bytes;
+}
+
+int mbrl_mppi_plan(const mbrl_mlp_shape* shape, const void* packed, const mbrl_norm* norm, const mbrl_cost* cost,
+                   const float* s0_in, const mbrl_mppi_params* p, const float* init_mu_rows, float* mu, float* sigma,
+                   float* actions_out, float* states_out, float* cost_hist, float* weight_hist, float* mu_hist,
+                   float* sigma_hist, mbrl_event_t* rollout_events, void* workspace, size_t ws_bytes,
+                   mbrl_stream_t stream_) {
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    Geometry g;
+    int rc = shape_geometry(shape, &g);
+    if (rc) return rc;
+    if ((rc = mppi_params_check(p))) return rc;
+    if (!packed || !actions_out || !states_out || !workspace)
+        return fail(MBRL_EINVAL, "mppi_plan: packed/actions_out/states_out/workspace NULL");
+    if (!s0_in) return fail(MBRL_EINVAL, "mppi_plan: s0 is NULL");
+    MppiWs w = mppi_ws(g, p, workspace);
+    if (ws_bytes < w.bytes) return fail(MBRL_EINVAL, "mppi_plan: workspace %zu < %zu", ws_bytes, w.bytes);
+    if ((rc = mppi_range_check(p->N, g.a))) return rc;
+    if ((rc = pair_forced_check(g, p->N))) return rc;
+    // the update draws the next proposals itself where cem_update_kernel would (update_samples)
+    const bool fuse_draw = update_samples(p->N, g.a);
+    const int S = fuse_draw ? draw_slices(p->H, 1, p->N, g.a) : 1;
+    const InitZero z = plan_zero(g, p->N, w.pair, w.xchg, w.xchg_bytes, w.status);
+    if (init_mu_rows)
+        hipLaunchKernelGGL(cem_init_kernel<true>, dim3(p->H * S, 1), dim3(1024), 0, stream, p->seed, p->init_mu,
+                           p->init_sigma, p->lo, p->hi, p->H, g.a, p->N, w.mu[0], w.sigma[0],
+                           fuse_draw ? w.actions[0] : nullptr, s0_in, g.s, w.s0, 0, z, init_mu_rows);
+    else
+        hipLaunchKernelGGL(cem_init_kernel<false>, dim3(p->H * S, 1), dim3(1024), 0, stream, p->seed, p->init_mu,
+                           p->init_sigma, p->lo, p->hi, p->H, g.a, p->N, w.mu[0], w.sigma[0],
+                           fuse_draw ? w.actions[0] : nullptr, s0_in, g.s, w.s0, 0, z, nullptr);
+    if ((rc = hip_check(hipGetLastError(), "init launch"))) return rc;
+    const size_t Ha = (size_t)p->H * g.a;
+    auto record = [&](int row, int cur) {   // the distribution after `row` updates into the history
+        hipError_t e = hipSuccess;
+        if (mu_hist) e = hipMemcpyAsync(mu_hist + row * Ha, w.mu[cur], Ha * 4, hipMemcpyDeviceToDevice, stream);
+        if (e == hipSuccess && sigma_hist)
+            e = hipMemcpyAsync(sigma_hist + row * Ha, w.sigma[cur], Ha * 4, hipMemcpyDeviceToDevice, stream);
+        return hip_check(e, "history copy");
+    };
+    if ((rc = record(0, 0))) return rc;
+    unsigned pair_epoch = 0;
+    const float* s0 = w.s0;   // the workspace copy (s0_in may be mapped host memory)
+    int cur = 0;
+    for (int it = 0; it < p->iterations; ++it) {
+        mbrl_sampler sp{};
+        sp.seed = p->seed; sp.iteration = it; sp.mu = w.mu[cur]; sp.sigma = w.sigma[cur]; sp.lo = p->lo; sp.hi = p->hi;
+        float* costs = cost_hist ? cost_hist + (size_t)it * g.E * p->N : w.costs;
+        if (rollout_events && rollout_events[2 * it]) {
+            rc = hip_check(hipEventRecord(reinterpret_cast<hipEvent_t>(rollout_events[2 * it]), stream), "event");
+            if (rc) return rc;
+        }
+        float* acts = w.actions[fuse_draw ? (it & 1) : 0];   // this iteration's proposals
+        rc = rollout_impl(g, packed, norm, cost, s0, 0, fuse_draw ? acts : nullptr, fuse_draw ? nullptr : &sp, p->N,
+                          p->H, 0, costs, acts, nullptr, stream, pair_area_bytes(g, p->N) ? w.pair : nullptr,
+                          z.ptr[0] ? &pair_epoch : nullptr);
+        if (rc) return rc;
+        if (rollout_events && rollout_events[2 * it + 1]) {
+            rc = hip_check(hipEventRecord(reinterpret_cast<hipEvent_t>(rollout_events[2 * it + 1]), stream), "event");
+            if (rc) return rc;
+        }
+        const bool last = it + 1 == p->iterations;   // the last update also writes mu / sigma / clip(mu)
+        MppiArgs U{};
+        U.costs = costs; U.E = g.E; U.N = p->N; U.H = p->H; U.a = g.a; U.actions = acts;
+        U.seed = p->seed; U.iteration = it; U.mu = w.mu[cur]; U.sigma = w.sigma[cur];
+        U.lo = p->lo; U.hi = p->hi; U.alpha = p->alpha; U.oma = 1.0f - p->alpha; U.temperature = p->temperature;
+        U.update_sigma = p->update_sigma != 0;
+        U.mu_out = w.mu[cur ^ 1]; U.sigma_out = w.sigma[cur ^ 1];
+        U.fin_mu = last ? mu : nullptr; U.fin_sigma = last ? sigma : nullptr; U.fin_actions = last ? actions_out : nullptr;
+        U.weights_out = weight_hist ? weight_hist + (size_t)it * p->N : nullptr;
+        U.next_actions = (fuse_draw && !last) ? w.actions[(it + 1) & 1] : nullptr;
+        U.draw_off = 0; U.draw_n = p->N;
+        rc = hip_check(launch_mppi_update(U, U.next_actions ? S : 1, stream), "mppi update launch");
+        if (rc) return rc;
+        cur ^= 1;
+        if ((rc = record(it + 1, cur))) return rc;
     }
     // final mean's rollout -> predicted states [E][H][s] (E == 1: straight into states_out), member mean
     float* per_member = g.E == 1 ? states_out : w.states;
@@ -2685,9 +2818,9 @@ static int plan_sharded_body(const mbrl_mlp_shape* shape, const void* packed, co
     // shard (global candidates [off, off + Nl)), the hand-off words and this rank's status zeroed
     const InitZero z = plan_zero(g, Nl, w.pair, w.xchg, w.xchg_bytes, w.status);
     if (!z.ptr[1]) step(hip_check(hipMemsetAsync(own_status, 0, 2 * sizeof(unsigned), stream), "status memset"));
-    hipLaunchKernelGGL(cem_init_kernel, dim3(H * (fuse_draw ? draw_slices(H, 1, Nl, a) : 1), 1), dim3(1024), 0, stream,
+    hipLaunchKernelGGL(cem_init_kernel<false>, dim3(H * (fuse_draw ? draw_slices(H, 1, Nl, a) : 1), 1), dim3(1024), 0, stream,
                        p->seed, p->init_mu, p->init_sigma, p->lo, p->hi, H, a, Nl, w.mu[0], w.sigma[0],
-                       fuse_draw ? w.actions : nullptr, s0_in, g.s, w.s0, off, z);
+                       fuse_draw ? w.actions : nullptr, s0_in, g.s, w.s0, off, z, nullptr);
     step(hip_check(hipGetLastError(), "init launch"));
     if (!fuse_draw && err == MBRL_OK) {
         mbrl_sampler sp0{};
@@ -2931,9 +3064,9 @@ int mbrl_cem_plan_batch(const mbrl_mlp_shape* shape, const void* packed, const m
     const bool fuse = update_kpt(p->N, p->K, g.a) != 0 && g_opt[MBRL_OPT_UNFUSED_UPDATE].load(std::memory_order_relaxed) == 0;
     const bool fuse_draw = fuse && update_samples(p->N, g.a);
     if (fuse_draw)
-        hipLaunchKernelGGL(cem_init_kernel, dim3(p->H * draw_slices(p->H, B, p->N, g.a), B), dim3(1024), 0, stream,
+        hipLaunchKernelGGL(cem_init_kernel<false>, dim3(p->H * draw_slices(p->H, B, p->N, g.a), B), dim3(1024), 0, stream,
                            p->seed, p->init_mu, p->init_sigma, p->lo, p->hi, p->H, g.a, p->N, w.mu[0], w.sigma[0],
-                           w.actions, nullptr, 0, nullptr, 0, InitZero{});
+                           w.actions, nullptr, 0, nullptr, 0, InitZero{}, nullptr);
     else
         hipLaunchKernelGGL(fill2_kernel, dim3((BHa + 255) / 256), dim3(256), 0, stream, w.mu[0], p->init_mu,
                            w.sigma[0], p->init_sigma, BHa);

@@ -334,6 +334,30 @@ struct TrajArgs {
 };
 hipError_t launch_traj(const TrajArgs& A, int E, hipStream_t stream);
 
+// MPPI update (mppi.hip): one launch per iteration after the rollout. Workgroup (t * S + j) forms the
+// member-mean returns, their minimum and the softmax weights for all N, then the weighted chunked sums
+// of row t of `actions`; slice j == 0 writes the row's new mu / sigma, every slice draws its share of
+// the next iteration's proposals. N <= MPPI_MAX_N, a <= MPPI_MAX_A.
+constexpr int MPPI_MAX_N = 32768;
+constexpr int MPPI_MAX_A = 64;
+struct MppiArgs {
+    const float* costs;          // [E][N]
+    int E, N, H, a;
+    const float* actions;        // [H][N][a] the proposals the rollout consumed
+    uint64_t seed;
+    int iteration;
+    const float *mu, *sigma;     // [H][a] this iteration's distribution
+    float lo, hi, alpha, oma, temperature;
+    int update_sigma;
+    float *mu_out, *sigma_out;   // [H][a]
+    float *fin_mu, *fin_sigma, *fin_actions;   // last iteration: plan outputs (or NULL)
+    float *weights_out, *returns_out, *stats_out;   // [N], [N], [2] = (beta, eta): lead workgroup, or NULL
+    float* next_actions;         // [H][draw_n][a] proposals of iteration + 1, or NULL
+    int draw_off, draw_n;
+};
+size_t mppi_update_lds_bytes(int N, int a);
+hipError_t launch_mppi_update(const MppiArgs& A, int S, hipStream_t stream);
+
 // Fused gradient-descent planner (gd.hip): one persistent workgroup runs every Adam iteration of
 // planners.py:103-137 (goal-state cost, one ensemble member).
 struct GdArgs {

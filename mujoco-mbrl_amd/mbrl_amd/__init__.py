@@ -9,7 +9,8 @@ from .agents import MPCPolicy  # noqa: F401
 from .env_wrappers import EnvWrapper  # noqa: F401
 from .models import (CoshLoss, CostModel, DynamicsModel, EnsembleModel, LinearModel, Model,  # noqa: F401
                      ModelWithReward, QuadraticCost, SmoothAbsLoss, compose, goal_state_cost, state_action_cost)
-from .planners import CEMPlanner, GradientDescentPlanner, ModelPlanner, RandomShootingPlanner  # noqa: F401
+from .planners import (CEMPlanner, GradientDescentPlanner, ModelPlanner, MPPIPlanner,  # noqa: F401
+                       RandomShootingPlanner)
 
 
 def load_extension():

@@ -630,6 +630,22 @@ def cem_update(costs, K, sampler, H, a, alpha, mu_out, sigma_out, elites=None, r
     return elites
 
 
+def mppi_update(costs, actions, sampler, H, a, temperature, alpha, update_sigma, mu_out, sigma_out, weights_out=None,
+                returns_out=None, stats_out=None, next_actions=None, draw_offset=0):
+    """mbrl_mppi_update: one MPPI iteration's softmax-weighted update in one launch. costs: [E, N];
+    actions: [H, N, a], the proposals those costs belong to; next_actions (optional, another buffer):
+    [H, count, a] receives iteration + 1's proposals for candidates [draw_offset, draw_offset + count).
+    A shape outside the kernel raises (there is no other path for the weighted update)."""
+    lib = _lib.load()
+    E, N = costs.shape
+    dn = 0 if next_actions is None else int(next_actions.shape[1])
+    _lib.check(lib.mbrl_mppi_update(_lib.ptr(costs), E, N, _lib.ptr(actions), ctypes_ref(sampler), H, a,
+                                    float(temperature), float(alpha), int(bool(update_sigma)), _lib.ptr(mu_out),
+                                    _lib.ptr(sigma_out), _lib.ptr(weights_out), _lib.ptr(returns_out),
+                                    _lib.ptr(stats_out), _lib.ptr(next_actions), int(draw_offset), dn,
+                                    _lib.stream_handle(costs.device)), "mbrl_mppi_update")
+
+
 def make_sampler(seed, iteration, mu, sigma, lo, hi):
     return _lib.Sampler(int(seed) & 0xFFFFFFFFFFFFFFFF, int(iteration), 0, _lib.ptr(mu), _lib.ptr(sigma),
                         float(lo), float(hi))

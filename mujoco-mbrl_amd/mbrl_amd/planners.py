@@ -837,3 +837,212 @@ def _cem_generic(model, cost, s0, st, a, dev):
     if st["record"]:
         out.update({k: torch.stack(v) for k, v in hist.items()})
     return out
+
+
+# ------------------------------------------------------------------------------------------------
+# MPPI
+# ------------------------------------------------------------------------------------------------
+def mppi_warm_start_rows(actions, horizon, shift, lo, hi):
+    """The initial mean an MPPI plan starts from, given the previous plan's actions (host only, no
+    device): rows [shift:] of `actions` (a [T, a] tensor / array, or a list of [1, a] / [a] rows as the
+    gradient-descent planner returns them), the last row repeated to keep `horizon` rows (or cut to
+    them), clipped to [lo, hi]. float32 [horizon, a]."""
+    if isinstance(actions, (list, tuple)):
+        actions = [np.asarray(x.detach().cpu() if isinstance(x, torch.Tensor) else x, dtype=np.float32).reshape(1, -1)
+                   for x in actions]
+        rows = np.concatenate(actions, 0) if actions else np.zeros((0, 0), np.float32)
+    else:
+        x = actions.detach().cpu() if isinstance(actions, torch.Tensor) else actions
+        rows = np.asarray(x, dtype=np.float32)
+        rows = rows.reshape(rows.shape[0], -1) if rows.ndim >= 1 else rows.reshape(1, 1)
+    H, shift = int(horizon), int(shift)
+    if shift < 0:
+        raise ValueError(f"shift must be >= 0, got {shift}")
+    rows = rows[shift:]
+    if rows.shape[0] == 0:
+        raise ValueError(f"initial_trajectory has no action row left after dropping {shift}")
+    if rows.shape[0] < H:
+        rows = np.concatenate([rows, np.repeat(rows[-1:], H - rows.shape[0], 0)], 0)
+    return np.clip(rows[:H], np.float32(lo), np.float32(hi)).astype(np.float32)
+
+
+class MPPIPlanner(ModelPlanner):
+    """Model-predictive path integral control (the information-theoretic update; not in the reference):
+    I iterations of Philox proposal -> persistent MFMA rollout -> softmax-weighted refit, in which every
+    candidate n contributes with weight exp(-(J_n - J_min) / temperature) (no elite cut), in the HIP
+    extension (mbrl_mppi_plan; csrc/mppi.hip).
+
+    kwargs (defaults): num_candidates (1000), num_iterations (1), temperature (1.0), alpha (0.0: the
+    smoothing of CEMPlanner), update_sigma (False: classic MPPI keeps sigma; True refits it from the
+    weighted variance), init_std (None -> (hi - lo) / 4), action_bounds (None -> from sample_action's
+    action_spec, else (-1, 1)), seed (None -> drawn from the global NumPy RNG), shift (1),
+    return_device (False), precision ("f32"), record (False).
+
+    Warm start: `initial_trajectory` is honoured. Its action rows, after dropping the first `shift`
+    and repeating the last to keep `horizon` rows, clipped to the bounds, are the initial mean
+    (mppi_warm_start_rows), so MPCPolicy gets receding-horizon behaviour with one or two iterations per
+    control step; shift=0 takes the rows as given, None starts from a zero mean.
+
+    plan returns (predicted states of the clipped final mean, the clipped final mean); plan_detailed
+    adds mu, sigma and, with record=True, costs [I, E, N], weights [I, N], mu_hist / sigma_hist
+    [I + 1, H, a] (row 0 the initial distribution). distributed=True and plan_batch are not implemented
+    for MPPI (NotImplementedError)."""
+    defaults = dict(num_candidates=1000, num_iterations=1, temperature=1.0, alpha=0.0, update_sigma=False,
+                    init_std=None, action_bounds=None, seed=None, shift=1, return_device=False, precision="f32",
+                    distributed=False)
+    warm_starts = True
+
+    @staticmethod
+    def plan(initial_state, model, cost, sample_action, horizon, initial_trajectory=None, **kwargs):
+        res = MPPIPlanner.plan_detailed(initial_state, model, cost, sample_action, horizon, initial_trajectory,
+                                        **kwargs)
+        return res["states"], res["actions"]
+
+    @staticmethod
+    def plan_batch(initial_states, model, cost, sample_action, horizon, **kwargs):
+        raise NotImplementedError("MPPIPlanner.plan_batch: batched MPPI plans are not implemented; call plan() per "
+                                  "row, or use CEMPlanner.plan_batch")
+
+    @staticmethod
+    def _settings_build(sample_action, horizon, kwargs):
+        d = MPPIPlanner.defaults
+        g = lambda k: kwargs.get(k, d[k])  # noqa: E731
+        if g("distributed"):
+            raise NotImplementedError("MPPIPlanner: distributed=True (sharded MPPI) is not implemented; "
+                                      "use CEMPlanner for multi-GPU plans")
+        N, I = int(g("num_candidates")), int(g("num_iterations"))
+        bounds = g("action_bounds")
+        sdesc = fused.describe_sampler(sample_action) if sample_action is not None else None
+        if bounds is None:
+            bounds = (sdesc[0], sdesc[1]) if sdesc is not None else (-1.0, 1.0)
+        lo, hi = float(bounds[0]), float(bounds[1])
+        init_std = g("init_std")
+        init_std = float(np.float32(hi - lo) / np.float32(4.0)) if init_std is None else float(init_std)
+        seed = g("seed")
+        if seed is None:
+            seed = int(np.random.randint(0, 2 ** 62, dtype=np.int64))
+        temperature = float(g("temperature"))
+        if not (temperature > 0.0 and np.isfinite(temperature)):
+            raise ValueError(f"temperature must be finite and > 0, got {temperature}")
+        if N < 1 or I < 1:
+            raise ValueError(f"need num_candidates ({N}) >= 1 and num_iterations ({I}) >= 1")
+        return dict(N=N, H=int(horizon), I=I, temperature=temperature, alpha=float(g("alpha")),
+                    update_sigma=bool(g("update_sigma")), lo=lo, hi=hi, init_std=init_std, seed=seed,
+                    shift=int(g("shift")), keep=bool(g("return_device")), record=bool(kwargs.get("record", False)),
+                    events=kwargs.get("rollout_events"), plan_events=kwargs.get("plan_events"),
+                    adim=sdesc[2] if sdesc else None, precision=_lib.precision_code(g("precision")))
+
+    @staticmethod
+    def plan_detailed(initial_state, model, cost, sample_action, horizon, initial_trajectory=None, **kwargs):
+        """plan() plus diagnostics: dict(states, actions, mu, sigma[, costs, weights, mu_hist, sigma_hist])."""
+        st = MPPIPlanner._settings_build(sample_action, horizon, kwargs)
+        dev = _device(kwargs)
+        rows = None
+        if initial_trajectory is not None:
+            rows = mppi_warm_start_rows(initial_trajectory[1], st["H"], st["shift"], st["lo"], st["hi"])
+        with _on_device(dev):
+            mdesc, cdesc, prob = fused.describe_problem(model, cost, dev, st["precision"])
+            if mdesc is not None and cdesc is not None:
+                if rows is not None and rows.shape[1] != mdesc["a"]:
+                    raise ValueError(f"initial_trajectory actions have {rows.shape[1]} dims, the model {mdesc['a']}")
+                res = _mppi_fused_single(prob, initial_state, st, rows)
+            else:
+                a = st["adim"] if rows is None else rows.shape[1]
+                if a is None:
+                    a = sample_action(batch_size=1).shape[1]
+                res = _mppi_generic(model, cost, initial_state.to(device=dev, dtype=torch.float32).contiguous(), st,
+                                    a, dev, rows)
+            both = res.pop("_both", None)
+            if both is not None and not st["keep"]:
+                host = both.cpu()              # one device-to-host copy for states and actions
+                H, s = res["states"].shape
+                res["states"] = host[:H * s].view(H, s)
+                res["actions"] = host[H * s:].view(H, -1)
+            else:
+                res["states"] = _to_host(res["states"], st["keep"])
+                res["actions"] = _to_host(res["actions"], st["keep"])
+            return res
+
+
+def _mppi_fused_single(prob, initial_state, st, rows):
+    """One C-ABI call: mbrl_mppi_plan (every iteration stream-ordered, no host sync)."""
+    lib = _lib.load()
+    dev = prob.device
+    md = prob.mdesc
+    N, H, I = st["N"], st["H"], st["I"]
+    a, s, E = md["a"], md["s"], md["E"]
+    pkey = ("mppi", N, H, I, st["update_sigma"], st["temperature"], st["alpha"], st["lo"], st["hi"], st["init_std"],
+            int(st["seed"]) & 0xFFFFFFFFFFFFFFFF)
+    hit = prob.plan_cache.get(pkey)
+    if hit is None:
+        params = _lib.MppiParams(N, H, I, int(st["update_sigma"]), st["temperature"], st["alpha"], st["lo"], st["hi"],
+                                 0.0, st["init_std"], pkey[-1])
+        need = lib.mbrl_mppi_workspace_bytes(fused.ctypes_ref(prob.shape), fused.ctypes_ref(params))
+        if need == 0:
+            _lib.check(_lib.MBRL_EINVAL, "mbrl_mppi_workspace_bytes")
+        if len(prob.plan_cache) > 64:
+            prob.plan_cache.clear()
+        hit = prob.plan_cache[pkey] = (params, fused.ctypes_ref(params), need)
+    params, pref, need = hit
+    ws = _workspace(("mppi", str(dev)), need, dev)
+    s0 = initial_state.to(device=dev, dtype=torch.float32).contiguous()
+    rows_d = None if rows is None else torch.from_numpy(np.ascontiguousarray(rows)).to(dev)
+    buf = torch.empty(H * (s + 3 * a), dtype=torch.float32, device=dev)
+    both = buf[:H * (s + a)]
+    states = both[:H * s].view(H, s)
+    actions = both[H * s:].view(H, a)
+    mu = buf[H * (s + a):H * (s + 2 * a)].view(H, a)
+    sigma = buf[H * (s + 2 * a):].view(H, a)
+    rec = st["record"]
+    cost_hist = torch.empty((I, E, N), dtype=torch.float32, device=dev) if rec else None
+    w_hist = torch.empty((I, N), dtype=torch.float32, device=dev) if rec else None
+    mu_hist = torch.empty((I + 1, H, a), dtype=torch.float32, device=dev) if rec else None
+    sg_hist = torch.empty((I + 1, H, a), dtype=torch.float32, device=dev) if rec else None
+    pev = st["plan_events"]
+    if pev is not None:
+        pev[0].record()
+    _lib.check(lib.mbrl_mppi_plan(*prob.refs, _lib.ptr(s0), pref, _lib.ptr(rows_d), _lib.ptr(mu), _lib.ptr(sigma),
+                                  _lib.ptr(actions), _lib.ptr(states), _lib.ptr(cost_hist), _lib.ptr(w_hist),
+                                  _lib.ptr(mu_hist), _lib.ptr(sg_hist), _events(st, I), _lib.ptr(ws), ws.numel(),
+                                  _lib.stream_handle(dev)), "mbrl_mppi_plan")
+    if pev is not None:
+        pev[1].record()
+    out = dict(states=states, actions=actions, mu=mu, sigma=sigma, _both=both)
+    if rec:
+        out.update(costs=cost_hist, weights=w_hist, mu_hist=mu_hist, sigma_hist=sg_hist)
+    return out
+
+
+def _mppi_generic(model, cost, s0, st, a, dev, rows):
+    """MPPI with opaque callables: HIP proposal draw, the callables on device tensors, then the HIP
+    weighted update (mbrl_mppi_update), as selection and refit stay in the extension for CEM."""
+    N, H, I = st["N"], st["H"], st["I"]
+    if rows is None:
+        mu = torch.zeros((H, a), dtype=torch.float32, device=dev)
+    else:
+        mu = torch.from_numpy(np.ascontiguousarray(rows)).to(dev)
+    sigma = torch.full((H, a), st["init_std"], dtype=torch.float32, device=dev)
+    mu_n, sigma_n = torch.empty_like(mu), torch.empty_like(sigma)
+    acts = torch.empty((H, N, a), dtype=torch.float32, device=dev)
+    rec = st["record"]
+    hist = dict(costs=[], weights=[], mu_hist=[mu.clone()], sigma_hist=[sigma.clone()])
+    for it in range(I):
+        sp = fused.make_sampler(st["seed"], it, mu, sigma, st["lo"], st["hi"])
+        fused.sample_actions(sp, H, a, N, 0, acts)
+        costs, _ = _generic_costs(model, cost, s0, acts, H, N)
+        wts = torch.empty(N, dtype=torch.float32, device=dev) if rec else None
+        fused.mppi_update(costs, acts, sp, H, a, st["temperature"], st["alpha"], st["update_sigma"], mu_n, sigma_n,
+                          weights_out=wts)
+        mu, mu_n = mu_n, mu
+        sigma, sigma_n = sigma_n, sigma
+        if rec:
+            hist["costs"].append(costs.clone())
+            hist["weights"].append(wts)
+            hist["mu_hist"].append(mu.clone())
+            hist["sigma_hist"].append(sigma.clone())
+    actions = mu.clamp(st["lo"], st["hi"]).contiguous()
+    _, states = _generic_costs(model, cost, s0, actions.view(H, 1, a), H, 1)
+    out = dict(states=states[:, 0, :], actions=actions, mu=mu, sigma=sigma)
+    if rec:
+        out.update({k: torch.stack(v) for k, v in hist.items()})
+    return out
