@@ -166,9 +166,12 @@ def test_select_fuzz_distributions(N):
     """The register-resident selection (wide 11-bit first pass, the bucket's keys listed in LDS, 8-bit
     passes over the list or over every key when the bucket is too large; the bitmap compaction when
     every key equal to the K-th is an elite, the packed-count compaction when ties are cut) against
-    NumPy's stable order on distributions that exercise each branch: plan-like returns in one binade
+    NumPy's stable order on random distributions: plan-like returns in one binade
     (wide, and a few % of it as walker's late iterations), a narrow cluster (the K-th bucket large), heavy ties, NaN- and signed-zero-heavy sets, a wide spread
-    over binades, all-equal keys; K from 1 to N; N not a multiple of 4 for the single-key layout."""
+    over binades, all-equal keys; K from 1 to N; N not a multiple of 4 for the single-key layout.
+    Which branches these draws reach is not checked here (KPT = 2 and 8, the scattered arm of the
+    every-key passes and a short wide pass are not among them): that every branch runs is
+    test_gpu_select_branches.py's claim, on inputs built for it."""
     from mbrl_amd import fused
     rng = np.random.default_rng(N)
     dists = [lambda: rng.uniform(130, 250, N), lambda: rng.uniform(189.3, 192.9, N), lambda: rng.uniform(120, 120.01, N),
