@@ -210,7 +210,14 @@ enum {
                                        elites' regeneration (select + regenerate, then refit + draw): 0 auto
                                        (K ceil(a/4) >= 2048 Philox blocks per row), 1 never, 2 always (A/B,
                                        tests; same bits) */
-    MBRL_OPT_COUNT = 22
+    MBRL_OPT_COUNT = 22,            /* the options of v13's first table (tests/test_abi.py pins it) */
+    /* added within v13, additively, as the MPPI calls were: ids go on from MBRL_OPT_COUNT */
+    MBRL_OPT_ROLLOUT_GROUP_SEAM = 22, /* the 8-wave ring fp32 rollout's hidden-layer hand-offs per half group of
+                                       four waves (two LDS counters) instead of a workgroup barrier: 0 auto
+                                       (on where measured faster: W = 512 with s + a <= 32 and s <= 32,
+                                       DESIGN.md §3.1), 1 on wherever the instance has it (8 waves, W <= 512),
+                                       2 off (A/B, tests; same bits) */
+    MBRL_OPT_END = 23               /* one past the last option id */
 };
 int mbrl_set_option(int32_t option, int32_t value);
 int mbrl_get_option(int32_t option);

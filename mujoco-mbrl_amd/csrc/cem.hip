@@ -29,7 +29,7 @@ namespace mbrl {
 static thread_local std::string g_err;
 
 // mbrl_set_option switches (include/mbrl_cem.h MBRL_OPT_*); 0 = automatic.
-static std::atomic<int> g_opt[MBRL_OPT_COUNT];
+static std::atomic<int> g_opt[MBRL_OPT_END];
 // MBRL_OPT_ROLLOUT_PAIR = 0 (auto) takes column-split pairs for small plans (2 = never, the A/B)
 static constexpr bool kPairAuto = true;
 // traj_coop_kernel hand-off mode under MBRL_OPT_TRAJ_HOP = 0 (TrajArgs.hop_mode)
@@ -1535,6 +1535,14 @@ static int rollout_impl(const Geometry& g, const void* packed, const mbrl_norm* 
     }
     A.actions = actions;
     A.costs = costs; A.states_out = states_out;
+    {
+        // half-group layer hand-offs of the 8-wave ring rollout (rollout.hip GS; same bits). Auto: on for
+        // the instances it was measured on, W = 512 with two layer-0 and two output chunks -- cheetah's
+        // 16- and walker's 32-candidate tiles; every other shape keeps the full barrier
+        const int gs = g_opt[MBRL_OPT_ROLLOUT_GROUP_SEAM].load(std::memory_order_relaxed);
+        const bool gs_auto = g.T == 8 && g.K0C == 2 && g.NOT == 2;
+        A.group_seam = (gs == 1 || (gs == 0 && gs_auto)) ? 1 : 0;
+    }
     // Tile height: two 16-row blocks per workgroup halve the weight stream per FLOP once there are
     // enough candidates to still give every CU a workgroup.
     int R = (N >= 2 * 16 * 256 && g.T <= 8) ? 2 : 1;
@@ -1867,7 +1875,7 @@ const char* mbrl_build_info(void) { return "src=" MBRL_SRC_DIGEST " arch=gfx950"
 const char* mbrl_last_error(void) { return g_err.c_str(); }
 
 int mbrl_set_option(int32_t option, int32_t value) {
-    if (option < 0 || option >= MBRL_OPT_COUNT) return fail(MBRL_EINVAL, "unknown option %d", option);
+    if (option < 0 || option >= MBRL_OPT_END) return fail(MBRL_EINVAL, "unknown option %d", option);
     bool ok = false;
     switch (option) {
         case MBRL_OPT_ROLLOUT_TILE: ok = value == 0 || value == 4 || value == 8 || value == 16; break;
@@ -1883,6 +1891,7 @@ int mbrl_set_option(int32_t option, int32_t value) {
         case MBRL_OPT_DEBUG_SHARD_FAIL_RANK: ok = value >= 0 && value <= 1 << 20; break;
         case MBRL_OPT_SHARD_EMULATE: ok = value >= 0 && value <= 2; break;
         case MBRL_OPT_UPDATE_SPLIT: ok = value >= 0 && value <= 2; break;
+        case MBRL_OPT_ROLLOUT_GROUP_SEAM: ok = value >= 0 && value <= 2; break;
         default: ok = value == 0 || value == 1; break;
     }
     if (!ok) return fail(MBRL_EINVAL, "option %d: value %d not allowed", option, value);
@@ -1943,7 +1952,7 @@ int mbrl_event_destroy(mbrl_event_t event) {
 }
 
 int mbrl_get_option(int32_t option) {
-    if (option < 0 || option >= MBRL_OPT_COUNT) return fail(MBRL_EINVAL, "unknown option %d", option);
+    if (option < 0 || option >= MBRL_OPT_END) return fail(MBRL_EINVAL, "unknown option %d", option);
     return g_opt[option].load();
 }
 

@@ -177,6 +177,9 @@ struct RolloutArgs {
     // epoch: one of its hand-offs timed out)
     const unsigned* gate;
     unsigned gate_epoch;
+    // 8-wave ring instances of rollout_kernel: hidden-layer hand-offs per half group of four waves
+    // instead of a full barrier (MBRL_OPT_ROLLOUT_GROUP_SEAM; same bits)
+    int group_seam;
 };
 
 // Hand-offs one pair launch makes at most (rollout.hip: a layer hand-off per hidden layer after layer

@@ -315,6 +315,21 @@ __device__ __forceinline__ void lds_wait_ge(const uint32_t* w, uint32_t need) {
     asm volatile("" ::: "memory");
 }
 
+// hidden_store for the half-group seam (rollout_kernel GS): no barrier. The wave stores its columns,
+// waits for its own LDS writes, releases them at workgroup scope and counts itself into its half's
+// monotonic LDS counter `cnt`; it goes on once all four waves of its half have stored this layer
+// (`need` = 4 x the seams so far). The other half's columns are waited for where they are first read
+// (MBRL_HIDDEN_CHUNK). All eight waves are resident together, so the waits cannot deadlock.
+template <int T, int R>
+__device__ __forceinline__ void hidden_store_half(const f32x4 (&acc)[R][T], const f32x4 (&bias)[T], float* out,
+                                                  int lda, int wave, int lane, uint32_t* cnt, uint32_t need) {
+    hidden_store_nobar<T, R>(acc, bias, out, lda, wave, lane);
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    if (lane == 0) __hip_atomic_fetch_add((lu32*)cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    lds_wait_ge(cnt, need);
+}
+
 // This hand-off wave's stores are drained; count it in (LDS word arr, the ns-th signal of the launch)
 // and let the last of the four set the workgroup's flag to `value` (l2: both halves on one XCD, an
 // L2-resident store; else sc1).
@@ -364,7 +379,9 @@ __device__ __forceinline__ void pair_await(gu32* pflag, uint32_t* go, unsigned b
 // NW = 8 two waves share a SIMD: while one issues its weight loads the other keeps the matrix pipe
 // busy (a wave's own VMEM issue otherwise stalls its MFMA stream ~10 %: tools/ubench). The epilogue
 // (per-candidate VALU work) runs on waves 0-3.
-template <int T, int R, int K0C_T, int NOT_T, int NW, bool PAIR = false>
+// GS (half-group seam; 8 waves, ring, not PAIR): the hidden-layer hand-offs release each half of the
+// waves on its own instead of through a full barrier -- see the seam comment in the step loop.
+template <int T, int R, int K0C_T, int NOT_T, int NW, bool PAIR = false, bool GS = false>
 __global__ void __launch_bounds__(64 * NW, 1) rollout_kernel(const RolloutArgs A) {
     constexpr int M = 16 * R;
     constexpr int TW = 4 * T / NW;
@@ -379,6 +396,7 @@ __global__ void __launch_bounds__(64 * NW, 1) rollout_kernel(const RolloutArgs A
     constexpr bool EREG = SS <= MBRL_EPI_REG_SLOTS && !(R == 2 && NW == 8);
     static_assert(!RING || ((K0C_T + NOT_T) % NB == 0 && K0C_T % 2 == 0 && NOT_T % 2 == 0), "ring layout");
     static_assert(!PAIR || (NW == 8 && R == 1 && RING && T % 2 == 0), "column-split pairs: 8 waves, 16 rows");
+    static_assert(!GS || (!PAIR && NW == 8 && RING), "half-group seam: the 8-wave ring instances");
     constexpr bool L0DUP = PAIR && K0C_T == 2;   // PAIR: layer 0 computed by both halves (below)
     // LDS row strides: compile-time for the ring instances (make_geometry: lda = max(Wpad, 16 K0C) + 4,
     // pw = 16 NOT + 4; the launcher checks them), so every LDS address of a row block, partial or
@@ -489,6 +507,11 @@ __global__ void __launch_bounds__(64 * NW, 1) rollout_kernel(const RolloutArgs A
     // partner's columns are K positions [2T, 4T) of every hidden layer for either half.
     [[maybe_unused]] const int pwait = PAIR ? 2 * T : -1;   // first K position of the partner's columns
     [[maybe_unused]] uint32_t xneed = 0;                                   // hand-offs consumed so far
+    // GS: lflag[4 + h] counts the stores of half h's four waves over the launch (zeroed above: 4, 5 < NW);
+    // gneed = 4 x the seams this wave has stored, the value both counters reach once that seam is complete
+    [[maybe_unused]] uint32_t* const gown = lflag + 4 + (2 * cw >= NW ? 1 : 0);
+    [[maybe_unused]] uint32_t* const gother = lflag + 4 + (2 * cw >= NW ? 0 : 1);
+    [[maybe_unused]] uint32_t gneed = 0;
     if constexpr (PAIR) {
         if (wave >= 4) {
             // ---- hand-off waves: per step the same barriers as the compute waves, and after each one
@@ -694,6 +717,7 @@ __global__ void __launch_bounds__(64 * NW, 1) rollout_kernel(const RolloutArgs A
     do {                                                                             \
         MBRL_LOAD_CHUNK(ring[((SLOT) + NB - 1) % NB], g + NB - 1);                   \
         if (PAIR && (KC) + 1 == pwl) lds_wait_ge(lflag, 4 * ++xneed);               \
+        if (GS && (KC) + 1 == 2 * T) lds_wait_ge(gother, gneed);                     \
         if ((KC) + 1 < (NK)) read_a<R>(aAB[((KC) + 1) & 1], IN, lda, (KC) + 1, lane); \
         mma_hidden<TW, R>(acc, aAB[(KC) & 1], ring[SLOT]);                           \
         MBRL_PIN();                                                                  \
@@ -742,6 +766,26 @@ __global__ void __launch_bounds__(64 * NW, 1) rollout_kernel(const RolloutArgs A
                 for (int kc = 0; kc < K0C_T; ++kc)
                     if (16 * kc < A.s + A.a) mma_hidden<TW, R>(acc, aAB[kc & 1], w0p[kc]);
                 hidden_store<TW, R>(acc, bias, actY, lda, ocw0, lane);
+            } else if constexpr (GS) {
+                // Half-group seam. The W->W layers run the half-rotated K order (rof), so the first 2T
+                // chunks of the next layer read only columns this wave's own half stored: the wave goes on
+                // once its half's four waves have stored (gown), and waits for the other half (gother)
+                // before the read_a of K position 2T (MBRL_HIDDEN_CHUNK). Same MFMA order, same bits.
+                // Why the ping-pong buffers stay safe without the full barrier, for every depth L: a
+                // wave that stores layer l + 1 (or, after the last hidden layer, its output partials)
+                // has passed layer l + 1's mid-layer wait, so all eight waves have stored layer l, so
+                // all eight have finished layer l's K loop and with it every read of layer l's input --
+                // the buffer layer l + 1's store overwrites (their ds_reads returned before their
+                // store's lgkmcnt(0)). L = 2: layer 0 -> Y is the only seam; the partials have their own
+                // area. L = 3: layer 1 -> X overwrites layer 0's input once all stored layer 0; the
+                // partials alias Y (part_alias; also the 32-candidate instance), which layer 1 read, and
+                // a wave writing partials has passed layer 2's mid-layer wait: all stored layer 1, none
+                // reads Y any more. L = 4: layer 1 -> X and layer 2 -> Y as above, each one layer behind
+                // its last reader; partials in their own area (L even). The step's first store (layer 0
+                // -> Y) follows the full barrier after the epilogue, which stays, as does the one after
+                // the output partials: the epilogue reads every wave's partials and rewrites X.
+                gneed += 4;
+                hidden_store_half<TW, R>(acc, bias, actY, lda, cw, lane, gown, gneed);
             } else {
                 hidden_store<TW, R>(acc, bias, actY, lda, cw, lane);
             }
@@ -763,7 +807,14 @@ __global__ void __launch_bounds__(64 * NW, 1) rollout_kernel(const RolloutArgs A
 #pragma unroll
             for (int kc = 0; kc < KH; ++kc) MBRL_HIDDEN_CHUNK((S0 + kc) % NB, kc, KH, (kc + 1 < KH / 2 ? inLo : inHi));
             STAMP(2);
-            if (l + 1 < A.L) hidden_store<TW, R>(acc, bias, out, lda, cw, lane);
+            if constexpr (GS) {
+                if (l + 1 < A.L) {
+                    gneed += 4;
+                    hidden_store_half<TW, R>(acc, bias, out, lda, cw, lane, gown, gneed);
+                }
+            } else {
+                if (l + 1 < A.L) hidden_store<TW, R>(acc, bias, out, lda, cw, lane);
+            }
             STAMP(3);
             float* tmp = in; in = out; out = tmp;
         }
@@ -926,8 +977,13 @@ static bool ring_strides_ok(const RolloutArgs& A) {
     else return A.lda == (64 * T > 16 * K0C_T ? 64 * T : 16 * K0C_T) + 4 && A.pw == 16 * NOT_T + 4;
 }
 
-template <int T, int R, int K0C_T, int NOT_T, int NW>
+template <int T, int R, int K0C_T, int NOT_T, int NW, bool GS = false>
 static hipError_t launch_rollout_tr(const RolloutArgs& A_in, hipStream_t stream) {
+    // the half-group seam (RolloutArgs.group_seam) exists for the 8-wave ring instances up to W = 512
+    // (T = 16 already spills at 256 VGPRs, and the seam's extra live values spill more)
+    if constexpr (!GS && NW == 8 && K0C_T > 0 && T <= 8) {
+        if (A_in.group_seam) return launch_rollout_tr<T, R, K0C_T, NOT_T, NW, true>(A_in, stream);
+    }
     RolloutArgs A = A_in;
     A.nw = NW;
     if (!ring_strides_ok<T, K0C_T, NOT_T>(A)) return hipErrorInvalidValue;
@@ -935,10 +991,10 @@ static hipError_t launch_rollout_tr(const RolloutArgs& A_in, hipStream_t stream)
     const int ntiles = (A.N + M - 1) / M;
     const dim3 grid = A.xcd_map ? dim3(ntiles * A.E) : dim3(ntiles, A.E);
     const size_t lds = rollout_lds_bytes(A, M);
-    hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(&rollout_kernel<T, R, K0C_T, NOT_T, NW>),
-                                      160 * 1024);
+    const auto fn = &rollout_kernel<T, R, K0C_T, NOT_T, NW, false, GS>;
+    hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(fn), 160 * 1024);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((rollout_kernel<T, R, K0C_T, NOT_T, NW>), grid, dim3(64 * NW), lds, stream, A);
+    hipLaunchKernelGGL(fn, grid, dim3(64 * NW), lds, stream, A);
     return hipGetLastError();
 }
 
