@@ -281,15 +281,15 @@ inline size_t rollout_lds_bytes(const RolloutArgs& A, int M) {
     return need > floor_bytes ? need : floor_bytes;
 }
 
-// Compute units of the current device (cached; cem.hip).
+// Compute units of the current device (cached; host.hip).
 int device_cu_count();
 
 // Raise `fn`'s dynamic-LDS limit to `bytes` on the current device, once per (kernel, device,
-// bytes); thread-safe (cem.hip).
+// bytes); thread-safe (host.hip).
 hipError_t ensure_dynamic_lds(const void* fn, int bytes);
 
 // Whether `blocks` workgroups of kernel `fn` (threads each, `lds` bytes of dynamic LDS) can all be
-// resident on the current device at once (occupancy query x CU count, cached; cem.hip). Kernels with
+// resident on the current device at once (occupancy query x CU count, cached; host.hip). Kernels with
 // grid-wide hand-offs check it and return hipErrorCooperativeLaunchTooLarge instead of launching.
 bool grid_fits(const void* fn, int threads, size_t lds, int blocks);
 
@@ -337,6 +337,53 @@ struct TrajArgs {
 };
 hipError_t launch_traj(const TrajArgs& A, int E, hipStream_t stream);
 
+// ---- CEM kernels' launchers (cem.hip). Those returning int give an MBRL_* code with the thread's
+// error message set (mbrl_host.h).
+// The fused per-iteration update (cem_update_kernel, or its two-launch split).
+struct UpdateArgs {
+    const float* costs;
+    int E, N, K, member_stride, H, a;
+    int64_t* elite_out;          // [B][K] local indices (block t = 0 of each problem writes them), or NULL
+    float* returns_out;          // [B][N] member-mean returns (block t = 0), or NULL
+    uint64_t seed;
+    int iteration;
+    const float *mu, *sigma;     // [B][H][a] this iteration's distribution
+    float lo, hi, alpha, oma;
+    float *mu_out, *sigma_out;   // [B][H][a] the refit
+    float *fin_mu, *fin_sigma, *fin_actions;   // last iteration: plan outputs (or NULL)
+    float* next_actions;         // [H][B*draw_n][a] proposals of iteration + 1, or NULL
+    int draw_off, draw_n;        // problem b draws candidates b*N + draw_off + [0, draw_n) (a plan: 0, N)
+    float* ael;                  // split update (B == 1): [H][K][a] the elites' actions between its launches
+};
+// KPT of the fused update's register-resident selection, 0 where the update does not fuse.
+int update_kpt(int N, int K, int a);
+// Whether the update also draws the next iteration's proposals.
+bool update_samples(int N, int a);
+// Candidate slices per row of a fused draw.
+int draw_slices(int H, int B, int N, int a);
+int update_impl(const UpdateArgs& U, int B, hipStream_t stream);
+int select_impl(const float* costs, int E, int N, int K, int nan_policy, int64_t* elite_idx, float* returns_out,
+                void* ws, size_t ws_bytes, hipStream_t stream, int segments = 1);
+int refit_impl(const mbrl_sampler* sp, int H, int a, const int64_t* elite_idx, int K, float alpha, float* aelite,
+               float* mu_out, float* sigma_out, hipStream_t stream, float* fin_mu = nullptr,
+               float* fin_sigma = nullptr, float* fin_actions = nullptr, int B = 1, int n_env = 0);
+int sample_impl(const mbrl_sampler* sp, int H, int a, int N, int n_offset, float* out, hipStream_t stream,
+                int n_env = 0);
+// The hand-off words a plan's first launch zeroes (cem_init_kernel; plan.hip plan_zero).
+struct InitZero {
+    unsigned* ptr[2];
+    size_t words[2];
+};
+// The plan's first launch (cem_init_kernel; mu_rows: the MPPI plan's warm start, or NULL). Errors are
+// left to the caller's hipGetLastError.
+void launch_cem_init(dim3 grid, hipStream_t stream, uint64_t seed, float init_mu, float init_sigma, float lo, float hi,
+                     int H, int a, int N, float* mu, float* sigma, float* actions, const float* s0_src, int s,
+                     float* s0_dst, int draw_off, const InitZero& zero, const float* mu_rows);
+// MBRL_OPT_SHARD_EMULATE 2 (plan_sharded.hip): the all-gather's buffers in one launch. The kernel
+// stays in cem.hip with the stamp buffer it writes in the diagnostic build.
+void launch_emu_gather(const float* local, const float* kept, int G, int rank, size_t slot, const unsigned* own_status,
+                       const unsigned* own_pair, float* gathered, unsigned* peer, hipStream_t stream);
+
 // MPPI update (mppi.hip): one launch per iteration after the rollout. Workgroup (t * S + j) forms the
 // member-mean returns, their minimum and the softmax weights for all N, then the weighted chunked sums
 // of row t of `actions`; slice j == 0 writes the row's new mu / sigma, every slice draws its share of
@@ -360,6 +407,13 @@ struct MppiArgs {
 };
 size_t mppi_update_lds_bytes(int N, int a);
 hipError_t launch_mppi_update(const MppiArgs& A, int S, hipStream_t stream);
+// The fill mbrl_mppi_update and mbrl_mppi_plan (plan.hip) share: one update of `sp`'s distribution over
+// all N candidates; the caller adds the fin_* / *_out diagnostics and the next proposals' draw.
+MppiArgs make_mppi_args(const float* costs, int E, int N, int H, int a, const float* actions, const mbrl_sampler& sp,
+                        float temperature, float alpha, int update_sigma, float* mu_out, float* sigma_out);
+// Argument checks of both (MBRL_* code, message set).
+int mppi_temperature_check(float temperature);
+int mppi_range_check(int N, int a);
 
 // Fused gradient-descent planner (gd.hip): one persistent workgroup runs every Adam iteration of
 // planners.py:103-137 (goal-state cost, one ensemble member).

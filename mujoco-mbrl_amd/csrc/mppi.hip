@@ -26,7 +26,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "mbrl_internal.h"
+#include "mbrl_host.h"
 #include "mbrl_rng.h"
 #include "mbrl_wave.h"
 
@@ -300,4 +300,54 @@ hipError_t launch_mppi_update(const MppiArgs& A, int S, hipStream_t stream) {
     return hipGetLastError();
 }
 
+MppiArgs make_mppi_args(const float* costs, int E, int N, int H, int a, const float* actions, const mbrl_sampler& sp,
+                        float temperature, float alpha, int update_sigma, float* mu_out, float* sigma_out) {
+    MppiArgs U{};
+    U.costs = costs; U.E = E; U.N = N; U.H = H; U.a = a; U.actions = actions;
+    U.seed = sp.seed; U.iteration = sp.iteration; U.mu = sp.mu; U.sigma = sp.sigma;
+    U.lo = sp.lo; U.hi = sp.hi; U.alpha = alpha; U.oma = 1.0f - alpha; U.temperature = temperature;
+    U.update_sigma = update_sigma != 0;
+    U.mu_out = mu_out; U.sigma_out = sigma_out;
+    U.draw_off = 0; U.draw_n = N;
+    return U;
+}
+
+int mppi_temperature_check(float temperature) {
+    if (!(temperature > 0.0f) || temperature > 3.402823466e+38f)
+        return fail(MBRL_EINVAL, "mppi: temperature %g must be finite and > 0", (double)temperature);
+    return MBRL_OK;
+}
+
+int mppi_range_check(int N, int a) {
+    if (N > MPPI_MAX_N || a > MPPI_MAX_A)
+        return fail(MBRL_EUNSUPPORTED, "mppi: N=%d a=%d exceeds the update kernel (N <= %d, a <= %d)", N, a, MPPI_MAX_N,
+                    MPPI_MAX_A);
+    return MBRL_OK;
+}
+
 }  // namespace mbrl
+
+using namespace mbrl;
+
+extern "C" int mbrl_mppi_update(const float* costs, int32_t E, int32_t N, const float* actions,
+                                const mbrl_sampler* sampler, int32_t H, int32_t a, float temperature, float alpha,
+                                int32_t update_sigma, float* mu_out, float* sigma_out, float* weights_out,
+                                float* returns_out, float* stats_out, float* next_actions, int32_t draw_offset,
+                                int32_t draw_count, mbrl_stream_t stream) {
+    if (!costs || !actions || !sampler || !sampler->mu || !sampler->sigma || !mu_out || !sigma_out)
+        return fail(MBRL_EINVAL, "mppi_update: NULL argument");
+    if (N < 1 || E < 1 || H < 1 || a < 1) return fail(MBRL_EINVAL, "mppi_update: need N (%d), E, H, a >= 1", N);
+    if (int rc = mppi_temperature_check(temperature)) return rc;
+    if (next_actions && (draw_count < 1 || draw_offset < 0 || (int64_t)draw_offset + draw_count > N))
+        return fail(MBRL_EINVAL, "mppi_update: draw range [%d, %d + %d) outside [0, %d)", draw_offset, draw_offset,
+                    draw_count, N);
+    if (next_actions == actions)
+        return fail(MBRL_EINVAL, "mppi_update: next_actions must not be the actions buffer (other workgroups still read it)");
+    if (int rc = mppi_range_check(N, a)) return rc;
+    MppiArgs U = make_mppi_args(costs, E, N, H, a, actions, *sampler, temperature, alpha, update_sigma, mu_out, sigma_out);
+    U.weights_out = weights_out; U.returns_out = returns_out; U.stats_out = stats_out;
+    if (next_actions) { U.next_actions = next_actions; U.draw_off = draw_offset; U.draw_n = draw_count; }
+    const int S = next_actions ? draw_slices(H, 1, draw_count, a) : 1;
+    return hip_check(launch_mppi_update(U, S, reinterpret_cast<hipStream_t>(stream)), "mppi update launch");
+}
+

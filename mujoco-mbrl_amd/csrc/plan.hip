@@ -1,0 +1,722 @@
+// The plans: host dispatch of the rollout and trajectory kernels (rollout_impl, traj_impl), the plan
+// workspaces, the helpers the plan loops share (mbrl_plan.h) and the single-GPU plan entries
+// (include/mbrl_cem.h): rollout cost, trajectory, CEM plan, MPPI plan, batched CEM plan.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "mbrl_plan.h"
+
+namespace mbrl {
+
+// MBRL_OPT_ROLLOUT_PAIR = 0 (auto) takes column-split pairs for small plans (2 = never, the A/B)
+static constexpr bool kPairAuto = true;
+
+__global__ void fill2_kernel(float* __restrict__ x, float vx, float* __restrict__ y, float vy, int n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) { x[i] = vx; y[i] = vy; }
+}
+
+__global__ void member_mean_kernel(const float* __restrict__ src, int E, int n, float* __restrict__ dst) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) {
+        float acc = src[i];
+        for (int e = 1; e < E; ++e) acc = __fadd_rn(acc, src[(size_t)e * n + i]);
+        dst[i] = E > 1 ? __fdiv_rn(acc, (float)E) : acc;
+    }
+}
+
+__global__ void expand_rows_kernel(const float* __restrict__ src, int B, int n_rep, int s, float* __restrict__ dst) {
+    const size_t total = (size_t)B * n_rep * s;
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const size_t row = i / s;
+        dst[i] = src[(row / n_rep) * s + (i - row * s)];
+    }
+}
+
+// (0: Wpad != 512, or more than 256 workgroups, the co-resident count of the 256-CU MI355X)
+size_t pair_area_bytes(const Geometry& g, int N) {
+    const int ntiles = (N + 15) / 16;
+    if (g.T != 8 || (size_t)2 * ntiles * g.E > 256) return 0;
+    return pair_layout(g.Wpad, g.pw, ntiles, g.E).bytes;
+}
+
+int pair_forced_check(const Geometry& g, int N) {
+    if (opt(MBRL_OPT_ROLLOUT_PAIR) == 1 && pair_area_bytes(g, N) == 0)
+        return fail(MBRL_EUNSUPPORTED, "rollout_pair forced: no pair kernel for N=%d (Wpad %d, E %d)", N, g.Wpad, g.E);
+    return MBRL_OK;
+}
+
+// The hand-off words a plan's first launch zeroes (cem_init_kernel): the pair flags of a shard of Nl
+// candidates (when the workspace offers pairs) and the trajectory kernel's granules with the status
+// word right behind them (the workspaces lay them out so; else the trajectory launch keeps its memset).
+InitZero plan_zero(const Geometry& g, int Nl, void* pair, const TrajScratch& ts) {
+    InitZero z{};
+    if (pair && pair_area_bytes(g, Nl)) {
+        z.ptr[0] = static_cast<unsigned*>(pair);
+        z.words[0] = pair_layout(g.Wpad, g.pw, (Nl + 15) / 16, g.E).zero_bytes / 4;
+    }
+    if (ts.xchg && ts.status && reinterpret_cast<char*>(ts.status) == reinterpret_cast<char*>(ts.xchg) + ts.xchg_bytes) {
+        z.ptr[1] = reinterpret_cast<unsigned*>(ts.xchg);
+        z.words[1] = (ts.xchg_bytes + 16) / 4;
+    }
+    return z;
+}
+
+// The argument checks of rollout_impl that depend on the problem only (not on N or the buffers): the
+// sharded plan runs them before its first collective.
+int rollout_validate(const Geometry& g, const mbrl_norm* norm, const mbrl_cost* cost) {
+    if (norm) {
+        if (norm->unnormalize_reward && (!norm->rew_mean || !norm->rew_std))
+            return fail(MBRL_EINVAL, "reward unnormalisation requested without rew_mean/rew_std");
+        if ((norm->normalize_state || norm->unnormalize_state) && (!norm->obs_mean || !norm->obs_std))
+            return fail(MBRL_EINVAL, "state normalisation requested without obs_mean/obs_std");
+        if (norm->normalize_action && (!norm->act_mean || !norm->act_std))
+            return fail(MBRL_EINVAL, "action normalisation requested without act_mean/act_std");
+    }
+    if (cost && cost->kind == MBRL_COST_MODEL_REWARD) {
+        if (!g.reward) return fail(MBRL_EINVAL, "MODEL_REWARD cost needs a reward_head model");
+    } else if (cost) {
+        if (cost->kind != MBRL_COST_GOAL_STATE) return fail(MBRL_EUNSUPPORTED, "cost kind %d", cost->kind);
+        if (cost->has_state_cost && (!cost->weights || !cost->goal))
+            return fail(MBRL_EINVAL, "state cost without weights/goal");
+    }
+    if (16 * g.a > 768) return fail(MBRL_EUNSUPPORTED, "action_dim %d too large (max 48)", g.a);
+    return MBRL_OK;
+}
+
+// pair_area: a pair_area_bytes(g, N) block of the caller's workspace, or NULL (no column-split pairs).
+// pair_epoch: NULL (the pair flags are zeroed by a memset before a pair launch), or the plan's counter
+// of pair launches, whose flags its first launch zeroed (cem_init_kernel): each pair launch takes the
+// next epoch (RolloutArgs), and a memset only when the epochs would outgrow the 32-bit flags.
+int rollout_impl(const Geometry& g, const void* packed, const mbrl_norm* norm, const mbrl_cost* cost, const float* s0,
+                 int s0_per_cand, const float* actions, const mbrl_sampler* sampler, int N, int H, int n_offset,
+                 float* costs, float* actions_out, float* states_out, hipStream_t stream, void* pair_area,
+                 unsigned* pair_epoch, const unsigned** pair_status_out) {
+    if (!packed || !s0 || !costs) return fail(MBRL_EINVAL, "packed, s0 and costs must be non-NULL");
+    if (N < 1 || H < 1) return fail(MBRL_EINVAL, "N=%d H=%d must be >= 1", N, H);
+    if (!actions && !sampler) return fail(MBRL_EINVAL, "need either actions or a sampler");
+    if (n_offset < 0) return fail(MBRL_EINVAL, "n_offset=%d < 0", n_offset);
+    if (int rc = rollout_validate(g, norm, cost)) return rc;
+    RolloutArgs A{};
+    A.packed = static_cast<const float*>(packed);
+    A.member_stride = g.member_stride;
+    A.stream_floats = g.stream_floats;
+    A.s = g.s; A.a = g.a; A.L = g.L; A.Wpad = g.Wpad; A.K0C = g.K0C; A.NOT = g.NOT; A.E = g.E;
+    A.chunks_per_step = g.C; A.lda = g.lda; A.pw = g.pw; A.k0pad_extra = 16 * g.K0C - g.s - g.a;
+    A.N = N; A.H = H; A.n_offset = n_offset;
+    if (norm) {
+        A.obs_mean = norm->obs_mean; A.obs_std = norm->obs_std;
+        A.act_mean = norm->act_mean; A.act_std = norm->act_std;
+        A.norm_s = norm->normalize_state; A.unnorm_s = norm->unnormalize_state; A.norm_a = norm->normalize_action;
+        A.unnorm_r = norm->unnormalize_reward; A.rew_mean = norm->rew_mean; A.rew_std = norm->rew_std;
+    }
+    if (cost && cost->kind == MBRL_COST_MODEL_REWARD) {
+        A.reward = 1;
+    } else if (cost) {
+        A.has_sc = cost->has_state_cost; A.has_ac = cost->has_action_cost;
+        A.cw = cost->weights; A.goal = cost->goal;
+        A.alpha_s = cost->alpha_state; A.alpha_s2 = cost->alpha_state * cost->alpha_state;
+        A.alpha_a = cost->alpha_action; A.alpha_a2 = cost->alpha_action * cost->alpha_action;
+    }
+    A.s0 = s0; A.s0_per_cand = s0_per_cand;
+    if (!actions) {
+        // CEM proposal: draw into actions_out first, then roll those actions out
+        if (!actions_out) return fail(MBRL_EINVAL, "a sampled rollout needs actions_out to hold the draw");
+        if (!sampler->mu || !sampler->sigma) return fail(MBRL_EINVAL, "sampler mu/sigma NULL");
+        int rc = sample_impl(sampler, H, g.a, N, n_offset, actions_out, stream);
+        if (rc) return rc;
+        actions = actions_out;
+    }
+    A.actions = actions;
+    A.costs = costs; A.states_out = states_out;
+    {
+        // half-group layer hand-offs of the 8-wave ring rollout (rollout.hip GS; same bits). Auto: on for
+        // the instances it was measured on, W = 512 with two layer-0 and two output chunks -- cheetah's
+        // 16- and walker's 32-candidate tiles; every other shape keeps the full barrier
+        const int gs = opt(MBRL_OPT_ROLLOUT_GROUP_SEAM);
+        const bool gs_auto = g.T == 8 && g.K0C == 2 && g.NOT == 2;
+        A.group_seam = (gs == 1 || (gs == 0 && gs_auto)) ? 1 : 0;
+    }
+    // Tile height: two 16-row blocks per workgroup halve the weight stream per FLOP once there are
+    // enough candidates to still give every CU a workgroup.
+    int R = (N >= 2 * 16 * 256 && g.T <= 8) ? 2 : 1;
+    const int G = (g.a + 3) / 4;
+    (void)G;
+    if (16 * R * g.a > 768) R = 1;
+    // waves per workgroup as launch_rollout_t picks them: 8 for R = 1 (T >= 2), else 4
+    A.nw = (R == 1 && g.T >= 2) ? 8 : 4;
+    if ((g.precision == MBRL_PRECISION_F16X3 || g.precision == MBRL_PRECISION_F16X6) && g.split_ok && !A.reward) {
+        const int P = g.precision == MBRL_PRECISION_F16X6 ? 3 : 2;
+        RolloutArgs S = A;
+        S.split_off = P == 3 ? g.split3_off : g.split_off;
+        S.K0S = g.K0S;
+        S.CS = g.CS;
+        S.sr = P * (g.Wpad > 32 * g.K0S ? g.Wpad : 32 * g.K0S) + 8;
+        S.nw = 8;
+        // 32 candidates per workgroup once that still gives every CU a workgroup (N >= 8192): the
+        // split kernel is bound by the L2 weight stream, which R = 2 halves per candidate. At
+        // N = 4096 R = 2 would idle half the CUs: 0.607 vs 0.571 ms per F16X3 rollout (cheetah, r01).
+        int RS = N >= 256 * 32 ? 2 : 1;
+        if (const int o = opt(MBRL_OPT_SPLIT_TILE)) RS = o == 32 ? 2 : 1;
+        RolloutArgs X = A;                 // the fp32 redo pass at the same tile height
+        X.redo = 1;
+        X.nw = RS == 1 && g.T >= 2 ? 8 : 4;
+        if (RS == 2 && (!rollout_split_supported(S, g.T, 2, P) || rollout_lds_bytes(X, 32) > 160 * 1024)) {
+            RS = 1;
+            X.nw = g.T >= 2 ? 8 : 4;
+        }
+        if (rollout_split_supported(S, g.T, RS, P)) {
+            hipError_t err = launch_rollout_split(S, g.T, RS, P, stream);
+            if (err != hipSuccess) return hip_check(err, "split rollout launch");
+            // fp32 redo of the workgroups that met an operand outside the split range (usually none:
+            // every workgroup reads its candidates' costs and exits)
+            return hip_check(launch_rollout(X, g.T, RS, stream), "split redo launch");
+        }
+    }
+    // ensembles: member-major workgroup order per XCD (mbrl_internal.h xcd_unit), opt-in. The plain
+    // (tile, member) grid already keeps each XCD on one member at a time (consecutive ids of one member
+    // round-robin over the XCDs), so it measured the same (humanoid 75.5 ms either way)
+    A.xcd_map = (g.E > 1 && opt(MBRL_OPT_XCD_MAP) == 1) ? 1 : 0;
+    // 8-candidate tiles (rollout_m8_kernel, bit-identical sums) when 16-candidate tiles would leave
+    // at least half the CUs idle: the shard of a strong-scaled plan, small plans.
+    // MBRL_OPT_ROLLOUT_TILE = 8 / 16 forces a choice (tests, A/B).
+    // column-split pairs: each 16-candidate tile on two workgroups of half the columns (16x16x4 MFMA at
+    // full clock, half the weight stream per workgroup) where 16-candidate tiles would leave at least
+    // half the CUs idle; opt-in until measured (MBRL_OPT_ROLLOUT_PAIR)
+    if (pair_area && !A.reward && opt(MBRL_OPT_ROLLOUT_TILE) == 0) {
+        const int po = opt(MBRL_OPT_ROLLOUT_PAIR);
+        const int ntiles = (N + 15) / 16;
+        // auto: where the pairs fill more than half the CUs and at most all of them (one workgroup per
+        // CU, all co-resident): the 2048-candidate shard of walker over 8 GPUs, 0.691 vs 0.715-0.722 ms
+        // per rollout on 8-candidate tiles with L2-resident hand-offs (profiles/r04/pair_l2_ab.json);
+        // at 1024 (half the chip) the 8-candidate tiles stay ahead, 0.54 vs 0.69 ms
+        const size_t pw = (size_t)ntiles * g.E * 2, cus = (size_t)device_cu_count();
+        const bool want = po == 1 || (po == 0 && kPairAuto && 2 * pw > cus && pw <= cus);
+        if (want && pair_area_bytes(g, N) != 0) {
+            RolloutArgs P = A;
+            P.pair_flags = static_cast<unsigned*>(pair_area);
+            P.pair_data = reinterpret_cast<float*>(static_cast<char*>(pair_area) +
+                                                   pair_layout(g.Wpad, g.pw, ntiles, g.E).flags_bytes);
+            if (rollout_pair_supported(P, g.T)) {
+                const int dpa = opt(MBRL_OPT_DEBUG_PAIR_ABORT);
+                P.debug_abort = dpa == 1;
+                P.pair_l2 = opt(MBRL_OPT_PAIR_L2) != 2;
+                const unsigned qs = pair_handoffs(H, g.L);
+                if (pair_epoch && (uint64_t)(*pair_epoch + 1) * qs + 16 < (1ull << 31)) {
+                    P.pair_epoch = ++*pair_epoch;   // flags zeroed by the plan's first launch
+                    P.pair_prezeroed = 1;
+                } else {
+                    P.pair_epoch = 1;               // a memset before the launch; the plan restarts its epochs
+                    P.pair_prezeroed = 0;
+                    if (pair_epoch) *pair_epoch = 1;
+                }
+                P.pair_base = (P.pair_epoch - 1) * qs;
+                const hipError_t err = launch_rollout_pair(P, g.T, stream);
+                if (err == hipSuccess && dpa == 2) return MBRL_OK;   // tests: the pair launch's own results
+                if (err == hipSuccess && pair_status_out && P.pair_prezeroed) {
+                    // the caller checks the plan's pair status word once, after the plan (a sharded plan
+                    // with peers: it redoes the whole plan without pairs if any hand-off timed out), so
+                    // no gated redo launch follows each pair launch
+                    *pair_status_out = P.pair_flags + (size_t)2 * ntiles * g.E * 32;
+                    return MBRL_OK;
+                }
+                if (err == hipSuccess) {
+                    // A pair's halves wait on each other, and a plain launch does not promise that both
+                    // are resident (another stream may hold CUs): a wait that timed out raised the status
+                    // word after the flags to the launch's epoch and left its tile's costs invalid. The
+                    // launch chosen below then recomputes every candidate if it did, else its workgroups
+                    // exit at once (bit-identical sums on every tile height).
+                    A.gate = P.pair_flags + (size_t)2 * ntiles * g.E * 32;
+                    A.gate_epoch = P.pair_epoch;
+                } else if (err != hipErrorCooperativeLaunchTooLarge || po == 1) {
+                    return hip_check(err, "rollout pair launch");
+                }
+            } else if (po == 1) {
+                return fail(MBRL_EUNSUPPORTED, "rollout_pair forced: shape not supported by the pair kernel");
+            }
+        } else if (po == 1) {
+            return fail(MBRL_EUNSUPPORTED, "rollout_pair forced: no pair area for N=%d (Wpad %d, E %d)", N, g.Wpad, g.E);
+        }
+    }
+    if (g.m8_ok) {
+        A.m8_off = g.m8_off;
+        A.C8 = g.C8;
+        A.m4_off = g.m4_off;
+        A.C4 = g.C4;
+        const int o = opt(MBRL_OPT_ROLLOUT_TILE);
+        // 4-candidate tiles (rollout_m4_kernel) once 8-candidate tiles would still leave at least half
+        // the CUs idle (cartpole's N = 1024, shards of <= 1024 candidates); both bit-identical
+        bool use4 = false;   // opt-in: slower than 8-candidate tiles at cartpole size
+        bool use8 = (size_t)((N + 15) / 16) * g.E * 2 <= (size_t)device_cu_count();
+        if (o) { use4 = o == 4; use8 = o == 8; }
+        if (use4 && g.m4_ok && rollout_m4_supported(A, g.T, g.NG4))
+            return hip_check(launch_rollout_m4(A, g.T, g.NG4, stream), "rollout m4 launch");
+        if ((use8 || use4) && rollout_m8_supported(A, g.T))
+            return hip_check(launch_rollout_m8(A, g.T, stream), "rollout m8 launch");
+    }
+    // partials in the activation buffer the last hidden layer does not read (rollout.hip): layer 0
+    // writes act2, hidden layer l reads act2 for odd l, so with L odd the last one reads act and act2
+    // is free from the barrier after layer L-2 until the next step's layer 0
+    // 32-candidate tiles on 8 waves (two per SIMD) when the 8 partials fit the aliased activation
+    // buffer: walker rollout 3.91 -> 3.83 ms, frac 0.883 -> 0.901 (profiles/r02_ab_r2_8waves.txt)
+    if (R == 2 && g.T >= 2 && !A.reward && g.L >= 3 && (g.L & 1) && (size_t)8 * g.pw <= (size_t)g.lda) A.nw = 8;
+    auto alias_ok = [&]() {
+        return !A.reward && g.L >= 3 && (g.L & 1) && (size_t)(A.nw > 4 ? A.nw : 4) * g.pw <= (size_t)g.lda;
+    };
+    A.part_alias = alias_ok() ? 1 : 0;
+    if (rollout_lds_bytes(A, 16 * R) > 160 * 1024) {
+        R = 1;
+        A.nw = g.T >= 2 ? 8 : 4;
+        A.part_alias = alias_ok() ? 1 : 0;
+        if (rollout_lds_bytes(A, 16) > 160 * 1024)
+            return fail(MBRL_EUNSUPPORTED, "LDS footprint %zu B exceeds 160 KiB", rollout_lds_bytes(A, 16));
+    }
+    return hip_check(launch_rollout(A, g.T, R, stream), "rollout launch");
+}
+
+// prezeroed: the plan's first launch zeroed the granules and status (cem_init_kernel), so no memset here.
+static int traj_impl(const Geometry& g, const void* packed, const mbrl_norm* norm, const float* s0,
+                     const float* actions, int H, float* states_out, const TrajScratch& ts, hipStream_t stream,
+                     int prezeroed) {
+    TrajArgs T{};
+    T.prezeroed = prezeroed;
+    T.packed = static_cast<const float*>(packed);
+    T.member_stride = g.member_stride;
+    T.bias_off = g.stream_floats;
+    T.tw_base = g.stream_floats + g.bias_floats;
+    for (int l = 0; l <= g.L; ++l) T.tw_off[l] = g.tw_off[l];
+    T.s = g.s; T.a = g.a; T.W = g.W; T.Wpad = g.Wpad; T.L = g.L; T.H = H;
+    if (norm) {
+        T.obs_mean = norm->obs_mean; T.obs_std = norm->obs_std;
+        T.act_mean = norm->act_mean; T.act_std = norm->act_std;
+        T.norm_s = norm->normalize_state; T.unnorm_s = norm->unnormalize_state; T.norm_a = norm->normalize_action;
+    }
+    T.s0 = s0; T.actions = actions; T.states_out = states_out;
+    if (traj_reg_supported(T) && opt(MBRL_OPT_DEBUG_TRAJ_ABORT) == 0)
+        return hip_check(launch_traj_reg(T, g.E, stream), "trajectory launch");
+    if (ts.xchg && ts.status && traj_coop_supported(T, g.E) && ts.xchg_bytes >= traj_coop_xchg_bytes(T, g.E)) {
+        T.debug_abort = opt(MBRL_OPT_DEBUG_TRAJ_ABORT) != 0;
+        const int hop = opt(MBRL_OPT_TRAJ_HOP);
+        T.hop_mode = hop == 0 ? kTrajHopDefault : hop - 1;
+        const hipError_t err = launch_traj_coop(T, g.E, ts.xchg, ts.status, stream);
+        if (err != hipErrorCooperativeLaunchTooLarge) {   // too large: the grid cannot be co-resident
+            int rc = hip_check(err, "trajectory launch");
+            if (rc) return rc;
+            // The cooperative kernel needs its P*E workgroups co-resident; if a hand-off ever timed
+            // out (another process holding CUs, say) it set `status` and gave up. The single-workgroup
+            // kernel then recomputes the states; otherwise its E workgroups read the status word and exit.
+            // (Run inside the cooperative launch instead, the fallback's registers raised the kernel's
+            // from 107 to 161 VGPRs: one workgroup per CU, and two plans' trajectories on one XCD then
+            // waited on each other until the hand-off timeout.)
+            T.gate = ts.status;
+        }
+        T.debug_abort = 0;
+    }
+    return hip_check(launch_traj(T, g.E, stream), "trajectory launch");
+}
+
+// ---- what the plan loops share (mbrl_plan.h)
+TrajScratch take_traj_scratch(WsCursor& c, const Geometry& g) {
+    TrajScratch ts{};
+    ts.xchg_bytes = (size_t)g.E * 2 * g.Wpad * 8;   // a 16-byte multiple
+    ts.xchg = c.take<unsigned long long>(ts.xchg_bytes);
+    ts.status = c.take<unsigned>(16);
+    return ts;
+}
+
+int cem_params_check(const mbrl_cem_params* p) {
+    if (p->N < 1 || p->H < 1 || p->K < 1 || p->K > p->N || p->iterations < 1)
+        return fail(MBRL_EINVAL, "bad CEM params N=%d H=%d K=%d I=%d", p->N, p->H, p->K, p->iterations);
+    return MBRL_OK;
+}
+
+FusePlan fuse_plan(int N_select, int N_draw, int K, int a) {
+    FusePlan f;
+    f.fuse = update_kpt(N_select, K, a) != 0 && opt(MBRL_OPT_UNFUSED_UPDATE) == 0;
+    f.fuse_draw = f.fuse && update_samples(N_draw, a);
+    return f;
+}
+
+int record_rollout_event(mbrl_event_t* events, int idx, hipStream_t stream) {
+    if (!events || !events[idx]) return MBRL_OK;
+    return hip_check(hipEventRecord(reinterpret_cast<hipEvent_t>(events[idx]), stream), "event");
+}
+
+UpdateArgs make_update_args(const Geometry& g, const mbrl_cem_params* p, int it, const float* costs,
+                            const float* mu_cur, const float* sigma_cur, float* mu_next, float* sigma_next,
+                            float* fin_mu, float* fin_sigma, float* fin_actions, float* next_actions) {
+    const bool last = it + 1 == p->iterations;   // the last refit also writes mu / sigma / clip(mu)
+    UpdateArgs U{};
+    U.costs = costs; U.E = g.E; U.N = p->N; U.K = p->K; U.member_stride = p->N; U.H = p->H; U.a = g.a;
+    U.seed = p->seed; U.iteration = it; U.mu = mu_cur; U.sigma = sigma_cur;
+    U.lo = p->lo; U.hi = p->hi; U.alpha = p->alpha; U.oma = 1.0f - p->alpha;
+    U.mu_out = mu_next; U.sigma_out = sigma_next;
+    U.fin_mu = last ? fin_mu : nullptr; U.fin_sigma = last ? fin_sigma : nullptr;
+    U.fin_actions = last ? fin_actions : nullptr;
+    U.next_actions = last ? nullptr : next_actions;
+    U.draw_off = 0; U.draw_n = p->N;
+    return U;
+}
+
+int final_trajectory(const Geometry& g, const void* packed, const mbrl_norm* norm, const float* s0,
+                     const float* actions, int H, float* states_out, float* member_scratch, const TrajScratch& ts,
+                     hipStream_t stream, int prezeroed, float* member_out) {
+    float* per_member = member_out ? member_out : (g.E == 1 ? states_out : member_scratch);
+    if (int rc = traj_impl(g, packed, norm, s0, actions, H, per_member, ts, stream, prezeroed)) return rc;
+    if (per_member != states_out) {
+        const int Hs = H * g.s;
+        hipLaunchKernelGGL(member_mean_kernel, dim3((Hs + 255) / 256), dim3(256), 0, stream, per_member, g.E, Hs,
+                           states_out);
+    }
+    return MBRL_OK;
+}
+
+}  // namespace mbrl
+
+using namespace mbrl;
+
+extern "C" {
+
+int mbrl_rollout_cost(const mbrl_mlp_shape* shape, const void* packed, const mbrl_norm* norm, const mbrl_cost* cost,
+                      const float* s0, int32_t s0_per_candidate, const float* actions, const mbrl_sampler* sampler,
+                      int32_t N, int32_t H, int32_t n_offset, float* costs, float* actions_out, float* states_out,
+                      mbrl_stream_t stream) {
+    Geometry g;
+    int rc = shape_geometry(shape, &g);
+    if (rc) return rc;
+    return rollout_impl(g, packed, norm, cost, s0, s0_per_candidate, actions, sampler, N, H, n_offset, costs,
+                        actions_out, states_out, reinterpret_cast<hipStream_t>(stream));
+}
+
+// Workspace for mbrl_trajectory: the hand-off scratch first, then the per-member states.
+struct TrajWs {
+    TrajScratch traj;
+    float* states;
+    size_t bytes;
+};
+
+static TrajWs traj_ws(const Geometry& g, int H, void* base) {
+    TrajWs w{};
+    WsCursor c(base);
+    w.traj = take_traj_scratch(c, g);
+    w.states = c.take<float>((size_t)g.E * H * g.s * 4);
+    w.bytes = c.off;
+    return w;
+}
+
+size_t mbrl_trajectory_workspace_bytes(const mbrl_mlp_shape* shape, int32_t H) {
+    Geometry g;
+    if (shape_geometry(shape, &g) != MBRL_OK || H < 1) return 0;
+    return traj_ws(g, H, nullptr).bytes;
+}
+
+int mbrl_trajectory(const mbrl_mlp_shape* shape, const void* packed, const mbrl_norm* norm, const float* s0,
+                    const float* actions, int32_t H, float* states_out, float* member_states_out, void* workspace,
+                    size_t ws_bytes, mbrl_stream_t stream_) {
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    Geometry g;
+    int rc = shape_geometry(shape, &g);
+    if (rc) return rc;
+    if (H < 1) return fail(MBRL_EINVAL, "trajectory: H=%d", H);
+    if (!packed || !s0 || !actions || !states_out || !workspace) return fail(MBRL_EINVAL, "trajectory: NULL argument");
+    TrajWs w = traj_ws(g, H, workspace);
+    if (ws_bytes < w.bytes) return fail(MBRL_EWORKSPACE, "trajectory workspace %zu < %zu", ws_bytes, w.bytes);
+    rc = final_trajectory(g, packed, norm, s0, actions, H, states_out, w.states, w.traj, stream, 0, member_states_out);
+    if (rc) return rc;
+    return hip_check(hipGetLastError(), "trajectory launch");
+}
+
+// Workspace layout for mbrl_cem_plan.
+struct PlanWs {
+    float *costs, *mu[2], *sigma[2], *aelite, *states, *tmp_cost, *actions, *s0;
+    void* pair;   // column-split pair exchange area (NULL-sized when pairs are not offered)
+    TrajScratch traj;
+    int64_t* elites;
+    uint32_t* keys;
+    size_t bytes;
+};
+
+static PlanWs plan_ws(const Geometry& g, const mbrl_cem_params* p, void* base) {
+    PlanWs w{};
+    WsCursor c(base);
+    const size_t Ha = (size_t)p->H * g.a;
+    w.costs = c.take<float>((size_t)g.E * p->N * 4);
+    w.actions = c.take<float>((size_t)p->H * p->N * g.a * 4);
+    w.mu[0] = c.take<float>(Ha * 4); w.mu[1] = c.take<float>(Ha * 4);
+    w.sigma[0] = c.take<float>(Ha * 4); w.sigma[1] = c.take<float>(Ha * 4);
+    w.aelite = c.take<float>((size_t)p->H * p->K * g.a * 4);
+    w.states = c.take<float>((size_t)g.E * p->H * g.s * 4);
+    w.tmp_cost = c.take<float>((size_t)g.E * 4);
+    w.elites = c.take<int64_t>((size_t)p->K * 8);
+    w.keys = c.take<uint32_t>((size_t)p->N * 4);
+    w.traj = take_traj_scratch(c, g);
+    w.s0 = c.take<float>((size_t)g.s * 4);
+    w.pair = c.take<char>(pair_area_bytes(g, p->N));
+    w.bytes = c.off;
+    return w;
+}
+
+size_t mbrl_cem_workspace_bytes(const mbrl_mlp_shape* shape, const mbrl_cem_params* params) {
+    Geometry g;
+    if (shape_geometry(shape, &g) != MBRL_OK || !params) return 0;
+    return plan_ws(g, params, nullptr).bytes;
+}
+
+int mbrl_cem_plan(const mbrl_mlp_shape* shape, const void* packed, const mbrl_norm* norm, const mbrl_cost* cost,
+                  const float* s0_in, const mbrl_cem_params* p, float* mu, float* sigma, float* actions_out,
+                  float* states_out, float* cost_hist, float* returns_hist, int64_t* elite_hist,
+                  mbrl_event_t* rollout_events, void* workspace, size_t ws_bytes, mbrl_stream_t stream_) {
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    Geometry g;
+    int rc = shape_geometry(shape, &g);
+    if (rc) return rc;
+    if (!p) return fail(MBRL_EINVAL, "params is NULL");
+    if ((rc = cem_params_check(p))) return rc;
+    if (!actions_out || !states_out || !workspace) return fail(MBRL_EINVAL, "actions_out/states_out/workspace NULL");
+    if (!s0_in) return fail(MBRL_EINVAL, "s0 is NULL");
+    PlanWs w = plan_ws(g, p, workspace);
+    if (ws_bytes < w.bytes) return fail(MBRL_EWORKSPACE, "workspace %zu < %zu", ws_bytes, w.bytes);
+    if ((rc = pair_forced_check(g, p->N))) return rc;
+    const FusePlan f = fuse_plan(p->N, p->N, p->K, g.a);
+    // one first launch: distribution rows, the s0 copy, iteration 0's proposals (where the update
+    // fuses the draw), and the plan's hand-off words zeroed (no memset before the pair / trajectory
+    // launches)
+    const InitZero z = plan_zero(g, p->N, w.pair, w.traj);
+    launch_cem_init(dim3(p->H * (f.fuse_draw ? draw_slices(p->H, 1, p->N, g.a) : 1), 1), stream, p->seed, p->init_mu,
+                    p->init_sigma, p->lo, p->hi, p->H, g.a, p->N, w.mu[0], w.sigma[0],
+                    f.fuse_draw ? w.actions : nullptr, s0_in, g.s, w.s0, 0, z, nullptr);
+    unsigned pair_epoch = 0;
+    const float* s0 = w.s0;   // the workspace copy (s0_in may be mapped host memory)
+    int cur = 0;
+    for (int it = 0; it < p->iterations; ++it) {
+        const mbrl_sampler sp = make_sampler(p, it, w.mu[cur], w.sigma[cur]);
+        float* costs = cost_hist ? cost_hist + (size_t)it * g.E * p->N : w.costs;
+        int64_t* elites = elite_hist ? elite_hist + (size_t)it * p->K : w.elites;
+        float* rets = returns_hist ? returns_hist + (size_t)it * p->N : nullptr;
+        if ((rc = record_rollout_event(rollout_events, 2 * it, stream))) return rc;
+        rc = rollout_impl(g, packed, norm, cost, s0, 0, f.fuse_draw ? w.actions : nullptr, f.fuse_draw ? nullptr : &sp,
+                          p->N, p->H, 0, costs, w.actions, nullptr, stream, pair_area_bytes(g, p->N) ? w.pair : nullptr,
+                          z.ptr[0] ? &pair_epoch : nullptr);
+        if (rc) return rc;
+        if ((rc = record_rollout_event(rollout_events, 2 * it + 1, stream))) return rc;
+        if (f.fuse) {
+            UpdateArgs U = make_update_args(g, p, it, costs, w.mu[cur], w.sigma[cur], w.mu[cur ^ 1], w.sigma[cur ^ 1], mu,
+                                            sigma, actions_out, f.fuse_draw ? w.actions : nullptr);
+            U.elite_out = elites; U.returns_out = rets;
+            U.ael = w.aelite;   // (scratch of the split update)
+            rc = update_impl(U, 1, stream);
+        } else {
+            const bool last = it + 1 == p->iterations;   // the last refit also writes mu / sigma / clip(mu)
+            rc = select_impl(costs, g.E, p->N, p->K, MBRL_NAN_LAST, elites, rets, w.keys, align256((size_t)p->N * 4), stream);
+            if (rc) return rc;
+            rc = refit_impl(&sp, p->H, g.a, elites, p->K, p->alpha, w.aelite, w.mu[cur ^ 1], w.sigma[cur ^ 1], stream,
+                            last ? mu : nullptr, last ? sigma : nullptr, last ? actions_out : nullptr);
+        }
+        if (rc) return rc;
+        cur ^= 1;
+    }
+    // final mean's rollout -> predicted states [E][H][s] (E == 1: straight into states_out), member mean
+    rc = final_trajectory(g, packed, norm, s0, actions_out, p->H, states_out, w.states, w.traj, stream,
+                          z.ptr[1] != nullptr);
+    if (rc) return rc;
+    return hip_check(hipGetLastError(), "plan launch");
+}
+
+// Workspace layout for mbrl_mppi_plan (PlanWs without the selection's and the elites' scratch).
+struct MppiWs {
+    float *costs, *mu[2], *sigma[2], *states, *actions[2], *s0;
+    void* pair;
+    TrajScratch traj;
+    size_t bytes;
+};
+
+// actions[2]: where the update draws the next proposals (update_samples) they go to the other buffer --
+// the row's other workgroups are still streaming the proposals the rollout consumed.
+static MppiWs mppi_ws(const Geometry& g, const mbrl_mppi_params* p, void* base) {
+    MppiWs w{};
+    WsCursor c(base);
+    const size_t Ha = (size_t)p->H * g.a;
+    w.costs = c.take<float>((size_t)g.E * p->N * 4);
+    w.actions[0] = c.take<float>((size_t)p->H * p->N * g.a * 4);
+    w.actions[1] = update_samples(p->N, g.a) ? c.take<float>((size_t)p->H * p->N * g.a * 4) : w.actions[0];
+    w.mu[0] = c.take<float>(Ha * 4); w.mu[1] = c.take<float>(Ha * 4);
+    w.sigma[0] = c.take<float>(Ha * 4); w.sigma[1] = c.take<float>(Ha * 4);
+    w.states = c.take<float>((size_t)g.E * p->H * g.s * 4);
+    w.traj = take_traj_scratch(c, g);
+    w.s0 = c.take<float>((size_t)g.s * 4);
+    w.pair = c.take<char>(pair_area_bytes(g, p->N));
+    w.bytes = c.off;
+    return w;
+}
+
+static int mppi_params_check(const mbrl_mppi_params* p) {
+    if (!p) return fail(MBRL_EINVAL, "mppi: params is NULL");
+    if (p->N < 1 || p->H < 1 || p->iterations < 1)
+        return fail(MBRL_EINVAL, "bad MPPI params N=%d H=%d I=%d", p->N, p->H, p->iterations);
+    return mppi_temperature_check(p->temperature);
+}
+
+size_t mbrl_mppi_workspace_bytes(const mbrl_mlp_shape* shape, const mbrl_mppi_params* params) {
+    Geometry g;
+    if (shape_geometry(shape, &g) != MBRL_OK || mppi_params_check(params) != MBRL_OK) return 0;
+    return mppi_ws(g, params, nullptr).bytes;
+}
+
+int mbrl_mppi_plan(const mbrl_mlp_shape* shape, const void* packed, const mbrl_norm* norm, const mbrl_cost* cost,
+                   const float* s0_in, const mbrl_mppi_params* p, const float* init_mu_rows, float* mu, float* sigma,
+                   float* actions_out, float* states_out, float* cost_hist, float* weight_hist, float* mu_hist,
+                   float* sigma_hist, mbrl_event_t* rollout_events, void* workspace, size_t ws_bytes,
+                   mbrl_stream_t stream_) {
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    Geometry g;
+    int rc = shape_geometry(shape, &g);
+    if (rc) return rc;
+    if ((rc = mppi_params_check(p))) return rc;
+    if (!packed || !actions_out || !states_out || !workspace)
+        return fail(MBRL_EINVAL, "mppi_plan: packed/actions_out/states_out/workspace NULL");
+    if (!s0_in) return fail(MBRL_EINVAL, "mppi_plan: s0 is NULL");
+    MppiWs w = mppi_ws(g, p, workspace);
+    if (ws_bytes < w.bytes) return fail(MBRL_EINVAL, "mppi_plan: workspace %zu < %zu", ws_bytes, w.bytes);
+    if ((rc = mppi_range_check(p->N, g.a))) return rc;
+    if ((rc = pair_forced_check(g, p->N))) return rc;
+    // the update draws the next proposals itself where cem_update_kernel would (update_samples)
+    const bool fuse_draw = update_samples(p->N, g.a);
+    const int S = fuse_draw ? draw_slices(p->H, 1, p->N, g.a) : 1;
+    const InitZero z = plan_zero(g, p->N, w.pair, w.traj);
+    launch_cem_init(dim3(p->H * S, 1), stream, p->seed, p->init_mu, p->init_sigma, p->lo, p->hi, p->H, g.a, p->N, w.mu[0],
+                    w.sigma[0], fuse_draw ? w.actions[0] : nullptr, s0_in, g.s, w.s0, 0, z, init_mu_rows);
+    if ((rc = hip_check(hipGetLastError(), "init launch"))) return rc;
+    const size_t Ha = (size_t)p->H * g.a;
+    auto record = [&](int row, int cur) {   // the distribution after `row` updates into the history
+        hipError_t e = hipSuccess;
+        if (mu_hist) e = hipMemcpyAsync(mu_hist + row * Ha, w.mu[cur], Ha * 4, hipMemcpyDeviceToDevice, stream);
+        if (e == hipSuccess && sigma_hist)
+            e = hipMemcpyAsync(sigma_hist + row * Ha, w.sigma[cur], Ha * 4, hipMemcpyDeviceToDevice, stream);
+        return hip_check(e, "history copy");
+    };
+    if ((rc = record(0, 0))) return rc;
+    unsigned pair_epoch = 0;
+    const float* s0 = w.s0;   // the workspace copy (s0_in may be mapped host memory)
+    int cur = 0;
+    for (int it = 0; it < p->iterations; ++it) {
+        const mbrl_sampler sp = make_sampler(p, it, w.mu[cur], w.sigma[cur]);
+        float* costs = cost_hist ? cost_hist + (size_t)it * g.E * p->N : w.costs;
+        if ((rc = record_rollout_event(rollout_events, 2 * it, stream))) return rc;
+        float* acts = w.actions[fuse_draw ? (it & 1) : 0];   // this iteration's proposals
+        rc = rollout_impl(g, packed, norm, cost, s0, 0, fuse_draw ? acts : nullptr, fuse_draw ? nullptr : &sp, p->N,
+                          p->H, 0, costs, acts, nullptr, stream, pair_area_bytes(g, p->N) ? w.pair : nullptr,
+                          z.ptr[0] ? &pair_epoch : nullptr);
+        if (rc) return rc;
+        if ((rc = record_rollout_event(rollout_events, 2 * it + 1, stream))) return rc;
+        const bool last = it + 1 == p->iterations;   // the last update also writes mu / sigma / clip(mu)
+        MppiArgs U = make_mppi_args(costs, g.E, p->N, p->H, g.a, acts, sp, p->temperature, p->alpha, p->update_sigma,
+                                    w.mu[cur ^ 1], w.sigma[cur ^ 1]);
+        U.fin_mu = last ? mu : nullptr; U.fin_sigma = last ? sigma : nullptr; U.fin_actions = last ? actions_out : nullptr;
+        U.weights_out = weight_hist ? weight_hist + (size_t)it * p->N : nullptr;
+        U.next_actions = (fuse_draw && !last) ? w.actions[(it + 1) & 1] : nullptr;
+        rc = hip_check(launch_mppi_update(U, U.next_actions ? S : 1, stream), "mppi update launch");
+        if (rc) return rc;
+        cur ^= 1;
+        if ((rc = record(it + 1, cur))) return rc;
+    }
+    // final mean's rollout -> predicted states [E][H][s] (E == 1: straight into states_out), member mean
+    rc = final_trajectory(g, packed, norm, s0, actions_out, p->H, states_out, w.states, w.traj, stream,
+                          z.ptr[1] != nullptr);
+    if (rc) return rc;
+    return hip_check(hipGetLastError(), "plan launch");
+}
+
+// ---- batched planning: B independent CEM plans (one initial state each) in shared launches.
+struct BatchWs {
+    float *costs, *actions, *mu[2], *sigma[2], *s0x, *states;
+    TrajScratch traj;
+    int64_t* elites;
+    uint32_t* keys;
+    size_t bytes;
+};
+
+static BatchWs batch_ws(const Geometry& g, const mbrl_cem_params* p, int B, void* base) {
+    BatchWs w{};
+    WsCursor c(base);
+    const size_t BN = (size_t)B * p->N, BHa = (size_t)B * p->H * g.a;
+    w.traj = take_traj_scratch(c, g);   // memset block first, status right behind
+    w.costs = c.take<float>((size_t)g.E * BN * 4);
+    w.actions = c.take<float>((size_t)p->H * BN * g.a * 4);
+    w.mu[0] = c.take<float>(BHa * 4); w.mu[1] = c.take<float>(BHa * 4);
+    w.sigma[0] = c.take<float>(BHa * 4); w.sigma[1] = c.take<float>(BHa * 4);
+    w.s0x = c.take<float>(BN * g.s * 4);
+    w.states = c.take<float>((size_t)g.E * p->H * g.s * 4);
+    w.elites = c.take<int64_t>((size_t)B * p->K * 8);
+    w.keys = c.take<uint32_t>(BN * 4);
+    w.bytes = c.off;
+    return w;
+}
+
+size_t mbrl_cem_plan_batch_workspace_bytes(const mbrl_mlp_shape* shape, const mbrl_cem_params* params, int32_t B) {
+    Geometry g;
+    if (shape_geometry(shape, &g) != MBRL_OK || !params || B < 1) return 0;
+    return batch_ws(g, params, B, nullptr).bytes;
+}
+
+int mbrl_cem_plan_batch(const mbrl_mlp_shape* shape, const void* packed, const mbrl_norm* norm, const mbrl_cost* cost,
+                        const float* s0, int32_t B, const mbrl_cem_params* p, float* mu, float* sigma,
+                        float* actions_out, float* states_out, void* workspace, size_t ws_bytes,
+                        mbrl_stream_t stream_) {
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    Geometry g;
+    int rc = shape_geometry(shape, &g);
+    if (rc) return rc;
+    if (!p || B < 1) return fail(MBRL_EINVAL, "params NULL or B=%d", B);
+    if ((rc = cem_params_check(p))) return rc;
+    if ((int64_t)B * p->N > INT32_MAX / 2) return fail(MBRL_EUNSUPPORTED, "B*N too large");
+    if (!s0 || !actions_out || !states_out || !workspace) return fail(MBRL_EINVAL, "s0/actions_out/states_out/workspace NULL");
+    BatchWs w = batch_ws(g, p, B, workspace);
+    if (ws_bytes < w.bytes) return fail(MBRL_EWORKSPACE, "workspace %zu < %zu", ws_bytes, w.bytes);
+    const int BN = B * p->N, BHa = B * p->H * g.a;
+    // as mbrl_cem_plan: one fused update launch per iteration where it fits (grid (H, B))
+    const FusePlan f = fuse_plan(p->N, p->N, p->K, g.a);
+    if (f.fuse_draw)
+        launch_cem_init(dim3(p->H * draw_slices(p->H, B, p->N, g.a), B), stream, p->seed, p->init_mu, p->init_sigma, p->lo,
+                        p->hi, p->H, g.a, p->N, w.mu[0], w.sigma[0], w.actions, nullptr, 0, nullptr, 0, InitZero{}, nullptr);
+    else
+        hipLaunchKernelGGL(fill2_kernel, dim3((BHa + 255) / 256), dim3(256), 0, stream, w.mu[0], p->init_mu,
+                           w.sigma[0], p->init_sigma, BHa);
+    hipLaunchKernelGGL(expand_rows_kernel, dim3(256), dim3(256), 0, stream, s0, B, p->N, g.s, w.s0x);
+    int cur = 0;
+    for (int it = 0; it < p->iterations; ++it) {
+        const mbrl_sampler sp = make_sampler(p, it, w.mu[cur], w.sigma[cur]);
+        // problem b's candidate n is global candidate b*N + n (its Philox counter)
+        if (!f.fuse_draw) {
+            rc = sample_impl(&sp, p->H, g.a, BN, 0, w.actions, stream, p->N);
+            if (rc) return rc;
+        }
+        rc = rollout_impl(g, packed, norm, cost, w.s0x, 1, w.actions, nullptr, BN, p->H, 0, w.costs, nullptr, nullptr,
+                          stream);
+        if (rc) return rc;
+        if (f.fuse) {
+            UpdateArgs U = make_update_args(g, p, it, w.costs, w.mu[cur], w.sigma[cur], w.mu[cur ^ 1], w.sigma[cur ^ 1],
+                                            mu, sigma, actions_out, f.fuse_draw ? w.actions : nullptr);
+            U.member_stride = BN;
+            rc = update_impl(U, B, stream);
+        } else {
+            const bool last = it + 1 == p->iterations;
+            rc = select_impl(w.costs, g.E, p->N, p->K, MBRL_NAN_LAST, w.elites, nullptr, w.keys,
+                             align256((size_t)BN * 4), stream, B);
+            if (rc) return rc;
+            rc = refit_impl(&sp, p->H, g.a, w.elites, p->K, p->alpha, nullptr, w.mu[cur ^ 1], w.sigma[cur ^ 1], stream,
+                            last ? mu : nullptr, last ? sigma : nullptr, last ? actions_out : nullptr, B, p->N);
+        }
+        if (rc) return rc;
+        cur ^= 1;
+    }
+    const size_t Hs = (size_t)p->H * g.s;
+    for (int b = 0; b < B; ++b) {   // each final mean's states (the cooperative trajectory kernel)
+        rc = final_trajectory(g, packed, norm, s0 + (size_t)b * g.s, actions_out + (size_t)b * p->H * g.a, p->H,
+                              states_out + b * Hs, w.states, w.traj, stream, 0);
+        if (rc) return rc;
+    }
+    return hip_check(hipGetLastError(), "batched plan launch");
+}
+
+}  // extern "C"
+

@@ -14,7 +14,7 @@
 //     operand: wave w owns output columns [w*W/NW, (w+1)*W/NW) of each hidden layer; the output
 //     layer splits K over the waves (each wave's own columns, straight from its accumulators) and
 //     reduces through LDS.
-//   * weights are pre-packed (pack kernels in cem.hip) into the exact fragment order each wave
+//   * weights are pre-packed (pack kernels in pack.hip) into the exact fragment order each wave
 //     consumes: one buffer_load_dwordx4 per lane = one 1 KiB coalesced fragment. The per-step
 //     stream (~2.2 MB for 3x512) stays resident in every XCD's 4 MB L2; each wave streams its
 //     slice through a 4-deep register ring that runs 3 chunks ahead across layer and step
@@ -431,7 +431,7 @@ __global__ void __launch_bounds__(64 * NW, 1) rollout_kernel(const RolloutArgs A
         xcd_unit(A.xcd_map, ntiles, tile, e);
     }
     const int cw = PAIR ? 4 * half + wave : wave;   // the 8-wave layout's wave whose columns this one computes
-    // half-rotated K order of the W->W layers (cem.hip rot_chunk): a wave whose columns lie in the
+    // half-rotated K order of the W->W layers (pack.hip rot_chunk): a wave whose columns lie in the
     // second half reads K chunk (kc + 2T) mod 4T at position kc; rof = that offset in floats
     const int rof = 2 * cw >= NW ? 16 * 2 * T : 0;
     if (A.redo) {
@@ -503,7 +503,7 @@ __global__ void __launch_bounds__(64 * NW, 1) rollout_kernel(const RolloutArgs A
 
     // PAIR: lflag[0] counts the hand-off waves' finished partner copies (the compute waves wait on it),
     // lflag[1] their drained publishes, lflag[2] the partner flag value seen by hand-off wave 0.
-    // Both halves run their own K half first (the half-rotated K order, cem.hip rot_chunk): the
+    // Both halves run their own K half first (the half-rotated K order, pack.hip rot_chunk): the
     // partner's columns are K positions [2T, 4T) of every hidden layer for either half.
     [[maybe_unused]] const int pwait = PAIR ? 2 * T : -1;   // first K position of the partner's columns
     [[maybe_unused]] uint32_t xneed = 0;                                   // hand-offs consumed so far
@@ -1093,7 +1093,7 @@ hipError_t launch_rollout_pair(const RolloutArgs& A, int T, hipStream_t stream) 
 // epilogue, operation for operation.
 // Wave w owns hidden features [64 w, 64 w + 64) (two 32-row tiles); T = Wpad / 64 waves. In KP mode
 // (below) wave w owns [32 w, 32 w + 32) of 8 waves.
-// Weight stream (packed by pack_m8_*_kernel in cem.hip): per 16-deep chunk, per wave, 4 x 64 lanes
+// Weight stream (packed by pack_m8_*_kernel in pack.hip): per 16-deep chunk, per wave, 4 x 64 lanes
 // x float4 (load s holds q = 0..3); chunks per step = K0C + (L-1) 4T + NOC (output: 2 K-chunk pairs
 // of the one 32-row tile, or own 4 K chunks x 2-tile pairs), plus DUM ring-alignment slots that
 // reload the last chunk (L2 hits; none for the BASELINE shapes).

@@ -30,7 +30,7 @@
 //     per candidate; chunk kc covers K rows 32kc .. 32kc + 31 in natural order.
 //   * output layer: K split over the 8 waves and fed from registers. A K-chunk pairs two of the
 //     wave's own tiles (2kk, 2kk+1): lane group g's eight k are units {4g..4g+3} of each, exactly
-//     what its accumulators hold; the weight pack uses the same permutation (cem.hip).
+//     what its accumulators hold; the weight pack uses the same permutation (pack.hip).
 // One workgroup = 8 waves = 16 R candidates of one member for all H steps; wave w owns units
 // [w W/8, (w+1) W/8) of every hidden layer (TW = T/2 tiles). Per chunk a wave loads TW P fragments
 // (TW tiles x P pieces, 1 KiB each) through a register ring of 4 slots of TS tiles (TS P fragments),

@@ -16,10 +16,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
 #include <utility>
+#include <vector>
 
-#include "../../include/mbrl_cem.h"
-#include "mbrl_internal.h"
+#include "mbrl_host.h"
 
 namespace mbrl {
 
@@ -1963,3 +1964,150 @@ extern "C" int mbrl_diag_set_train_stamps(void* buf) {
     return (int)hipMemcpyToSymbol(HIP_SYMBOL(mbrl::g_train_stamps), &buf, sizeof(buf));
 }
 #endif
+
+using namespace mbrl;
+
+// ---- ABI entries (include/mbrl_cem.h): argument checks around the launchers above
+extern "C" {
+
+int mbrl_adam_step(const mbrl_adam_tensor* tensors, int32_t count, const mbrl_adam_hparams* hparams,
+                   mbrl_stream_t stream) {
+    if (count < 0 || (count > 0 && !tensors) || !hparams) return fail(MBRL_EINVAL, "adam_step: NULL argument");
+    for (int i = 0; i < count; ++i) {
+        const mbrl_adam_tensor& t = tensors[i];
+        if (t.numel < 0 || (t.numel > 0 && (!t.param || !t.grad || !t.exp_avg || !t.exp_avg_sq)))
+            return fail(MBRL_EINVAL, "adam_step: tensor %d: NULL pointer or negative numel", i);
+    }
+    const int o = opt(MBRL_OPT_ADAM_ARITH);
+    return hip_check(launch_adam_step(tensors, count, *hparams, o ? o - 1 : ADAM_ARITH_TORCH,
+                                      reinterpret_cast<hipStream_t>(stream)), "adam_step");
+}
+
+static int train_shape(const mbrl_train_model* m, TrainShape* t) {
+    if (!m) return fail(MBRL_EINVAL, "train: NULL model");
+    if (m->state_dim < 1 || m->action_dim < 0 || m->hidden < 1 || m->horizon < 1 || m->n_hidden < 1 ||
+        m->n_hidden + 2 > MBRL_TRAIN_MAX_LAYERS || (m->reward_head != 0 && m->reward_head != 1))
+        return fail(MBRL_EINVAL, "train: bad shape (state %d, action %d, hidden %d x %d, horizon %d, reward %d)",
+                    m->state_dim, m->action_dim, m->hidden, m->n_hidden, m->horizon, m->reward_head);
+    t->s = m->state_dim; t->a = m->action_dim; t->W = m->hidden; t->L = m->n_hidden; t->reward = m->reward_head;
+    t->H = m->horizon;
+    t->tile = opt(MBRL_OPT_TRAIN_TILE);
+    t->fold = opt(MBRL_OPT_TRAIN_NO_FOLD) == 0 ? 1 : 0;
+    t->xcd = opt(MBRL_OPT_TRAIN_XCD) == 1 ? 1 : 0;
+    t->split = opt(MBRL_OPT_TRAIN_SPLIT) == 1 ? 1 : 0;
+    t->fo_split = opt(MBRL_OPT_TRAIN_FO) == 1 ? 1 : 0;
+    return MBRL_OK;
+}
+
+size_t mbrl_train_workspace_bytes(const mbrl_train_model* model, int32_t batch) {
+    TrainShape t;
+    if (batch < 1 || train_shape(model, &t) != MBRL_OK) return 0;
+    return train_ws_floats(t, batch) * sizeof(float);
+}
+
+size_t mbrl_train_status_offset(const mbrl_train_model* model, int32_t batch) {
+    TrainShape t;
+    if (batch < 1 || train_shape(model, &t) != MBRL_OK) return (size_t)-1;
+    return train_status_offset(t, batch);
+}
+
+int mbrl_train_grads(const mbrl_train_model* model, const mbrl_train_data* data, const int64_t* batch_idx,
+                     int32_t batch, float* loss_out, void* workspace, size_t ws_bytes, mbrl_stream_t stream) {
+    TrainShape t;
+    if (int rc = train_shape(model, &t)) return rc;
+    if (!data || !batch_idx || !workspace || !data->states || !data->next_states || (t.a > 0 && !data->actions) ||
+        (t.reward && !data->rewards))
+        return fail(MBRL_EINVAL, "train_grads: NULL argument");
+    if (batch < 1 || (int64_t)batch > data->transitions)
+        return fail(MBRL_EINVAL, "train_grads: batch %d outside [1, %lld]", batch, (long long)data->transitions);
+    const int layers = t.L + 1 + t.reward;
+    for (int l = 0; l < layers; ++l)
+        if (!model->weight[l] || !model->bias[l] || !model->weight_grad[l] || !model->bias_grad[l])
+            return fail(MBRL_EINVAL, "train_grads: layer %d: NULL weight, bias or gradient", l);
+    const size_t need = train_ws_floats(t, batch) * sizeof(float);
+    if (ws_bytes < need) return fail(MBRL_EWORKSPACE, "train_grads: workspace %zu < %zu bytes", ws_bytes, need);
+    TrainTensors w{model->weight, model->bias, model->weight_grad, model->bias_grad,
+                   data->states, data->actions, data->next_states, data->rewards};
+    const hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (int rc = hip_check(hipMemsetAsync(workspace, 0, train_counter_bytes(t, batch), st), "train_grads counters"))
+        return rc;
+    return hip_check(launch_train_grads(t, w, batch_idx, batch, loss_out, static_cast<float*>(workspace), st),
+                     "train_grads");
+}
+
+int mbrl_train_epoch(const mbrl_train_model* model, const mbrl_train_data* data, const int64_t* order, int64_t rows,
+                     int32_t batch_size, const mbrl_adam_tensor* tensors, int32_t count,
+                     const mbrl_adam_hparams* hparams, const float* step_sizes, const float* bc2_sqrt, float* losses,
+                     void* workspace, size_t ws_bytes, mbrl_stream_t stream) {
+    TrainShape t;
+    if (int rc = train_shape(model, &t)) return rc;
+    if (!data || !order || !workspace || !data->states || !data->next_states || (t.a > 0 && !data->actions) ||
+        (t.reward && !data->rewards) || !tensors || count < 1 || !hparams || !step_sizes || !bc2_sqrt)
+        return fail(MBRL_EINVAL, "train_epoch: NULL argument");
+    if (batch_size < 1 || rows < 1 || rows > data->transitions)
+        return fail(MBRL_EINVAL, "train_epoch: rows %lld / batch %d outside [1, %lld]", (long long)rows, batch_size,
+                    (long long)data->transitions);
+    const int layers = t.L + 1 + t.reward;
+    for (int l = 0; l < layers; ++l)
+        if (!model->weight[l] || !model->bias[l] || !model->weight_grad[l] || !model->bias_grad[l])
+            return fail(MBRL_EINVAL, "train_epoch: layer %d: NULL weight, bias or gradient", l);
+    for (int i = 0; i < count; ++i)
+        if (tensors[i].numel < 0 || (tensors[i].numel > 0 && (!tensors[i].param || !tensors[i].grad ||
+                                                              !tensors[i].exp_avg || !tensors[i].exp_avg_sq)))
+            return fail(MBRL_EINVAL, "train_epoch: Adam tensor %d: NULL pointer or negative numel", i);
+    const int bs = (int)std::min<int64_t>(batch_size, rows);
+    const size_t need = train_ws_floats(t, bs) * sizeof(float);
+    if (ws_bytes < need) return fail(MBRL_EWORKSPACE, "train_epoch: workspace %zu < %zu bytes", ws_bytes, need);
+    TrainTensors w{model->weight, model->bias, model->weight_grad, model->bias_grad,
+                   data->states, data->actions, data->next_states, data->rewards};
+    const int arith = opt(MBRL_OPT_ADAM_ARITH);
+    const hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    // the tickets and band counters start the epoch at zero whatever the workspace held
+    if (int rc = hip_check(hipMemsetAsync(workspace, 0, train_counter_bytes(t, bs), st), "train_epoch counters"))
+        return rc;
+    std::vector<mbrl_adam_tensor> table(tensors, tensors + count);
+    const int64_t batches = (rows + batch_size - 1) / batch_size;
+    // the Adam step rides in the backward launches when the table is the model's layers in order
+    // (weight, bias per Linear, gradients = the model's buffers); otherwise a separate launch
+    bool fold = count == 2 * layers;
+    for (int l = 0; fold && l < layers; ++l)
+        fold = tensors[2 * l].param == model->weight[l] && tensors[2 * l].grad == model->weight_grad[l] &&
+               tensors[2 * l + 1].param == model->bias[l] && tensors[2 * l + 1].grad == model->bias_grad[l];
+    const int ar = arith ? arith - 1 : ADAM_ARITH_TORCH;
+    // a layer's step the layer-0 fold defers: carried by the next batch's first launch, or launched
+    // after the last batch
+    mbrl_adam_tensor carry[2][4];
+    int carry_n = 0;
+    // the fused step's F gathers the next batch's rows while it runs when both batches are full-size
+    // fused ones (alternating gather slots; the first batch gathers its own)
+    TrainGather gather{};
+    for (int64_t b = 0; b < batches; ++b) {
+        const int n = (int)std::min<int64_t>(batch_size, rows - b * batch_size);
+        const int n_next = b + 1 < batches ? (int)std::min<int64_t>(batch_size, rows - (b + 1) * batch_size) : 0;
+        const bool hand = n_next == n && t.W > 32 && train_fused_applies(t, n);   // (F's second column tiles)
+        gather.idx_next = hand ? order + (b + 1) * batch_size : nullptr;
+        gather.batch_next = hand ? n_next : 0;
+        for (int i = 0; i < count; ++i) {
+            table[i].step_size = step_sizes[b * count + i];
+            table[i].bc2_sqrt = bc2_sqrt[b * count + i];
+        }
+        mbrl_adam_tensor* next = carry[(b + 1) & 1];
+        int next_n = 0;
+        if (int rc = hip_check(launch_train_grads(t, w, order + b * batch_size, n, losses ? losses + 3 * b : nullptr,
+                                                  static_cast<float*>(workspace), st, fold ? table.data() : nullptr,
+                                                  hparams, ar, carry[b & 1], carry_n, next, &next_n, &gather),
+                               "train_epoch grads"))
+            return rc;
+        gather.pre_rows = hand ? 1 : 0;
+        if (hand) gather.slot ^= 1;
+        carry_n = next_n;
+        if (!fold)
+            if (int rc = hip_check(launch_adam_step(table.data(), count, *hparams, ar, st), "train_epoch adam")) return rc;
+    }
+    if (carry_n > 0)
+        if (int rc = hip_check(launch_adam_step(carry[batches & 1], carry_n, *hparams, ar, st), "train_epoch adam tail"))
+            return rc;
+    return MBRL_OK;
+}
+
+}  // extern "C"

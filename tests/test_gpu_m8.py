@@ -2,7 +2,7 @@
 the 16-candidate kernel and the CPU oracle. The two kernels consume every accumulator's k in the
 same order, so their costs and states must agree BIT FOR BIT (that keeps a sharded plan independent
 of the tile height its shard size picks); both stay within the oracle bars of test_gpu_parity.py.
-mbrl_set_option(MBRL_OPT_ROLLOUT_TILE, 8 / 16) forces the tile height (cem.hip rollout_impl)."""
+mbrl_set_option(MBRL_OPT_ROLLOUT_TILE, 8 / 16) forces the tile height (plan.hip rollout_impl)."""
 import numpy as np
 import pytest
 import torch
