@@ -16,10 +16,16 @@ CEMPlanner            -- the CEM hot path of BASELINE.json:
     one RCCL all-gather of the per-candidate returns per iteration; every rank then runs the same
     deterministic selection and refit (the refit regenerates elite actions from the counter RNG,
     so no moment collective is needed and the result is bit-identical for any rank count).
+MPPIPlanner           -- CEM's loop with a softmax-weighted refit over every candidate in place of
+    the elite cut (mbrl_mppi_plan), warm-started from the previous plan.
+GradientDescentPlanner -- the reference's Adam loop on one action sequence (planners.py:28-137).
 
-Both take the fused path when fused.describe_* recognise the model / cost closures; otherwise the
-user's callables run on device tensors (reference semantics, planners.py:199-210) and selection /
-refit still run in the HIP extension.
+All four take the fused path when fused.describe_* (gd.describe) recognise the model / cost closures;
+otherwise the user's callables run on device tensors (reference semantics, planners.py:199-210), with
+selection / refit / the weighted update still in the HIP extension (gradient descent: gd.plan_generic).
+What the CEM and MPPI paths share is written once: _common_settings, _plan_params, _layout /
+_device_outputs / _stage_in / _stage_out (the one output buffer, on the device or in mapped host
+staging), _cem_record_buffers, _mark, _finish and _generic_plan (the loop over opaque callables).
 """
 import contextlib
 import threading
@@ -63,6 +69,40 @@ def _to_host(x, keep_device):
     return x if keep_device else x.cpu()
 
 
+def _finish(res, keep):
+    """The tail of plan_detailed: states and actions to the host (unless `keep`), in ONE device-to-host
+    copy where the path left them side by side in res["_both"] (_device_outputs)."""
+    both = res.pop("_both", None)
+    if both is not None and not keep:
+        host = both.cpu()
+        H, s = res["states"].shape
+        res["states"], res["actions"] = host[:H * s].view(H, s), host[H * s:].view(H, -1)
+    else:
+        res["states"], res["actions"] = _to_host(res["states"], keep), _to_host(res["actions"], keep)
+    return res
+
+
+def _common_settings(defaults, sample_action, horizon, kwargs):
+    """What CEMPlanner and MPPIPlanner read alike: bounds (action_bounds, else the sampler's action_spec,
+    else (-1, 1)), init_std (default (hi - lo) / 4 in float32), seed (None: ONE draw from the global
+    NumPy RNG, like the reference's sampler), alpha, the switches, the timing hooks and the precision."""
+    g = lambda k: kwargs.get(k, defaults[k])  # noqa: E731
+    bounds = g("action_bounds")
+    sdesc = fused.describe_sampler(sample_action) if sample_action is not None else None
+    if bounds is None:
+        bounds = (sdesc[0], sdesc[1]) if sdesc is not None else (-1.0, 1.0)
+    lo, hi = float(bounds[0]), float(bounds[1])
+    init_std = g("init_std")
+    init_std = float(np.float32(hi - lo) / np.float32(4.0)) if init_std is None else float(init_std)
+    seed = g("seed")
+    if seed is None:
+        seed = int(np.random.randint(0, 2 ** 62, dtype=np.int64))
+    return dict(H=int(horizon), alpha=float(g("alpha")), lo=lo, hi=hi, init_std=init_std, seed=seed,
+                keep=bool(g("return_device")), record=bool(kwargs.get("record", False)),
+                events=kwargs.get("rollout_events"), plan_events=kwargs.get("plan_events"),
+                adim=sdesc[2] if sdesc else None, precision=_lib.precision_code(g("precision")))
+
+
 def _generic_costs(model, cost, s0, actions, H, N):
     """planners.py:199-210 with the caller's callables. actions [H, N, a] on the GPU.
 
@@ -104,15 +144,22 @@ class GradientDescentPlanner(ModelPlanner):
     warm_starts = True
 
     @staticmethod
-    def plan(initial_state, model, cost, sample_action, horizon, initial_trajectory=None, **kwargs):
+    def _setup(model, cost, kwargs):
+        """The kwargs, and gd.describe's view of the closures (None without a GPU or when not recognised)."""
         from . import gd
-        num_iterations = int(kwargs.get("num_iterations", GradientDescentPlanner.defaults["num_iterations"]))
-        stop_condition = float(kwargs.get("stop_condition", GradientDescentPlanner.defaults["stop_condition"]))
-        H = int(horizon)
-        mdesc = None
+        d = GradientDescentPlanner.defaults
+        num_iterations = int(kwargs.get("num_iterations", d["num_iterations"]))
+        stop_condition = float(kwargs.get("stop_condition", d["stop_condition"]))
+        dev = mdesc = cdesc = None
         if torch.cuda.is_available():
             dev = _device(kwargs)
             mdesc, cdesc = gd.describe(model, cost, dev)
+        return gd, num_iterations, stop_condition, dev, mdesc, cdesc
+
+    @staticmethod
+    def plan(initial_state, model, cost, sample_action, horizon, initial_trajectory=None, **kwargs):
+        gd, num_iterations, stop_condition, dev, mdesc, cdesc = GradientDescentPlanner._setup(model, cost, kwargs)
+        H = int(horizon)
         if mdesc is not None:
             if initial_trajectory is None:
                 # planners.py:94: the nominal sequence (its states are not used for a deterministic model)
@@ -137,16 +184,10 @@ class GradientDescentPlanner(ModelPlanner):
         B plan() calls would draw). Recognised closures run in shared launches (mbrl_gd_plan_batch: the
         cooperative grids of up to 256 / (Wpad / 16) plans at once); others run plan() per row.
         Returns (states [B, H+1, s], actions [B, H, a])."""
-        from . import gd
-        num_iterations = int(kwargs.get("num_iterations", GradientDescentPlanner.defaults["num_iterations"]))
-        stop_condition = float(kwargs.get("stop_condition", GradientDescentPlanner.defaults["stop_condition"]))
+        gd, num_iterations, stop_condition, dev, mdesc, cdesc = GradientDescentPlanner._setup(model, cost, kwargs)
         H, B = int(horizon), int(initial_states.shape[0])
         inits = [None if initial_trajectories is None else initial_trajectories[b] for b in range(B)]
         keep = kwargs.get("return_device", False)
-        mdesc = cdesc = None
-        if torch.cuda.is_available():
-            dev = _device(kwargs)
-            mdesc, cdesc = gd.describe(model, cost, dev)
         if mdesc is not None and gd.fused_supported(mdesc, cdesc, dev) and num_iterations > 0:
             starts = [torch.cat(list(sample_action(batch_size=H).split(1, dim=0)), 0) if init is None
                       else torch.cat([x.reshape(1, -1) for x in init[1]], 0) for init in inits]
@@ -329,24 +370,11 @@ class CEMPlanner(ModelPlanner):
         N = int(g("num_candidates"))
         K = g("num_elites")
         K = max(1, N // 10) if K is None else int(K)
-        bounds = g("action_bounds")
-        sdesc = fused.describe_sampler(sample_action) if sample_action is not None else None
-        if bounds is None:
-            bounds = (sdesc[0], sdesc[1]) if sdesc is not None else (-1.0, 1.0)
-        lo, hi = float(bounds[0]), float(bounds[1])
-        init_std = g("init_std")
-        init_std = float(np.float32(hi - lo) / np.float32(4.0)) if init_std is None else float(init_std)
-        seed = g("seed")
-        if seed is None:
-            seed = int(np.random.randint(0, 2 ** 62, dtype=np.int64))
+        st = _common_settings(d, sample_action, horizon, kwargs)
         if not 1 <= K <= N:
             raise ValueError(f"need 1 <= num_elites ({K}) <= num_candidates ({N})")
-        return dict(N=N, K=K, H=int(horizon), I=int(g("num_iterations")), alpha=float(g("alpha")), lo=lo, hi=hi,
-                    init_std=init_std, seed=seed, distributed=bool(g("distributed")),
-                    keep=bool(g("return_device")), record=bool(kwargs.get("record", False)),
-                    events=kwargs.get("rollout_events"), plan_events=kwargs.get("plan_events"),
-                    adim=sdesc[2] if sdesc else None,
-                    precision=_lib.precision_code(g("precision")))
+        st.update(N=N, K=K, I=int(g("num_iterations")), distributed=bool(g("distributed")))
+        return st
 
     @staticmethod
     def plan_detailed(initial_state, model, cost, sample_action, horizon, initial_trajectory=None, **kwargs):
@@ -362,28 +390,17 @@ class CEMPlanner(ModelPlanner):
             if mdesc is not None and cdesc is not None:
                 if ws is None:
                     res = _cem_fused_single(prob, initial_state, st)
-                    if res.pop("_host", False):
-                        return res
                 else:
                     res = _cem_fused_sharded(prob, initial_state, st, ws)
-                    if res.pop("_host", False):
-                        return res
+                if res.pop("_host", False):      # host staging: the results are host tensors already
+                    return res
             else:
                 a = st["adim"]
                 if a is None:
                     a = sample_action(batch_size=1).shape[1]
                 res = _cem_generic(model, cost, initial_state.to(device=dev, dtype=torch.float32).contiguous(), st,
                                    a, dev)
-            both = res.pop("_both", None)
-            if both is not None and not st["keep"]:
-                host = both.cpu()              # one device-to-host copy for states and actions
-                H, s = res["states"].shape
-                res["states"] = host[:H * s].view(H, s)
-                res["actions"] = host[H * s:].view(H, -1)
-            else:
-                res["states"] = _to_host(res["states"], st["keep"])
-                res["actions"] = _to_host(res["actions"], st["keep"])
-            return res
+            return _finish(res, st["keep"])
 
 
 def cem_plan_batch(initial_states, model, cost, sample_action, horizon, **kwargs):
@@ -405,20 +422,16 @@ def cem_plan_batch(initial_states, model, cost, sample_action, horizon, **kwargs
             states, actions = torch.stack([o[0] for o in outs]), torch.stack([o[1] for o in outs])
         else:
             lib = _lib.load()
-            N, K, H, I = st["N"], st["K"], st["H"], st["I"]
-            a, s = mdesc["a"], mdesc["s"]
-            params = _lib.CemParams(N, H, K, I, st["alpha"], st["lo"], st["hi"], 0.0, st["init_std"], 0,
-                                    int(st["seed"]) & 0xFFFFFFFFFFFFFFFF)
+            H, a, s = st["H"], mdesc["a"], mdesc["s"]
+            params = _cem_params(st, int(st["seed"]) & 0xFFFFFFFFFFFFFFFF)
             need = lib.mbrl_cem_plan_batch_workspace_bytes(fused.ctypes_ref(prob.shape), fused.ctypes_ref(params), B)
             ws = _workspace(("cem_batch", str(dev)), need, dev)
             s0 = initial_states.to(device=dev, dtype=torch.float32).reshape(B, s).contiguous()
             actions = torch.empty((B, H, a), dtype=torch.float32, device=dev)
             states = torch.empty((B, H, s), dtype=torch.float32, device=dev)
-            _lib.check(lib.mbrl_cem_plan_batch(fused.ctypes_ref(prob.shape), _lib.ptr(prob.packed),
-                                               fused.ctypes_ref(prob.norm), fused.ctypes_ref(prob.cost), _lib.ptr(s0),
-                                               B, fused.ctypes_ref(params), None, None, _lib.ptr(actions),
-                                               _lib.ptr(states), _lib.ptr(ws), ws.numel(), _lib.stream_handle(dev)),
-                       "mbrl_cem_plan_batch")
+            _lib.check(lib.mbrl_cem_plan_batch(*prob.refs, _lib.ptr(s0), B, fused.ctypes_ref(params), None, None,
+                                               _lib.ptr(actions), _lib.ptr(states), _lib.ptr(ws), ws.numel(),
+                                               _lib.stream_handle(dev)), "mbrl_cem_plan_batch")
         keep = st["keep"]
         return _to_host(states, keep), _to_host(actions, keep)
 
@@ -462,33 +475,75 @@ def _staging(dev, n):
     return buf
 
 
-def _cem_plan_host(lib, prob, initial_state, st, params, ws, pref):
-    """mbrl_cem_plan with host staging (_lib.HostStaging): the plan's first launch reads the initial
-    state from mapped host memory and its last launches write states, actions, mu and sigma there, so
-    no copy launch precedes or follows the plan; one stream sync, then host tensors."""
-    dev = prob.device
-    md = prob.mdesc
-    H, a, s = st["H"], md["a"], md["s"]
-    stage = _staging(dev, H * (s + 3 * a) + s)
-    arr = stage.array
-    o_s0 = H * (s + 3 * a)
-    x = initial_state.detach() if initial_state.requires_grad else initial_state
-    arr[o_s0:o_s0 + s] = x.numpy().reshape(-1) if x.dtype == torch.float32 else x.reshape(-1).to(torch.float32).numpy()
-    o_act, o_mu, o_sg = H * s, H * (s + a), H * (s + 2 * a)
-    at = stage.cached_at((H, s, a), (o_s0, o_mu, o_sg, o_act, 0))
-    pev = st["plan_events"]
-    if pev is not None:
-        pev[0].record()
-    _lib.check(lib.mbrl_cem_plan(*prob.refs, at[0], pref, at[1], at[2], at[3], at[4], None, None, None,
-                                 _events(st, params.iterations), _lib.ptr(ws), ws.numel(), _lib.stream_handle(dev)),
-               "mbrl_cem_plan")
-    if pev is not None:
-        pev[1].record()
-    torch.cuda.current_stream(dev).synchronize()
-    x = arr[:o_s0].copy()                 # (NumPy views wrapped once each: ~2.4x cheaper than torch views)
+def _layout(H, s, a):
+    """The plan's output buffer, in floats: states [H, s] at 0, then the offsets of actions, mu and sigma
+    ([H, a] each) and the length H (s + 3 a). States and actions lie side by side, so that one copy hands
+    both to the host (_finish); host staging keeps s0 behind the outputs."""
+    return H * s, H * (s + a), H * (s + 2 * a), H * (s + 3 * a)
+
+
+def _stage_in(dev, s0, H, s, a):
+    """s0 (a host tensor) into this thread's staging buffer, behind the outputs. Returns the buffer's host
+    array and the device addresses the C call takes: (s0, mu, sigma, actions, states)."""
+    o_act, o_mu, o_sg, o_s0 = _layout(H, s, a)
+    stage = _staging(dev, o_s0 + s)
+    x = s0.detach() if s0.requires_grad else s0
+    stage.array[o_s0:o_s0 + s] = (x.numpy().reshape(-1) if x.dtype == torch.float32
+                                  else x.reshape(-1).to(torch.float32).numpy())
+    return stage.array, stage.cached_at((H, s, a), (o_s0, o_mu, o_sg, o_act, 0))
+
+
+def _stage_out(arr, H, s, a):
+    """The finished plan's outputs as host tensors over ONE copy of the staging array (NumPy views wrapped
+    once each: ~2.4x cheaper than torch views). "_host": nothing is left for plan_detailed to bring back."""
+    o_act, o_mu, o_sg, end = _layout(H, s, a)
+    x = arr[:end].copy()
     return dict(states=torch.from_numpy(x[:o_act].reshape(H, s)), actions=torch.from_numpy(x[o_act:o_mu].reshape(H, a)),
                 mu=torch.from_numpy(x[o_mu:o_sg].reshape(H, a)), sigma=torch.from_numpy(x[o_sg:].reshape(H, a)),
                 _host=True)
+
+
+def _device_outputs(dev, H, s, a):
+    """One device allocation in _layout's order, as the result dict: states, actions, mu, sigma and
+    "_both", the stretch that holds states and actions."""
+    o_act, o_mu, o_sg, end = _layout(H, s, a)
+    buf = torch.empty(end, dtype=torch.float32, device=dev)
+    both = buf[:o_mu]
+    return dict(states=both[:o_act].view(H, s), actions=both[o_act:].view(H, a), mu=buf[o_mu:o_sg].view(H, a),
+                sigma=buf[o_sg:].view(H, a), _both=both)
+
+
+def _output_ptrs(out):
+    """The device addresses of _device_outputs' tensors in the C calls' order: mu, sigma, actions, states."""
+    return _lib.ptr(out["mu"]), _lib.ptr(out["sigma"]), _lib.ptr(out["actions"]), _lib.ptr(out["states"])
+
+
+def _cem_record_buffers(dev, rec, I, E, N, K):
+    """record=True: every iteration's costs [I, E, N], returns [I, N] and elites [I, K]; else Nones."""
+    shapes = ((I, E, N), torch.float32), ((I, N), torch.float32), ((I, K), torch.int64)
+    return [torch.empty(sh, dtype=dt, device=dev) if rec else None for sh, dt in shapes]
+
+
+def _plan_params(prob, key, make_params, workspace_bytes, *extra):
+    """(params struct, its ctypes reference, workspace bytes) for the settings in `key`, built once per
+    problem and kept in prob.plan_cache (host turn). workspace_bytes(shape, params, *extra) is the
+    library's query; its answer 0 (settings refused: the caller raises) is not kept."""
+    hit = prob.plan_cache.get(key)
+    if hit is None:
+        params = make_params()
+        need = workspace_bytes(fused.ctypes_ref(prob.shape), fused.ctypes_ref(params), *extra)
+        if need == 0:
+            return params, fused.ctypes_ref(params), 0
+        if len(prob.plan_cache) > 64:
+            prob.plan_cache.clear()
+        hit = prob.plan_cache[key] = (params, fused.ctypes_ref(params), need)
+    return hit
+
+
+def _mark(pev, i):
+    """Record event i of the plan_events pair around the C call (bench.py's device span), if asked for."""
+    if pev is not None:
+        pev[i].record()
 
 
 _EVENT_ARRAYS = {}
@@ -507,6 +562,29 @@ def _events(st, I):
     return arr
 
 
+def _cem_params(st, seed):
+    return _lib.CemParams(st["N"], st["H"], st["K"], st["I"], st["alpha"], st["lo"], st["hi"], 0.0, st["init_std"], 0,
+                          seed)
+
+
+def _cem_plan_host(lib, prob, initial_state, st, params, ws, pref):
+    """mbrl_cem_plan with host staging (_lib.HostStaging): the plan's first launch reads the initial
+    state from mapped host memory and its last launches write states, actions, mu and sigma there, so
+    no copy launch precedes or follows the plan; one stream sync, then host tensors."""
+    dev = prob.device
+    md = prob.mdesc
+    H, a, s = st["H"], md["a"], md["s"]
+    arr, (p_s0, p_mu, p_sg, p_act, p_st) = _stage_in(dev, initial_state, H, s, a)
+    pev = st["plan_events"]
+    _mark(pev, 0)
+    _lib.check(lib.mbrl_cem_plan(*prob.refs, p_s0, pref, p_mu, p_sg, p_act, p_st, None, None, None,
+                                 _events(st, params.iterations), _lib.ptr(ws), ws.numel(), _lib.stream_handle(dev)),
+               "mbrl_cem_plan")
+    _mark(pev, 1)
+    torch.cuda.current_stream(dev).synchronize()
+    return _stage_out(arr, H, s, a)
+
+
 def _cem_fused_single(prob, initial_state, st):
     """One C-ABI call: mbrl_cem_plan (every iteration stream-ordered, no host sync)."""
     lib = _lib.load()
@@ -514,44 +592,22 @@ def _cem_fused_single(prob, initial_state, st):
     md = prob.mdesc
     N, K, H, I = st["N"], st["K"], st["H"], st["I"]
     a, s, E = md["a"], md["s"], md["E"]
-    # the params struct and the workspace size per settings, built once per problem (host turn)
     pkey = (N, H, K, I, st["alpha"], st["lo"], st["hi"], st["init_std"], int(st["seed"]) & 0xFFFFFFFFFFFFFFFF)
-    hit = prob.plan_cache.get(pkey)
-    if hit is None:
-        params = _lib.CemParams(N, H, K, I, st["alpha"], st["lo"], st["hi"], 0.0, st["init_std"], 0, pkey[-1])
-        need = lib.mbrl_cem_workspace_bytes(fused.ctypes_ref(prob.shape), fused.ctypes_ref(params))
-        if len(prob.plan_cache) > 64:
-            prob.plan_cache.clear()
-        hit = prob.plan_cache[pkey] = (params, fused.ctypes_ref(params), need)
-    params, pref, need = hit
+    params, pref, need = _plan_params(prob, pkey, lambda: _cem_params(st, pkey[-1]), lib.mbrl_cem_workspace_bytes)
     ws = _workspace(("cem", str(dev)), need, dev)
-    if HOST_STAGING and not st["keep"] and not st["record"] and not initial_state.is_cuda:
+    rec = st["record"]
+    if HOST_STAGING and not st["keep"] and not rec and not initial_state.is_cuda:
         return _cem_plan_host(lib, prob, initial_state, st, params, ws, pref)
     s0 = initial_state.to(device=dev, dtype=torch.float32).contiguous()
-    # one allocation for the outputs; states and actions side by side, so that plan() hands both
-    # back to the host in ONE copy
-    buf = torch.empty(H * (s + 3 * a), dtype=torch.float32, device=dev)
-    both = buf[:H * (s + a)]
-    states = both[:H * s].view(H, s)
-    actions = both[H * s:].view(H, a)
-    mu = buf[H * (s + a):H * (s + 2 * a)].view(H, a)
-    sigma = buf[H * (s + 2 * a):].view(H, a)
-    rec = st["record"]
-    cost_hist = torch.empty((I, E, N), dtype=torch.float32, device=dev) if rec else None
-    ret_hist = torch.empty((I, N), dtype=torch.float32, device=dev) if rec else None
-    elite_hist = torch.empty((I, K), dtype=torch.int64, device=dev) if rec else None
+    out = _device_outputs(dev, H, s, a)
+    cost_hist, ret_hist, elite_hist = _cem_record_buffers(dev, rec, I, E, N, K)
     ev_arr = _events(st, I)
     pev = st["plan_events"]
-    if pev is not None:
-        pev[0].record()
-    _lib.check(lib.mbrl_cem_plan(fused.ctypes_ref(prob.shape), _lib.ptr(prob.packed), fused.ctypes_ref(prob.norm),
-                                 fused.ctypes_ref(prob.cost), _lib.ptr(s0), fused.ctypes_ref(params), _lib.ptr(mu),
-                                 _lib.ptr(sigma), _lib.ptr(actions), _lib.ptr(states), _lib.ptr(cost_hist),
+    _mark(pev, 0)
+    _lib.check(lib.mbrl_cem_plan(*prob.refs, _lib.ptr(s0), pref, *_output_ptrs(out), _lib.ptr(cost_hist),
                                  _lib.ptr(ret_hist), _lib.ptr(elite_hist), ev_arr, _lib.ptr(ws), ws.numel(),
                                  _lib.stream_handle(dev)), "mbrl_cem_plan")
-    if pev is not None:
-        pev[1].record()
-    out = dict(states=states, actions=actions, mu=mu, sigma=sigma, _both=both)
+    _mark(pev, 1)
     if rec:
         out.update(costs=cost_hist, returns=ret_hist, elites=elite_hist)
     return out
@@ -743,59 +799,35 @@ def _cem_sharded_native(prob, s0, st, world, rank, comm=_OWN_COMM):
     a, s, E = md["a"], md["s"], md["E"]
     pkey = ("sharded", world, N, H, K, I, st["alpha"], st["lo"], st["hi"], st["init_std"],
             int(st["seed"]) & 0xFFFFFFFFFFFFFFFF, lib.mbrl_get_option(_lib.OPTIONS["shard_emulate"]))
-    hit = prob.plan_cache.get(pkey)
-    if hit is None:
-        params = _lib.CemParams(N, H, K, I, st["alpha"], st["lo"], st["hi"], 0.0, st["init_std"], 0, pkey[10])
-        need = lib.mbrl_cem_plan_sharded_workspace_bytes(fused.ctypes_ref(prob.shape), fused.ctypes_ref(params), world)
-        if need == 0:
-            raise ValueError(f"num_candidates {N} must divide evenly over {world} ranks")
-        if len(prob.plan_cache) > 64:
-            prob.plan_cache.clear()
-        hit = prob.plan_cache[pkey] = (params, fused.ctypes_ref(params), need)
-    params, pref, need = hit
+    _, pref, need = _plan_params(prob, pkey, lambda: _cem_params(st, pkey[10]),
+                                 lib.mbrl_cem_plan_sharded_workspace_bytes, world)
+    if need == 0:
+        raise ValueError(f"num_candidates {N} must divide evenly over {world} ranks")
     ws = _workspace(("cem_sharded", str(dev)), need, dev)
     if comm is _OWN_COMM:
         comm = _rccl_comm(dev, world, rank)
     rec = st["record"]
     staged = HOST_STAGING and not st["keep"] and not rec and not s0.is_cuda
     if staged:
-        stage = _staging(dev, H * (s + 3 * a) + s)
-        arr = stage.array
-        o_s0 = H * (s + 3 * a)
-        x = s0.detach() if s0.requires_grad else s0
-        arr[o_s0:o_s0 + s] = x.numpy().reshape(-1) if x.dtype == torch.float32 else x.reshape(-1).to(torch.float32).numpy()
-        o_act, o_mu, o_sg = H * s, H * (s + a), H * (s + 2 * a)
-        at = stage.cached_at((H, s, a), (o_s0, o_mu, o_sg, o_act, 0))
-        p_s0, p_mu, p_sg, p_act, p_st = at
+        arr, (p_s0, p_mu, p_sg, p_act, p_st) = _stage_in(dev, s0, H, s, a)
     else:
         s0 = s0.to(device=dev, dtype=torch.float32).contiguous()
-        buf = torch.empty(H * (s + 3 * a), dtype=torch.float32, device=dev)
-        both = buf[:H * (s + a)]
-        states, actions = both[:H * s].view(H, s), both[H * s:].view(H, a)
-        mu, sigma = buf[H * (s + a):H * (s + 2 * a)].view(H, a), buf[H * (s + 2 * a):].view(H, a)
-        p_s0, p_mu, p_sg, p_act, p_st = _lib.ptr(s0), _lib.ptr(mu), _lib.ptr(sigma), _lib.ptr(actions), _lib.ptr(states)
-    cost_hist = torch.empty((I, E, N), dtype=torch.float32, device=dev) if rec else None
-    ret_hist = torch.empty((I, N), dtype=torch.float32, device=dev) if rec else None
-    elite_hist = torch.empty((I, K), dtype=torch.int64, device=dev) if rec else None
+        out = _device_outputs(dev, H, s, a)
+        p_s0, (p_mu, p_sg, p_act, p_st) = _lib.ptr(s0), _output_ptrs(out)
+    cost_hist, ret_hist, elite_hist = _cem_record_buffers(dev, rec, I, E, N, K)
     pev = st.get("plan_events")
-    if pev is not None:
-        pev[0].record()
+    _mark(pev, 0)
     rc = lib.mbrl_cem_plan_sharded(*prob.refs, p_s0, pref, comm, world, rank, p_mu, p_sg, p_act, p_st,
                                    _lib.ptr(cost_hist), _lib.ptr(ret_hist), _lib.ptr(elite_hist), _events(st, I),
                                    _lib.ptr(ws), ws.numel(), _lib.stream_handle(dev))
-    if pev is not None and rc == _lib.MBRL_OK:
-        pev[1].record()
     # a failure after the argument checks still joined every all-gather of the plan, and every rank
     # learns of it (include/mbrl_cem.h): the communicator stays in step with the other ranks and is kept
     _lib.check(rc, "mbrl_cem_plan_sharded")
+    _mark(pev, 1)
     if staged:
         if world == 1:     # (with peers the call has synchronised already)
             torch.cuda.current_stream(dev).synchronize()
-        x = arr[:o_s0].copy()
-        return dict(states=torch.from_numpy(x[:o_act].reshape(H, s)), actions=torch.from_numpy(x[o_act:o_mu].reshape(H, a)),
-                    mu=torch.from_numpy(x[o_mu:o_sg].reshape(H, a)), sigma=torch.from_numpy(x[o_sg:].reshape(H, a)),
-                    _host=True)
-    out = dict(states=states, actions=actions, mu=mu, sigma=sigma, _both=both)
+        return _stage_out(arr, H, s, a)
     if rec:
         out.update(costs=cost_hist, returns=ret_hist, elites=elite_hist)
     return out
@@ -810,33 +842,46 @@ def _cem_fused_sharded(prob, s0, st, world):
                                 st, world, dist.get_rank())
 
 
-def _cem_generic(model, cost, s0, st, a, dev):
-    """CEM with opaque callables: HIP proposal draw, the callables on device tensors, HIP select/refit."""
-    N, K, H, I = st["N"], st["K"], st["H"], st["I"]
-    mu = torch.zeros((H, a), dtype=torch.float32, device=dev)
+def _generic_plan(model, cost, s0, st, a, dev, mu, update, hist):
+    """A sampling plan with opaque callables, from the initial mean `mu`: per iteration the HIP proposal
+    draw, the callables on device tensors (_generic_costs), then the planner's own HIP
+    update(sampler, costs, actions, mu_out, sigma_out); at the end the clipped mean and its predicted
+    states. record=True: each iteration's costs and the dict `update` returned go into `hist`'s lists."""
+    N, H, I = st["N"], st["H"], st["I"]
     sigma = torch.full((H, a), st["init_std"], dtype=torch.float32, device=dev)
     mu_n, sigma_n = torch.empty_like(mu), torch.empty_like(sigma)
     acts = torch.empty((H, N, a), dtype=torch.float32, device=dev)
-    hist = dict(costs=[], returns=[], elites=[])
+    rec = st["record"]
     for it in range(I):
         sp = fused.make_sampler(st["seed"], it, mu, sigma, st["lo"], st["hi"])
         fused.sample_actions(sp, H, a, N, 0, acts)
         costs, _ = _generic_costs(model, cost, s0, acts, H, N)
-        rets = torch.empty(N, dtype=torch.float32, device=dev)
-        elites = fused.select(costs, K, returns_out=rets)
-        fused.refit(sp, H, a, elites, st["alpha"], mu_n, sigma_n)
+        kept = update(sp, costs, acts, mu_n, sigma_n)
         mu, mu_n = mu_n, mu
         sigma, sigma_n = sigma_n, sigma
-        if st["record"]:
+        if rec:
             hist["costs"].append(costs.clone())
-            hist["returns"].append(rets)
-            hist["elites"].append(elites)
+            for k, v in kept.items():
+                hist[k].append(v)
     actions = mu.clamp(st["lo"], st["hi"]).contiguous()
     _, states = _generic_costs(model, cost, s0, actions.view(H, 1, a), H, 1)
     out = dict(states=states[:, 0, :], actions=actions, mu=mu, sigma=sigma)
-    if st["record"]:
+    if rec:
         out.update({k: torch.stack(v) for k, v in hist.items()})
     return out
+
+
+def _cem_generic(model, cost, s0, st, a, dev):
+    """CEM with opaque callables: HIP proposal draw, the callables on device tensors, HIP select/refit."""
+    N, K, H = st["N"], st["K"], st["H"]
+
+    def update(sp, costs, acts, mu_out, sigma_out):
+        rets = torch.empty(N, dtype=torch.float32, device=dev)
+        elites = fused.select(costs, K, returns_out=rets)
+        fused.refit(sp, H, a, elites, st["alpha"], mu_out, sigma_out)
+        return dict(returns=rets, elites=elites)
+    return _generic_plan(model, cost, s0, st, a, dev, torch.zeros((H, a), dtype=torch.float32, device=dev), update,
+                         dict(costs=[], returns=[], elites=[]))
 
 
 # ------------------------------------------------------------------------------------------------
@@ -911,26 +956,14 @@ class MPPIPlanner(ModelPlanner):
             raise NotImplementedError("MPPIPlanner: distributed=True (sharded MPPI) is not implemented; "
                                       "use CEMPlanner for multi-GPU plans")
         N, I = int(g("num_candidates")), int(g("num_iterations"))
-        bounds = g("action_bounds")
-        sdesc = fused.describe_sampler(sample_action) if sample_action is not None else None
-        if bounds is None:
-            bounds = (sdesc[0], sdesc[1]) if sdesc is not None else (-1.0, 1.0)
-        lo, hi = float(bounds[0]), float(bounds[1])
-        init_std = g("init_std")
-        init_std = float(np.float32(hi - lo) / np.float32(4.0)) if init_std is None else float(init_std)
-        seed = g("seed")
-        if seed is None:
-            seed = int(np.random.randint(0, 2 ** 62, dtype=np.int64))
+        st = _common_settings(d, sample_action, horizon, kwargs)
         temperature = float(g("temperature"))
         if not (temperature > 0.0 and np.isfinite(temperature)):
             raise ValueError(f"temperature must be finite and > 0, got {temperature}")
         if N < 1 or I < 1:
             raise ValueError(f"need num_candidates ({N}) >= 1 and num_iterations ({I}) >= 1")
-        return dict(N=N, H=int(horizon), I=I, temperature=temperature, alpha=float(g("alpha")),
-                    update_sigma=bool(g("update_sigma")), lo=lo, hi=hi, init_std=init_std, seed=seed,
-                    shift=int(g("shift")), keep=bool(g("return_device")), record=bool(kwargs.get("record", False)),
-                    events=kwargs.get("rollout_events"), plan_events=kwargs.get("plan_events"),
-                    adim=sdesc[2] if sdesc else None, precision=_lib.precision_code(g("precision")))
+        st.update(N=N, I=I, temperature=temperature, update_sigma=bool(g("update_sigma")), shift=int(g("shift")))
+        return st
 
     @staticmethod
     def plan_detailed(initial_state, model, cost, sample_action, horizon, initial_trajectory=None, **kwargs):
@@ -952,16 +985,7 @@ class MPPIPlanner(ModelPlanner):
                     a = sample_action(batch_size=1).shape[1]
                 res = _mppi_generic(model, cost, initial_state.to(device=dev, dtype=torch.float32).contiguous(), st,
                                     a, dev, rows)
-            both = res.pop("_both", None)
-            if both is not None and not st["keep"]:
-                host = both.cpu()              # one device-to-host copy for states and actions
-                H, s = res["states"].shape
-                res["states"] = host[:H * s].view(H, s)
-                res["actions"] = host[H * s:].view(H, -1)
-            else:
-                res["states"] = _to_host(res["states"], st["keep"])
-                res["actions"] = _to_host(res["actions"], st["keep"])
-            return res
+            return _finish(res, st["keep"])
 
 
 def _mppi_fused_single(prob, initial_state, st, rows):
@@ -973,41 +997,26 @@ def _mppi_fused_single(prob, initial_state, st, rows):
     a, s, E = md["a"], md["s"], md["E"]
     pkey = ("mppi", N, H, I, st["update_sigma"], st["temperature"], st["alpha"], st["lo"], st["hi"], st["init_std"],
             int(st["seed"]) & 0xFFFFFFFFFFFFFFFF)
-    hit = prob.plan_cache.get(pkey)
-    if hit is None:
-        params = _lib.MppiParams(N, H, I, int(st["update_sigma"]), st["temperature"], st["alpha"], st["lo"], st["hi"],
-                                 0.0, st["init_std"], pkey[-1])
-        need = lib.mbrl_mppi_workspace_bytes(fused.ctypes_ref(prob.shape), fused.ctypes_ref(params))
-        if need == 0:
-            _lib.check(_lib.MBRL_EINVAL, "mbrl_mppi_workspace_bytes")
-        if len(prob.plan_cache) > 64:
-            prob.plan_cache.clear()
-        hit = prob.plan_cache[pkey] = (params, fused.ctypes_ref(params), need)
-    params, pref, need = hit
+
+    def make_params():
+        return _lib.MppiParams(N, H, I, int(st["update_sigma"]), st["temperature"], st["alpha"], st["lo"], st["hi"],
+                               0.0, st["init_std"], pkey[-1])
+    _, pref, need = _plan_params(prob, pkey, make_params, lib.mbrl_mppi_workspace_bytes)
+    if need == 0:
+        _lib.check(_lib.MBRL_EINVAL, "mbrl_mppi_workspace_bytes")
     ws = _workspace(("mppi", str(dev)), need, dev)
     s0 = initial_state.to(device=dev, dtype=torch.float32).contiguous()
     rows_d = None if rows is None else torch.from_numpy(np.ascontiguousarray(rows)).to(dev)
-    buf = torch.empty(H * (s + 3 * a), dtype=torch.float32, device=dev)
-    both = buf[:H * (s + a)]
-    states = both[:H * s].view(H, s)
-    actions = both[H * s:].view(H, a)
-    mu = buf[H * (s + a):H * (s + 2 * a)].view(H, a)
-    sigma = buf[H * (s + 2 * a):].view(H, a)
+    out = _device_outputs(dev, H, s, a)
     rec = st["record"]
-    cost_hist = torch.empty((I, E, N), dtype=torch.float32, device=dev) if rec else None
-    w_hist = torch.empty((I, N), dtype=torch.float32, device=dev) if rec else None
-    mu_hist = torch.empty((I + 1, H, a), dtype=torch.float32, device=dev) if rec else None
-    sg_hist = torch.empty((I + 1, H, a), dtype=torch.float32, device=dev) if rec else None
+    cost_hist, w_hist, mu_hist, sg_hist = [torch.empty(sh, dtype=torch.float32, device=dev) if rec else None
+                                           for sh in ((I, E, N), (I, N), (I + 1, H, a), (I + 1, H, a))]
     pev = st["plan_events"]
-    if pev is not None:
-        pev[0].record()
-    _lib.check(lib.mbrl_mppi_plan(*prob.refs, _lib.ptr(s0), pref, _lib.ptr(rows_d), _lib.ptr(mu), _lib.ptr(sigma),
-                                  _lib.ptr(actions), _lib.ptr(states), _lib.ptr(cost_hist), _lib.ptr(w_hist),
-                                  _lib.ptr(mu_hist), _lib.ptr(sg_hist), _events(st, I), _lib.ptr(ws), ws.numel(),
-                                  _lib.stream_handle(dev)), "mbrl_mppi_plan")
-    if pev is not None:
-        pev[1].record()
-    out = dict(states=states, actions=actions, mu=mu, sigma=sigma, _both=both)
+    _mark(pev, 0)
+    _lib.check(lib.mbrl_mppi_plan(*prob.refs, _lib.ptr(s0), pref, _lib.ptr(rows_d), *_output_ptrs(out),
+                                  _lib.ptr(cost_hist), _lib.ptr(w_hist), _lib.ptr(mu_hist), _lib.ptr(sg_hist),
+                                  _events(st, I), _lib.ptr(ws), ws.numel(), _lib.stream_handle(dev)), "mbrl_mppi_plan")
+    _mark(pev, 1)
     if rec:
         out.update(costs=cost_hist, weights=w_hist, mu_hist=mu_hist, sigma_hist=sg_hist)
     return out
@@ -1016,33 +1025,18 @@ def _mppi_fused_single(prob, initial_state, st, rows):
 def _mppi_generic(model, cost, s0, st, a, dev, rows):
     """MPPI with opaque callables: HIP proposal draw, the callables on device tensors, then the HIP
     weighted update (mbrl_mppi_update), as selection and refit stay in the extension for CEM."""
-    N, H, I = st["N"], st["H"], st["I"]
+    N, H = st["N"], st["H"]
+    rec = st["record"]
     if rows is None:
         mu = torch.zeros((H, a), dtype=torch.float32, device=dev)
     else:
         mu = torch.from_numpy(np.ascontiguousarray(rows)).to(dev)
-    sigma = torch.full((H, a), st["init_std"], dtype=torch.float32, device=dev)
-    mu_n, sigma_n = torch.empty_like(mu), torch.empty_like(sigma)
-    acts = torch.empty((H, N, a), dtype=torch.float32, device=dev)
-    rec = st["record"]
-    hist = dict(costs=[], weights=[], mu_hist=[mu.clone()], sigma_hist=[sigma.clone()])
-    for it in range(I):
-        sp = fused.make_sampler(st["seed"], it, mu, sigma, st["lo"], st["hi"])
-        fused.sample_actions(sp, H, a, N, 0, acts)
-        costs, _ = _generic_costs(model, cost, s0, acts, H, N)
+
+    def update(sp, costs, acts, mu_out, sigma_out):
         wts = torch.empty(N, dtype=torch.float32, device=dev) if rec else None
-        fused.mppi_update(costs, acts, sp, H, a, st["temperature"], st["alpha"], st["update_sigma"], mu_n, sigma_n,
-                          weights_out=wts)
-        mu, mu_n = mu_n, mu
-        sigma, sigma_n = sigma_n, sigma
-        if rec:
-            hist["costs"].append(costs.clone())
-            hist["weights"].append(wts)
-            hist["mu_hist"].append(mu.clone())
-            hist["sigma_hist"].append(sigma.clone())
-    actions = mu.clamp(st["lo"], st["hi"]).contiguous()
-    _, states = _generic_costs(model, cost, s0, actions.view(H, 1, a), H, 1)
-    out = dict(states=states[:, 0, :], actions=actions, mu=mu, sigma=sigma)
-    if rec:
-        out.update({k: torch.stack(v) for k, v in hist.items()})
-    return out
+        fused.mppi_update(costs, acts, sp, H, a, st["temperature"], st["alpha"], st["update_sigma"], mu_out,
+                          sigma_out, weights_out=wts)
+        return dict(weights=wts, mu_hist=mu_out.clone(), sigma_hist=sigma_out.clone()) if rec else None
+    sigma0 = torch.full((H, a), st["init_std"], dtype=torch.float32, device=dev)     # (row 0 of sigma_hist)
+    return _generic_plan(model, cost, s0, st, a, dev, mu, update,
+                         dict(costs=[], weights=[], mu_hist=[mu.clone()], sigma_hist=[sigma0]))

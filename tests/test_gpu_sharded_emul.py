@@ -82,6 +82,30 @@ def test_sharded_plan_every_rank_equals_single_gpu_plan(cid, N, H, over, worlds)
           f"(elites {tuple(ref['elites'].shape)}, mu[0,0] {float(ref['mu'][0, 0]):.6g})")
 
 
+def test_sharded_plan_with_s0_on_the_host_equals_s0_on_the_device():
+    """s0 on the host (no records, no device outputs) sends the sharded plan through mapped host
+    staging; s0 on the device through device buffers. Same plan: states, actions, mu and sigma equal bit
+    for bit, on both ranks (ensemble config 5, N = 256, H = 4, I = 2, G = 2)."""
+    from mbrl_amd import CEMPlanner, _lib, fused, planners
+    p = ocem.synth_problem(5, N=256, H=4)
+    _, model_fn, cost_fn, sample_action = build(p)
+    dev = torch.device(DEV)
+    md = fused.describe_model(model_fn)
+    prob = fused.device_problem(md, fused.describe_cost(cost_fn, md["s"], md), dev)
+    st = CEMPlanner._settings(sample_action, 4, dict(num_candidates=256, num_iterations=2, seed=p["rng_seed"]))
+    s0 = torch.from_numpy(p["s0"])
+    assert planners.HOST_STAGING and not st["keep"] and not st["record"]
+    for rank in range(2):
+        with _lib.option("shard_emulate", 1), torch.cuda.device(dev):
+            staged = planners._cem_sharded_native(prob, s0, st, 2, rank, comm=None)
+            on_dev = planners._cem_sharded_native(prob, s0.to(dev), st, 2, rank, comm=None)
+            torch.cuda.synchronize()
+        assert staged.get("_host") is True and "_host" not in on_dev
+        for k in ("states", "actions", "mu", "sigma"):
+            assert not staged[k].is_cuda and on_dev[k].is_cuda, k
+            assert torch.equal(staged[k], on_dev[k].cpu()), (rank, k)
+
+
 def test_sharded_plan_through_the_c_entry_rejects_bad_calls():
     """The C entry's refusals: N % nranks != 0 (workspace query 0, plan MBRL_EINVAL), comm == NULL
     without the emulation switch, bad communicator arguments -- all before any collective."""

@@ -1,7 +1,9 @@
 """Diagnostic: the host side of one bench plan (CEMPlanner.plan_detailed on a host s0, the bench's
-kwargs) statement by statement -- the same calls planners.plan_detailed / _cem_fused_single /
-_cem_plan_host make, in order, with a perf_counter stamp after each -- mean microseconds per segment
-over many plans. Usage: python tools/host_lines.py [config_id] [plans] [candidates]"""
+kwargs) step by step -- the calls planners.plan_detailed / _cem_fused_single / _cem_plan_host make, in
+order, the staging through planners' own helpers (_stage_in, _stage_out), with a perf_counter stamp
+after each -- mean microseconds per segment over many plans. "staging lookup" times the lookup
+_stage_in starts with on its own; "s0 into staging" is _stage_in whole (a second lookup, s0, the cached
+device addresses). Usage: python tools/host_lines.py [config_id] [plans] [candidates]"""
 import json
 import os
 import sys
@@ -50,14 +52,10 @@ def main():
         stamp("workspace")
         md = prob.mdesc
         a, s = md["a"], md["s"]
-        stage = planners._staging(d, Hh * (s + 3 * a) + s)
+        planners._staging(d, planners._layout(Hh, s, a)[-1] + s)
         stamp("staging lookup")
-        arr = stage.array
-        o_s0 = Hh * (s + 3 * a)
-        arr[o_s0:o_s0 + s] = s0.detach().reshape(-1).to(torch.float32).numpy()
+        arr, at = planners._stage_in(d, s0, Hh, s, a)
         stamp("s0 into staging")
-        o_act, o_mu, o_sg = Hh * s, Hh * (s + a), Hh * (s + 2 * a)
-        at = stage.cached_at((Hh, s, a), (o_s0, o_mu, o_sg, o_act, 0))
         ev = planners._events(st, I)
         wsp = _lib.ptr(ws)
         sh = _lib.stream_handle(d)
@@ -68,9 +66,7 @@ def main():
         _lib.check(rc, "mbrl_cem_plan")
         torch.cuda.current_stream(d).synchronize()
         stamp("sync (GPU plan)")
-        x = arr[:o_s0].copy()
-        res = dict(states=torch.from_numpy(x[:o_act].reshape(Hh, s)), actions=torch.from_numpy(x[o_act:o_mu].reshape(Hh, a)),
-                   mu=torch.from_numpy(x[o_mu:o_sg].reshape(Hh, a)), sigma=torch.from_numpy(x[o_sg:].reshape(Hh, a)))
+        res = planners._stage_out(arr, Hh, s, a)
         stamp("copy-out")
         ctx.__exit__(None, None, None)
         stamp("cuda.device exit")
