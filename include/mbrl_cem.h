@@ -92,7 +92,14 @@ typedef struct {
 } mbrl_mlp_shape;
 
 /* Normalisation affine, TransitionsDataset.normalize_field / unnormalize_field (data.py:255-260),
- * bound as in agents.py:219-230. A zero flag = that keyword was None in the reference call. */
+ * bound as in agents.py:219-230. A zero flag = that keyword was None in the reference call.
+ * A statistics pointer may be NULL exactly when no set flag uses it: obs_mean / obs_std when
+ * normalize_state and unnormalize_state are both 0, act_mean / act_std when normalize_action is 0,
+ * rew_mean / rew_std when unnormalize_reward is 0. A set flag whose statistics are NULL is
+ * MBRL_EINVAL in every entry that takes an mbrl_norm, returned before any kernel that reads the
+ * statistics is launched (mbrl_rollout_cost, mbrl_trajectory and mbrl_gd_plan launch nothing at
+ * all; the whole-plan entries may already have launched their initialisation kernel, which reads
+ * none). Passing norm == NULL means all four flags are 0. */
 typedef struct {
     const float* obs_mean;  /* [s] */
     const float* obs_std;   /* [s] */

@@ -64,14 +64,22 @@ InitZero plan_zero(const Geometry& g, int Nl, void* pair, const TrajScratch& ts)
 
 // The argument checks of rollout_impl that depend on the problem only (not on N or the buffers): the
 // sharded plan runs them before its first collective.
+// A state or action flag needs its statistics; a statistics pointer no flag uses may be NULL (the
+// kernels then never read it, or read it as mean 0 / std 1). Shared by the rollout and the trajectory.
+static int norm_stats_validate(const mbrl_norm* norm) {
+    if (!norm) return MBRL_OK;
+    if ((norm->normalize_state || norm->unnormalize_state) && (!norm->obs_mean || !norm->obs_std))
+        return fail(MBRL_EINVAL, "state normalisation requested without obs_mean/obs_std");
+    if (norm->normalize_action && (!norm->act_mean || !norm->act_std))
+        return fail(MBRL_EINVAL, "action normalisation requested without act_mean/act_std");
+    return MBRL_OK;
+}
+
 int rollout_validate(const Geometry& g, const mbrl_norm* norm, const mbrl_cost* cost) {
     if (norm) {
         if (norm->unnormalize_reward && (!norm->rew_mean || !norm->rew_std))
             return fail(MBRL_EINVAL, "reward unnormalisation requested without rew_mean/rew_std");
-        if ((norm->normalize_state || norm->unnormalize_state) && (!norm->obs_mean || !norm->obs_std))
-            return fail(MBRL_EINVAL, "state normalisation requested without obs_mean/obs_std");
-        if (norm->normalize_action && (!norm->act_mean || !norm->act_std))
-            return fail(MBRL_EINVAL, "action normalisation requested without act_mean/act_std");
+        if (int rc = norm_stats_validate(norm)) return rc;
     }
     if (cost && cost->kind == MBRL_COST_MODEL_REWARD) {
         if (!g.reward) return fail(MBRL_EINVAL, "MODEL_REWARD cost needs a reward_head model");
@@ -278,6 +286,7 @@ int rollout_impl(const Geometry& g, const void* packed, const mbrl_norm* norm, c
 static int traj_impl(const Geometry& g, const void* packed, const mbrl_norm* norm, const float* s0,
                      const float* actions, int H, float* states_out, const TrajScratch& ts, hipStream_t stream,
                      int prezeroed) {
+    if (int rc = norm_stats_validate(norm)) return rc;   // before any launch
     TrajArgs T{};
     T.prezeroed = prezeroed;
     T.packed = static_cast<const float*>(packed);

@@ -252,8 +252,8 @@ __global__ void __launch_bounds__(COOP_THREADS) traj_coop_kernel(const TrajArgs 
         hb[i] = bias[(size_t)(1 + i / COOP_ROWS) * Wp + p * COOP_ROWS + (i % COOP_ROWS)];
     for (int d = tid; d < s; d += COOP_THREADS) {
         ob[d] = bias[(size_t)A.L * Wp + d];
-        om[d] = A.obs_mean[d];
-        os[d] = A.obs_std[d];
+        om[d] = A.obs_mean ? A.obs_mean[d] : 0.0f;   // NULL statistics are legal when no state flag is set
+        os[d] = A.obs_std ? A.obs_std[d] : 1.0f;
         const float sv = A.s0[d];
         x0[d] = A.norm_s ? (sv - A.obs_mean[d]) / A.obs_std[d] : sv;
     }

@@ -105,11 +105,30 @@ def synth_state_goal(seed, s):
     return s0, goal
 
 
-def synth_problem(config_id, **overrides):
-    """Everything a config needs: model members, normalisation, s0, goal-state cost, CEM seed."""
+NORM_FLAGS = ("normalize_state", "unnormalize_state", "normalize_action", "unnormalize_reward")
+
+
+def synth_weights(seed, s):
+    """Non-unit SmoothAbsLoss weights from the problem seed: U(0.25, 3), one exact zero when s >= 3."""
+    rng = np.random.Generator(np.random.PCG64(seed + 5))
+    w = rng.uniform(0.25, 3.0, size=s).astype(F32)
+    if s >= 3:
+        w[int(rng.integers(0, s))] = F32(0)
+    return w
+
+
+def synth_problem(config_id, *, seed=None, norm_flags=None, no_norm=False, random_weights=False, alpha_state=None,
+                  alpha_action=None, has_state_cost=None, has_action_cost=None, **overrides):
+    """Everything a config needs: model members, normalisation, s0, goal-state cost, CEM seed.
+
+    Keyword switches (all default to the configs' own problem: every normaliser on, unit weights, the
+    default alphas, both cost terms): `seed` replaces 1000 + config id; `norm_flags` is a dict of
+    NORM_FLAGS booleans stored in `norm` (an absent flag stays on); `no_norm` makes `norm` None;
+    `random_weights` draws synth_weights; `alpha_state` / `alpha_action` replace the defaults;
+    `has_state_cost` / `has_action_cost` store cost["has_state"] / cost["has_action"]."""
     cfg = dict(CONFIGS[config_id])
     cfg.update(overrides)
-    seed = 1000 + config_id
+    seed = 1000 + config_id if seed is None else int(seed)
     s, a = cfg["s"], cfg["a"]
     norm = synth_norm(seed, s, a)
     s0, goal = synth_state_goal(seed, s)
@@ -120,8 +139,18 @@ def synth_problem(config_id, **overrides):
         cost = dict(kind="reward")
     else:
         model = synth_model(seed, s, a, cfg["W"], cfg["L"], cfg["E"])
-        cost = dict(weights=np.ones(s, dtype=F32), goal=goal, alpha_state=SMOOTH_ABS_ALPHA,
-                    alpha_action=COSH_ALPHA)
+        cost = dict(weights=synth_weights(seed, s) if random_weights else np.ones(s, dtype=F32), goal=goal,
+                    alpha_state=SMOOTH_ABS_ALPHA if alpha_state is None else float(alpha_state),
+                    alpha_action=COSH_ALPHA if alpha_action is None else float(alpha_action))
+        if has_state_cost is not None:
+            cost["has_state"] = bool(has_state_cost)
+        if has_action_cost is not None:
+            cost["has_action"] = bool(has_action_cost)
+    if norm_flags:
+        assert set(norm_flags) <= set(NORM_FLAGS), norm_flags
+        norm.update({k: bool(v) for k, v in norm_flags.items()})
+    if no_norm:
+        norm = None
     return dict(cfg=cfg, seed=seed, rng_seed=seed + 3, model=model, norm=norm, s0=s0, cost=cost)
 
 
@@ -145,22 +174,37 @@ def mlp_forward(layers, x):
     return (x @ w.T + b).astype(F32)
 
 
-def _model_out(layers, norm, s, a):
-    """normalize_action, normalize_state, cat (state first), the MLP (models.py:13-29 / 143-163)."""
-    if norm is not None:
+def norm_flag(norm, key):
+    """Whether normaliser `key` (one of NORM_FLAGS) applies: norm None = none does (the keyword was None
+    in the reference call); a flag absent from the dict is on (unnormalize_reward: when the reward
+    statistics are there)."""
+    if norm is None:
+        return False
+    if key == "unnormalize_reward" and norm.get("rew_mean") is None:
+        return False
+    return bool(norm.get(key, True))
+
+
+def model_input(norm, s, a):
+    """normalize_action, normalize_state (each if its flag is on), cat (state first): the first
+    layer's input (models.py:13-29 / 143-163)."""
+    if norm_flag(norm, "normalize_action"):
         a = ((a - norm["act_mean"]) / norm["act_std"]).astype(F32)        # normalize_action first
-        sn = ((s - norm["obs_mean"]) / norm["obs_std"]).astype(F32)       # then normalize_state
-    else:
-        sn = s
-    x = np.concatenate([sn, a], axis=1).astype(F32)                        # state first
-    return mlp_forward(layers, x)
+    if norm_flag(norm, "normalize_state"):
+        s = ((s - norm["obs_mean"]) / norm["obs_std"]).astype(F32)        # then normalize_state
+    return np.concatenate([s, a], axis=1).astype(F32)                      # state first
+
+
+def _model_out(layers, norm, s, a):
+    """The MLP on model_input (models.py:13-29 / 143-163)."""
+    return mlp_forward(layers, model_input(norm, s, a))
 
 
 def dynamics_step(layers, norm, s, a):
     """DynamicsModel.forward (models.py:13-29) with the GoalStateAgent normalisers (agents.py:219-230);
     for a reward-head model, the state head of ModelWithReward.forward (models.py:143-163)."""
     out = _model_out(layers, norm, s, a)[:, :s.shape[1]]
-    if norm is not None:
+    if norm_flag(norm, "unnormalize_state"):
         out = (out * norm["obs_std"] + norm["obs_mean"]).astype(F32)       # unnormalize_state
     return out
 
@@ -169,20 +213,25 @@ def reward_cost(layers, norm, s_next, a):
     """RewardAgent's cost (agents.py:353-362): compose(partial(model, ...), itemgetter(1)) evaluated on
     (s_{t+1}, a_t) (planners.py:210) = the reward head, unnormalised (models.py:157-158)."""
     r = _model_out(layers, norm, s_next, a)[:, s_next.shape[1]]
-    if norm is not None and norm.get("rew_mean") is not None:
+    if norm_flag(norm, "unnormalize_reward"):
         r = (r * norm["rew_std"][0] + norm["rew_mean"][0]).astype(F32)      # unnormalize_reward
     return r.astype(F32)
 
 
 def goal_state_cost(s, a, cost):
-    """state_action_cost (agents.py:182-183) = SmoothAbsLoss(s) (models.py:255-259) + CoshLoss(a) (:271-272)."""
-    al = F32(cost["alpha_state"])
-    al2 = F32(cost["alpha_state"] ** 2)
-    x = (s - cost["goal"]).astype(F32)
-    sc = np.sum(np.sqrt(((x * cost["weights"]) ** 2 + al2).astype(F32)) - al, axis=-1, dtype=F32)
-    aa = F32(cost["alpha_action"])
-    aa2 = F32(cost["alpha_action"] ** 2)
-    ac = aa2 * np.mean(np.cosh((a / aa).astype(F32)) - F32(1), axis=-1, dtype=F32)
+    """state_action_cost (agents.py:182-183) = SmoothAbsLoss(s) (models.py:255-259) + CoshLoss(a) (:271-272).
+    cost["has_state"] / cost["has_action"] (default on) drop a term: the ABI's has_state_cost /
+    has_action_cost; with both off the cost is exactly 0."""
+    sc = ac = np.zeros(s.shape[:-1], dtype=F32)
+    if cost.get("has_state", True):
+        al = F32(cost["alpha_state"])
+        al2 = F32(cost["alpha_state"] ** 2)
+        x = (s - cost["goal"]).astype(F32)
+        sc = np.sum(np.sqrt(((x * cost["weights"]) ** 2 + al2).astype(F32)) - al, axis=-1, dtype=F32)
+    if cost.get("has_action", True):
+        aa = F32(cost["alpha_action"])
+        aa2 = F32(cost["alpha_action"] ** 2)
+        ac = aa2 * np.mean(np.cosh((a / aa).astype(F32)) - F32(1), axis=-1, dtype=F32)
     return (sc + ac).astype(F32)
 
 

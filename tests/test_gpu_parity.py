@@ -21,9 +21,13 @@ def rel_err(x, ref):
     return float(np.max(np.abs(x.astype(np.float64) - ref) / np.maximum(np.abs(ref), 1.0)))
 
 
-def build(problem):
+def build(problem, norm_keys=None):
     """mbrl_amd model / cost / sampler closures wired exactly as GoalStateAgent (agents.py:219-233),
-    or as RewardAgent (agents.py:336-362) for a reward-head problem."""
+    or as RewardAgent (agents.py:336-362) for a reward-head problem. norm_keys: the subset of
+    TransitionsDataset.normalizers()' keywords bound to the model (None: all of them, the agents' own
+    wiring; an unbound keyword is None in the model call, as in the reference)."""
+    def subset(kw):
+        return kw if norm_keys is None else {k: v for k, v in kw.items() if k in norm_keys}
     from mbrl_amd import data, env, models
     cfg = problem["cfg"]
     s, a, W, L = cfg["s"], cfg["a"], cfg["W"], cfg["L"]
@@ -38,7 +42,7 @@ def build(problem):
         nm = problem["norm"]
         ds = data.TransitionsDataset.from_statistics({k: {"mean": torch.from_numpy(nm[p + "_mean"]), "std": torch.from_numpy(nm[p + "_std"])}
                                       for k, p in (("observations", "obs"), ("actions", "act"), ("rewards", "rew"))})
-        kw = ds.normalizers(reward=True)
+        kw = subset(ds.normalizers(reward=True))
         model_fn = models.compose(functools.partial(m, **kw), operator.itemgetter(0))
         cost_fn = models.compose(functools.partial(m, **kw), operator.itemgetter(1))
         return m, model_fn, cost_fn, env.sample_action_fn(env.BoundedActionSpec(a, -1.0, 1.0))
@@ -56,7 +60,7 @@ def build(problem):
                                                    "std": torch.from_numpy(nm["obs_std"])},
                                   "actions": {"mean": torch.from_numpy(nm["act_mean"]),
                                               "std": torch.from_numpy(nm["act_std"])}})
-    model_fn = functools.partial(module, **ds.normalizers())
+    model_fn = functools.partial(module, **subset(ds.normalizers()))
     c = problem["cost"]
     cost_fn = models.goal_state_cost(models.SmoothAbsLoss(torch.from_numpy(c["weights"]), torch.from_numpy(c["goal"]),
                                                           c["alpha_state"]), models.CoshLoss(c["alpha_action"]))
