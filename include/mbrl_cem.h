@@ -82,9 +82,9 @@ enum { MBRL_PRECISION_F32 = 0, MBRL_PRECISION_F16X3 = 1, MBRL_PRECISION_F16X6 = 
  * Linear(W -> 1) beside the state head. */
 typedef struct {
     int32_t state_dim;   /* s  (observation dim, env_wrappers.py:86 flat 'observations') */
-    int32_t action_dim;  /* a */
-    int32_t hidden;      /* W  (any >= 1; zero-padded inside the packed stream) */
-    int32_t n_hidden;    /* L >= 1 */
+    int32_t action_dim;  /* a  (rollouts and plans: <= 48, else MBRL_EUNSUPPORTED) */
+    int32_t hidden;      /* W  (1 .. 1024, else MBRL_EUNSUPPORTED; zero-padded inside the packed stream) */
+    int32_t n_hidden;    /* L  (1 .. 4, else MBRL_EUNSUPPORTED) */
     int32_t ensemble;    /* E >= 1 */
     int32_t reward_head; /* 0 or 1 */
     int32_t precision;   /* MBRL_PRECISION_* (rollout only; the packed buffer holds every weight
@@ -273,7 +273,16 @@ int mbrl_mlp_pack(const mbrl_mlp_shape* shape, const float* const* weights, cons
  *          actions_out first (actions_out is then required).
  * costs: [E][N] per-member return sum_t cost(s_{t+1}, a_t), summed sequentially in t.
  * actions_out: [H][N][a] or NULL. states_out: [E][H][N][s] or NULL.
- * n_offset: global index of local candidate 0 (rank shard offset; keys the RNG). */
+ * n_offset: global index of local candidate 0 (rank shard offset; keys the RNG).
+ * W <= 1024, a <= 48 and L <= 4 are necessary, not sufficient: a 16-candidate workgroup must also fit
+ * 160 KiB (163,840 B) of LDS, else MBRL_EUNSUPPORTED "LDS footprint ... B exceeds 160 KiB", returned
+ * before the proposal draw or any other launch (the whole-plan entries may already have launched their
+ * initialisation kernel). With Wp = W rounded up to 64, 128, 256, 512 or 1024, lda = max(Wp,
+ * 32 ceil((s + a) / 32)) + 4 and po = 32 ceil((s + reward_head) / 32) the bytes are about
+ *   4 (32 lda + 128 (po + 4) + 16 s + 32 a + L Wp + po + 4 s + 2 a + 16),
+ * (64 (po + 4) in place of 128 (po + 4) for W <= 64), less the 128 (po + 4) term when L is 3, there is no reward head and 8 (po + 4) <= lda (the output
+ * partials then share an activation buffer). So W = 1024 runs s = 17, a = 6 with L <= 3 (160,640 B at
+ * L = 2) but not L = 4 (168,832 B), and s = 67, a = 21 only with L = 3. */
 int mbrl_rollout_cost(const mbrl_mlp_shape* shape, const void* packed, const mbrl_norm* norm,
                       const mbrl_cost* cost, const float* s0, int32_t s0_per_candidate,
                       const float* actions, const mbrl_sampler* sampler, int32_t N, int32_t H,

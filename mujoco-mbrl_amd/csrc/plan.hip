@@ -75,6 +75,22 @@ static int norm_stats_validate(const mbrl_norm* norm) {
     return MBRL_OK;
 }
 
+// Whether the output partials may live in the activation buffer the last hidden layer does not read
+// (RolloutArgs.part_alias) with nw waves per workgroup.
+static bool part_alias_ok(const Geometry& g, bool reward, int nw) {
+    return !reward && g.L >= 3 && (g.L & 1) && (size_t)(nw > 4 ? nw : 4) * g.pw <= (size_t)g.lda;
+}
+
+// Dynamic LDS of the 16-candidate fp32 tile as rollout_impl launches it (8 waves from Wpad = 128, the
+// partials aliased where they can be): the least any fp32 rollout of this shape needs.
+static size_t min_tile_lds_bytes(const Geometry& g, bool reward) {
+    RolloutArgs A{};
+    A.s = g.s; A.a = g.a; A.L = g.L; A.Wpad = g.Wpad; A.NOT = g.NOT; A.lda = g.lda; A.pw = g.pw;
+    A.nw = g.T >= 2 ? 8 : 4;
+    A.part_alias = part_alias_ok(g, reward, A.nw) ? 1 : 0;
+    return rollout_lds_bytes(A, 16);
+}
+
 int rollout_validate(const Geometry& g, const mbrl_norm* norm, const mbrl_cost* cost) {
     if (norm) {
         if (norm->unnormalize_reward && (!norm->rew_mean || !norm->rew_std))
@@ -89,6 +105,11 @@ int rollout_validate(const Geometry& g, const mbrl_norm* norm, const mbrl_cost* 
             return fail(MBRL_EINVAL, "state cost without weights/goal");
     }
     if (16 * g.a > 768) return fail(MBRL_EUNSUPPORTED, "action_dim %d too large (max 48)", g.a);
+    // the smallest fp32 tile (16 candidates) must fit LDS; refused here, before the proposal draw or any
+    // other launch, so a refused call leaves every buffer as it was
+    const bool reward = cost && cost->kind == MBRL_COST_MODEL_REWARD;
+    if (const size_t need = min_tile_lds_bytes(g, reward); need > 160 * 1024)
+        return fail(MBRL_EUNSUPPORTED, "LDS footprint %zu B exceeds 160 KiB", need);
     return MBRL_OK;
 }
 
@@ -268,11 +289,10 @@ int rollout_impl(const Geometry& g, const void* packed, const mbrl_norm* norm, c
     // 32-candidate tiles on 8 waves (two per SIMD) when the 8 partials fit the aliased activation
     // buffer: walker rollout 3.91 -> 3.83 ms, frac 0.883 -> 0.901 (profiles/r02_ab_r2_8waves.txt)
     if (R == 2 && g.T >= 2 && !A.reward && g.L >= 3 && (g.L & 1) && (size_t)8 * g.pw <= (size_t)g.lda) A.nw = 8;
-    auto alias_ok = [&]() {
-        return !A.reward && g.L >= 3 && (g.L & 1) && (size_t)(A.nw > 4 ? A.nw : 4) * g.pw <= (size_t)g.lda;
-    };
+    auto alias_ok = [&]() { return part_alias_ok(g, A.reward != 0, A.nw); };
     A.part_alias = alias_ok() ? 1 : 0;
     if (rollout_lds_bytes(A, 16 * R) > 160 * 1024) {
+        // the 16-candidate tile of min_tile_lds_bytes, which rollout_validate found to fit
         R = 1;
         A.nw = g.T >= 2 ? 8 : 4;
         A.part_alias = alias_ok() ? 1 : 0;
