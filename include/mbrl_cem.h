@@ -30,7 +30,8 @@ extern "C" {
 
 /* v13 also carries the MPPI calls (mbrl_mppi_update, mbrl_mppi_workspace_bytes, mbrl_mppi_plan and
  * mbrl_mppi_params): they were added within v13, purely additively -- no existing entry point, struct
- * or option changed, so the version did not move. */
+ * or option changed, so the version did not move. The receding-horizon CEM plan (mbrl_cem_rh_params,
+ * mbrl_cem_rh_workspace_bytes, mbrl_cem_plan_rh) joined them the same way. */
 #define MBRL_ABI_VERSION 13
 
 typedef struct ihipStream_t* mbrl_stream_t; /* == hipStream_t */
@@ -435,6 +436,48 @@ int mbrl_mppi_plan(const mbrl_mlp_shape* shape, const void* packed, const mbrl_n
                    float* sigma, float* actions_out, float* states_out, float* cost_hist, float* weight_hist,
                    float* mu_hist, float* sigma_hist, mbrl_event_t* rollout_events, void* workspace,
                    size_t ws_bytes, mbrl_stream_t stream);
+
+/* ---- receding-horizon CEM plan (warm start and elite carry-over, the two iCEM ingredients of Pinneri
+ * et al. 2020; not in the reference; added within ABI v13, additively, as the MPPI calls were).
+ * mbrl_cem_plan with three more inputs and a `keep` count Kc (0 <= Kc <= K):
+ *   init_mu_rows    [H][a] device or NULL: row t of the initial mean is init_mu_rows[t] clipped to [lo, hi]
+ *                   instead of params->cem.init_mu (e.g. the previous plan shifted by one step);
+ *   init_sigma_rows [H][a] device or NULL: row t of the initial std instead of params->cem.init_sigma. Every
+ *                   entry must be finite and > 0; the C call cannot read device rows, so this is the CALLER'S
+ *                   check (the Python layer makes it on the host and raises before the call);
+ *   carry_in        [Kc][H][a] device or NULL: the rows kept from the previous plan (its carry_out, shifted).
+ * Proposals of iteration i: candidate n < Kc takes kept_i[n] clipped to [lo, hi] (a NaN entry stays NaN:
+ * the row's return is then NaN and it sorts last) when a kept set exists -- kept_0 = carry_in where given,
+ * and always from iteration 1 on; every other candidate is drawn exactly as mbrl_cem_plan draws it, from
+ * Philox counter (n, t, i, d >> 2). The counter space does not move: a slot taken by a kept row skips its
+ * draw, so candidates n >= Kc are bit-identical to the plain plan's from the same mu / sigma.
+ * After iteration i's rollout the member-mean returns give two selections (both mbrl_select_elites,
+ * NAN_LAST, ascending candidate index): the K elites, refitted exactly as mbrl_cem_refit does over their
+ * action rows, and the Kc best, whose action rows become kept_{i+1}. A row's actions are read back from
+ * kept_i where the slot was filled from it, else regenerated from the counter RNG.
+ * Outputs: mu, sigma, actions_out, states_out and the records cost_hist, returns_hist, elite_hist as
+ * mbrl_cem_plan's. Optional (NULL = off): carry_out [Kc][H][a] = kept_I, the action rows of the last
+ * iteration's Kc best; carry_returns_out [Kc] their returns; kept_hist [I + 1][Kc][H][a], row i = kept_i
+ * (row 0: carry_in as given, or zeros without one).
+ * keep == 0 enqueues exactly mbrl_cem_plan's launches (the fused or split update, the pair rollouts); only
+ * the first launch differs where rows are given. keep > 0 runs each iteration's update as five small
+ * launches (two selections, the gather, the refit, the next proposals' scatter and draw).
+ * Before any launch: MBRL_EINVAL for bad mbrl_cem_params, keep outside [0, K], carry_in with keep == 0,
+ * NULL packed / s0 / actions_out / states_out / workspace or a workspace below
+ * mbrl_cem_rh_workspace_bytes (which returns 0 for a bad shape or bad params); MBRL_EUNSUPPORTED for
+ * N > 32768. Batched and sharded receding-horizon plans do not exist. */
+typedef struct {
+    mbrl_cem_params cem;
+    int32_t keep;  /* Kc */
+    int32_t _pad;
+} mbrl_cem_rh_params;
+size_t mbrl_cem_rh_workspace_bytes(const mbrl_mlp_shape* shape, const mbrl_cem_rh_params* params);
+int mbrl_cem_plan_rh(const mbrl_mlp_shape* shape, const void* packed, const mbrl_norm* norm, const mbrl_cost* cost,
+                     const float* s0, const mbrl_cem_rh_params* params, const float* init_mu_rows,
+                     const float* init_sigma_rows, const float* carry_in, float* mu, float* sigma,
+                     float* actions_out, float* states_out, float* carry_out, float* carry_returns_out,
+                     float* cost_hist, float* returns_hist, int64_t* elite_hist, float* kept_hist,
+                     mbrl_event_t* rollout_events, void* workspace, size_t ws_bytes, mbrl_stream_t stream);
 
 /* ---- gradient-descent planner: replaces GradientDescentPlanner's
  * _optimize_trajectory (planners.py:103-137) -- Adam(lr) on the action sequence through the dynamics

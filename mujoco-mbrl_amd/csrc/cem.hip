@@ -1111,6 +1111,22 @@ int refit_impl(const mbrl_sampler* sp, int H, int a, const int64_t* elite_idx, i
     return hip_check(hipGetLastError(), "refit launch");
 }
 
+int refit_staged_check(int a, int K) {
+    if (a < 1 || a > 64 || K < 1) return fail(MBRL_EINVAL, "refit: a=%d K=%d", a, K);
+    if ((size_t)((K + ELITE_CHUNK - 1) / ELITE_CHUNK) * a * sizeof(float) > 64 * 1024)
+        return fail(MBRL_EUNSUPPORTED, "refit: K=%d x a=%d exceeds the refit kernel's LDS", K, a);
+    return MBRL_OK;
+}
+
+int refit_staged_impl(const float* aelite, int H, int a, int K, float alpha, const float* mu, const float* sigma,
+                      float* mu_out, float* sigma_out, hipStream_t stream) {
+    if (int rc = refit_staged_check(a, K)) return rc;
+    const int nch = (K + ELITE_CHUNK - 1) / ELITE_CHUNK;
+    hipLaunchKernelGGL(refit_kernel, dim3(H), dim3(256), (size_t)nch * a * sizeof(float), stream, aelite, a, K, alpha,
+                       1.0f - alpha, mu, sigma, mu_out, sigma_out);
+    return hip_check(hipGetLastError(), "refit launch");
+}
+
 // The fused per-iteration update (cem_update_kernel) when its selection fits in registers (N <= 32768)
 // and the selection or refit working set fits LDS; KPT of that selection, 0 if not fusable.
 int update_kpt(int N, int K, int a) {

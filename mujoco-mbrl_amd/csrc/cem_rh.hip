@@ -1,0 +1,213 @@
+// Receding-horizon CEM (include/mbrl_cem.h mbrl_cem_plan_rh; DESIGN.md "Receding-horizon CEM"): the kernels
+// around the selection and refit_kernel when rows are kept from one iteration (or plan) to the next --
+// the plan's first launch, the gather of the elites' and the best rows' actions, and the next proposals'
+// scatter and draw -- with their launchers (mbrl_internal.h). The plan loop is in plan.hip.
+//
+// Layouts: proposals `actions` [H][N][a] time-major (the rollout's), kept rows [Kc][H][a] row-contiguous
+// (what a caller carries from plan to plan), the elites' actions [H][K][a] (refit_kernel's). Every kernel
+// is a grid-stride loop of one thread per (row, t, d >> 2) -- a Philox block's four dimensions -- ordered
+// so that consecutive threads write consecutive addresses of the buffer they fill, with 16-byte loads and
+// stores where a is a multiple of 4 and the buffers are 16-byte aligned (VEC). Plain loads and stores
+// only: nothing here waits on another workgroup.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <initializer_list>
+
+#include "mbrl_host.h"
+#include "mbrl_rng.h"
+
+namespace mbrl {
+
+typedef float rh_f4 __attribute__((ext_vector_type(4)));
+
+// clip of a kept entry: a NaN stays NaN (np.minimum(np.maximum(x, lo), hi)), so a poisoned row's return
+// is NaN and the row sorts last; fminf / fmaxf alone would turn it into lo.
+__device__ __forceinline__ float kept_clip(float x, float lo, float hi) {
+    return x != x ? x : fminf(fmaxf(x, lo), hi);
+}
+
+// Dimensions 4g .. 4g+3 of a kept row's step (src = the step's [a] floats), clipped.
+template <bool VEC>
+__device__ __forceinline__ void kept_load4(const float* __restrict__ src, int g, int a, float lo, float hi, float v[4]) {
+    if (VEC) {
+        const rh_f4 x = *reinterpret_cast<const rh_f4*>(src + 4 * g);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = kept_clip(x[j], lo, hi);
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = 4 * g + j < a ? kept_clip(src[4 * g + j], lo, hi) : 0.f;
+    }
+}
+
+// The same four dimensions drawn from the counter RNG around (mu_t, sigma_t) (the step's [a] floats each),
+// as sample_kernel and gather_elites_kernel draw them.
+__device__ __forceinline__ void draw4(uint64_t seed, uint32_t n, uint32_t t, uint32_t it, int g, int a,
+                                      const float* __restrict__ mu_t, const float* __restrict__ sigma_t, float lo,
+                                      float hi, float v[4]) {
+    float z[4];
+    cem_normal4(seed, n, t, it, (uint32_t)g, z);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int d = 4 * g + j;
+        v[j] = d < a ? cem_action(mu_t[d], sigma_t[d], z[j], lo, hi) : 0.f;
+    }
+}
+
+template <bool VEC>
+__device__ __forceinline__ void store4(float* __restrict__ dst, int g, int a, const float v[4]) {
+    if (VEC) {
+        *reinterpret_cast<rh_f4*>(dst + 4 * g) = rh_f4{v[0], v[1], v[2], v[3]};
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (4 * g + j < a) dst[4 * g + j] = v[j];
+    }
+}
+
+template <bool VEC>
+__global__ void __launch_bounds__(256) rh_init_kernel(const RhInitArgs A) {
+    const size_t gid = blockIdx.x * (size_t)blockDim.x + threadIdx.x, gsz = (size_t)gridDim.x * blockDim.x;
+#pragma unroll
+    for (int r = 0; r < 2; ++r)
+        for (size_t i = gid; A.zero.ptr[r] && i < A.zero.words[r]; i += gsz) A.zero.ptr[r][i] = 0u;
+    if (A.s0_src)
+        for (size_t i = gid; i < (size_t)A.s; i += gsz) A.s0_dst[i] = A.s0_src[i];
+    const int a = A.a;
+    const size_t Ha = (size_t)A.H * a;
+    // the initial distribution: what the draws below use, whether or not this thread also stores it
+    auto mu0 = [&](size_t i) { return A.mu_rows ? fminf(fmaxf(A.mu_rows[i], A.lo), A.hi) : A.init_mu; };
+    auto sg0 = [&](size_t i) { return A.sigma_rows ? A.sigma_rows[i] : A.init_sigma; };
+    for (size_t i = gid; i < Ha; i += gsz) {
+        A.mu[i] = mu0(i);
+        A.sigma[i] = sg0(i);
+    }
+    if (A.kept0)
+        for (size_t i = gid; i < (size_t)A.Kc * Ha; i += gsz) A.kept0[i] = A.carry_in ? A.carry_in[i] : 0.f;
+    if (!A.actions) return;
+    const int G = (a + 3) >> 2, N = A.N;
+    const size_t total = (size_t)A.H * N * G;
+    for (size_t i = gid; i < total; i += gsz) {
+        const int g = (int)(i % G), n = (int)((i / G) % N), t = (int)(i / G / N);
+        float v[4];
+        if (A.carry_in && n < A.Kc) {
+            kept_load4<VEC>(A.carry_in + ((size_t)n * A.H + t) * a, g, a, A.lo, A.hi, v);
+        } else {
+            float z[4];
+            cem_normal4(A.seed, (uint32_t)n, (uint32_t)t, 0u, (uint32_t)g, z);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int d = 4 * g + j;
+                v[j] = d < a ? cem_action(mu0((size_t)t * a + d), sg0((size_t)t * a + d), z[j], A.lo, A.hi) : 0.f;
+            }
+        }
+        store4<VEC>(A.actions + ((size_t)t * N + n) * a, g, a, v);
+    }
+}
+
+template <bool VEC>
+__global__ void __launch_bounds__(256) rh_gather_kernel(const RhGatherArgs A) {
+    const size_t gid = blockIdx.x * (size_t)blockDim.x + threadIdx.x, gsz = (size_t)gridDim.x * blockDim.x;
+    const int a = A.a, H = A.H, K = A.K, Kc = A.Kc, G = (a + 3) >> 2;
+    if (A.best_returns)
+        for (size_t i = gid; i < (size_t)Kc; i += gsz) {
+            const int64_t b = A.best[i];   // (a candidate index; anything else reads nothing)
+            A.best_returns[i] = (uint64_t)b < (uint64_t)A.N ? A.returns[b] : __uint_as_float(0x7FC00000u);
+        }
+    // threads [0, H K G): elite e's step t in (t, e, g) order, aelite's; then [0, Kc H G): best row j's step
+    // t in (j, t, g) order, the kept rows'
+    const size_t n_el = (size_t)H * K * G, total = n_el + (size_t)Kc * H * G;
+    for (size_t i = gid; i < total; i += gsz) {
+        int g, t, n;
+        float *dst, *dst2 = nullptr;
+        if (i < n_el) {
+            g = (int)(i % G);
+            const int e = (int)((i / G) % K);
+            t = (int)(i / G / K);
+            n = (int)A.elites[e];
+            dst = A.aelite + ((size_t)t * K + e) * a;
+        } else {
+            const size_t q = i - n_el;
+            g = (int)(q % G);
+            t = (int)((q / G) % H);
+            const int j = (int)(q / G / H);
+            n = (int)A.best[j];
+            dst = A.kept_next + ((size_t)j * H + t) * a;
+            if (A.kept_copy) dst2 = A.kept_copy + ((size_t)j * H + t) * a;
+        }
+        float v[4];
+        if (A.from_kept && (unsigned)n < (unsigned)Kc)
+            kept_load4<VEC>(A.kept_cur + ((size_t)n * H + t) * a, g, a, A.lo, A.hi, v);
+        else
+            draw4(A.seed, (uint32_t)n, (uint32_t)t, (uint32_t)A.iteration, g, a, A.mu + (size_t)t * a,
+                  A.sigma + (size_t)t * a, A.lo, A.hi, v);
+        store4<VEC>(dst, g, a, v);
+        if (dst2) store4<VEC>(dst2, g, a, v);
+    }
+}
+
+template <bool VEC>
+__global__ void __launch_bounds__(256) rh_draw_kernel(const RhDrawArgs A) {
+    const size_t gid = blockIdx.x * (size_t)blockDim.x + threadIdx.x, gsz = (size_t)gridDim.x * blockDim.x;
+    const int a = A.a, H = A.H, N = A.N, G = (a + 3) >> 2;
+    if (A.fin_actions)
+        for (size_t i = gid; i < (size_t)H * a; i += gsz) {
+            const float m = A.mu[i];
+            if (A.fin_mu) A.fin_mu[i] = m;
+            if (A.fin_sigma) A.fin_sigma[i] = A.sigma[i];
+            A.fin_actions[i] = fminf(fmaxf(m, A.lo), A.hi);
+        }
+    if (!A.actions) return;
+    const size_t total = (size_t)H * N * G;
+    for (size_t i = gid; i < total; i += gsz) {
+        const int g = (int)(i % G), n = (int)((i / G) % N), t = (int)(i / G / N);
+        float v[4];
+        if (n < A.Kc)
+            kept_load4<VEC>(A.kept + ((size_t)n * H + t) * a, g, a, A.lo, A.hi, v);
+        else
+            draw4(A.seed, (uint32_t)n, (uint32_t)t, (uint32_t)A.iteration, g, a, A.mu + (size_t)t * a,
+                  A.sigma + (size_t)t * a, A.lo, A.hi, v);
+        store4<VEC>(A.actions + ((size_t)t * N + n) * a, g, a, v);
+    }
+}
+
+// One thread per Philox block, at most 8192 workgroups of 256 (sample_impl's grid).
+static dim3 rh_grid(size_t threads) {
+    const size_t b = (threads + 255) / 256;
+    return dim3((unsigned)(b < 1 ? 1 : (b < 8192 ? b : 8192)));
+}
+
+static bool aligned16(std::initializer_list<const void*> ps) {
+    for (const void* p : ps)
+        if (reinterpret_cast<uintptr_t>(p) & 15) return false;
+    return true;
+}
+
+hipError_t launch_rh_init(const RhInitArgs& A, hipStream_t stream) {
+    const size_t G = (size_t)(A.a + 3) / 4;
+    const size_t threads = A.actions ? (size_t)A.H * A.N * G : (size_t)A.H * A.a;
+    const bool vec = (A.a & 3) == 0 && aligned16({A.carry_in, A.actions});
+    if (vec) hipLaunchKernelGGL(rh_init_kernel<true>, rh_grid(threads), dim3(256), 0, stream, A);
+    else hipLaunchKernelGGL(rh_init_kernel<false>, rh_grid(threads), dim3(256), 0, stream, A);
+    return hipGetLastError();
+}
+
+hipError_t launch_rh_gather(const RhGatherArgs& A, hipStream_t stream) {
+    const size_t G = (size_t)(A.a + 3) / 4;
+    const bool vec = (A.a & 3) == 0 && aligned16({A.kept_cur, A.aelite, A.kept_next, A.kept_copy});
+    const dim3 grid = rh_grid((size_t)A.H * ((size_t)A.K + A.Kc) * G);
+    if (vec) hipLaunchKernelGGL(rh_gather_kernel<true>, grid, dim3(256), 0, stream, A);
+    else hipLaunchKernelGGL(rh_gather_kernel<false>, grid, dim3(256), 0, stream, A);
+    return hipGetLastError();
+}
+
+hipError_t launch_rh_draw(const RhDrawArgs& A, hipStream_t stream) {
+    const size_t G = (size_t)(A.a + 3) / 4;
+    const size_t threads = A.actions ? (size_t)A.H * A.N * G : (size_t)A.H * A.a;
+    const bool vec = (A.a & 3) == 0 && aligned16({A.kept, A.actions});
+    if (vec) hipLaunchKernelGGL(rh_draw_kernel<true>, rh_grid(threads), dim3(256), 0, stream, A);
+    else hipLaunchKernelGGL(rh_draw_kernel<false>, rh_grid(threads), dim3(256), 0, stream, A);
+    return hipGetLastError();
+}
+
+}  // namespace mbrl

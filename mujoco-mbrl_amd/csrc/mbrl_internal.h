@@ -379,6 +379,52 @@ struct InitZero {
 void launch_cem_init(dim3 grid, hipStream_t stream, uint64_t seed, float init_mu, float init_sigma, float lo, float hi,
                      int H, int a, int N, float* mu, float* sigma, float* actions, const float* s0_src, int s,
                      float* s0_dst, int draw_off, const InitZero& zero, const float* mu_rows);
+// refit_kernel alone over elite actions already staged as aelite [H][K][a] (the second launch of
+// refit_impl's staged path): the receding-horizon plan gathers them itself (cem_rh.hip).
+int refit_staged_check(int a, int K);
+int refit_staged_impl(const float* aelite, int H, int a, int K, float alpha, const float* mu, const float* sigma,
+                      float* mu_out, float* sigma_out, hipStream_t stream);
+
+// ---- receding-horizon CEM (cem_rh.hip; include/mbrl_cem.h mbrl_cem_plan_rh). kept rows are [Kc][H][a].
+// The plan's first launch where cem_init_kernel does not apply (sigma rows, or kept rows): the hand-off
+// words zeroed, the s0 copy, the distribution rows (mu_rows / sigma_rows, each or NULL), kept_0 (carry_in
+// or zeros, when kept0 is given) and, with `actions`, iteration 0's proposals: slots [0, Kc) from
+// carry_in where given, every other candidate drawn as cem_init_kernel draws it.
+struct RhInitArgs {
+    uint64_t seed;
+    float init_mu, init_sigma, lo, hi;
+    int H, a, N, Kc, s;
+    const float *mu_rows, *sigma_rows, *carry_in;
+    float *mu, *sigma, *actions, *kept0;
+    const float* s0_src;
+    float* s0_dst;
+    InitZero zero;
+};
+hipError_t launch_rh_init(const RhInitArgs& A, hipStream_t stream);
+// After iteration `iteration`'s two selections: the elites' action rows into aelite [H][K][a] (refit_kernel's
+// layout) and the best rows into kept_next [Kc][H][a] (and kept_copy, best_returns where given). A row of
+// candidate n < Kc is read from kept_cur when from_kept, else regenerated from the counter RNG.
+struct RhGatherArgs {
+    uint64_t seed;
+    int iteration, N, H, a, K, Kc, from_kept;
+    float lo, hi;
+    const float *mu, *sigma, *kept_cur, *returns;
+    const int64_t *elites, *best;
+    float *aelite, *kept_next, *kept_copy, *best_returns;
+};
+hipError_t launch_rh_gather(const RhGatherArgs& A, hipStream_t stream);
+// After the refit: iteration + 1's proposals (kept rows scattered into slots [0, Kc), the rest drawn from
+// mu / sigma) where `actions` is given, and the plan outputs (fin_*: mu / sigma copies, clip(mu)) where
+// fin_actions is given.
+struct RhDrawArgs {
+    uint64_t seed;
+    int iteration, H, a, N, Kc;
+    float lo, hi;
+    const float *mu, *sigma, *kept;
+    float *actions, *fin_mu, *fin_sigma, *fin_actions;
+};
+hipError_t launch_rh_draw(const RhDrawArgs& A, hipStream_t stream);
+
 // MBRL_OPT_SHARD_EMULATE 2 (plan_sharded.hip): the all-gather's buffers in one launch. The kernel
 // stays in cem.hip with the stamp buffer it writes in the diagnostic build.
 void launch_emu_gather(const float* local, const float* kept, int G, int rank, size_t slot, const unsigned* own_status,

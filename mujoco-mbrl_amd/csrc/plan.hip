@@ -1,6 +1,7 @@
 // The plans: host dispatch of the rollout and trajectory kernels (rollout_impl, traj_impl), the plan
 // workspaces, the helpers the plan loops share (mbrl_plan.h) and the single-GPU plan entries
-// (include/mbrl_cem.h): rollout cost, trajectory, CEM plan, MPPI plan, batched CEM plan.
+// (include/mbrl_cem.h): rollout cost, trajectory, CEM plan, receding-horizon CEM plan, MPPI plan, batched
+// CEM plan.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -491,29 +492,32 @@ size_t mbrl_cem_workspace_bytes(const mbrl_mlp_shape* shape, const mbrl_cem_para
     return plan_ws(g, params, nullptr).bytes;
 }
 
-int mbrl_cem_plan(const mbrl_mlp_shape* shape, const void* packed, const mbrl_norm* norm, const mbrl_cost* cost,
-                  const float* s0_in, const mbrl_cem_params* p, float* mu, float* sigma, float* actions_out,
-                  float* states_out, float* cost_hist, float* returns_hist, int64_t* elite_hist,
-                  mbrl_event_t* rollout_events, void* workspace, size_t ws_bytes, mbrl_stream_t stream_) {
-    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-    Geometry g;
-    int rc = shape_geometry(shape, &g);
-    if (rc) return rc;
-    if (!p) return fail(MBRL_EINVAL, "params is NULL");
-    if ((rc = cem_params_check(p))) return rc;
-    if (!actions_out || !states_out || !workspace) return fail(MBRL_EINVAL, "actions_out/states_out/workspace NULL");
-    if (!s0_in) return fail(MBRL_EINVAL, "s0 is NULL");
-    PlanWs w = plan_ws(g, p, workspace);
-    if (ws_bytes < w.bytes) return fail(MBRL_EWORKSPACE, "workspace %zu < %zu", ws_bytes, w.bytes);
-    if ((rc = pair_forced_check(g, p->N))) return rc;
+// mbrl_cem_plan's launches, the arguments checked and the workspace carved: shared with the receding-horizon
+// plan that keeps no rows (mbrl_cem_plan_rh, keep == 0), which differs in the first launch alone -- the
+// initial distribution's rows (mu_rows / sigma_rows, each or NULL).
+static int cem_plan_run(const Geometry& g, const void* packed, const mbrl_norm* norm, const mbrl_cost* cost,
+                        const float* s0_in, const mbrl_cem_params* p, const float* mu_rows, const float* sigma_rows,
+                        float* mu, float* sigma, float* actions_out, float* states_out, float* cost_hist,
+                        float* returns_hist, int64_t* elite_hist, mbrl_event_t* rollout_events, const PlanWs& w,
+                        hipStream_t stream) {
+    int rc;
     const FusePlan f = fuse_plan(p->N, p->N, p->K, g.a);
     // one first launch: distribution rows, the s0 copy, iteration 0's proposals (where the update
     // fuses the draw), and the plan's hand-off words zeroed (no memset before the pair / trajectory
     // launches)
     const InitZero z = plan_zero(g, p->N, w.pair, w.traj);
-    launch_cem_init(dim3(p->H * (f.fuse_draw ? draw_slices(p->H, 1, p->N, g.a) : 1), 1), stream, p->seed, p->init_mu,
-                    p->init_sigma, p->lo, p->hi, p->H, g.a, p->N, w.mu[0], w.sigma[0],
-                    f.fuse_draw ? w.actions : nullptr, s0_in, g.s, w.s0, 0, z, nullptr);
+    if (sigma_rows) {   // (cem_init_kernel has no sigma rows: rh_init_kernel, the same values)
+        RhInitArgs A{};
+        A.seed = p->seed; A.init_mu = p->init_mu; A.init_sigma = p->init_sigma; A.lo = p->lo; A.hi = p->hi;
+        A.H = p->H; A.a = g.a; A.N = p->N; A.s = g.s; A.mu_rows = mu_rows; A.sigma_rows = sigma_rows;
+        A.mu = w.mu[0]; A.sigma = w.sigma[0]; A.actions = f.fuse_draw ? w.actions : nullptr;
+        A.s0_src = s0_in; A.s0_dst = w.s0; A.zero = z;
+        if ((rc = hip_check(launch_rh_init(A, stream), "init launch"))) return rc;
+    } else {
+        launch_cem_init(dim3(p->H * (f.fuse_draw ? draw_slices(p->H, 1, p->N, g.a) : 1), 1), stream, p->seed,
+                        p->init_mu, p->init_sigma, p->lo, p->hi, p->H, g.a, p->N, w.mu[0], w.sigma[0],
+                        f.fuse_draw ? w.actions : nullptr, s0_in, g.s, w.s0, 0, z, mu_rows);
+    }
     unsigned pair_epoch = 0;
     const float* s0 = w.s0;   // the workspace copy (s0_in may be mapped host memory)
     int cur = 0;
@@ -549,6 +553,158 @@ int mbrl_cem_plan(const mbrl_mlp_shape* shape, const void* packed, const mbrl_no
                           z.ptr[1] != nullptr);
     if (rc) return rc;
     return hip_check(hipGetLastError(), "plan launch");
+}
+
+int mbrl_cem_plan(const mbrl_mlp_shape* shape, const void* packed, const mbrl_norm* norm, const mbrl_cost* cost,
+                  const float* s0_in, const mbrl_cem_params* p, float* mu, float* sigma, float* actions_out,
+                  float* states_out, float* cost_hist, float* returns_hist, int64_t* elite_hist,
+                  mbrl_event_t* rollout_events, void* workspace, size_t ws_bytes, mbrl_stream_t stream_) {
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    Geometry g;
+    int rc = shape_geometry(shape, &g);
+    if (rc) return rc;
+    if (!p) return fail(MBRL_EINVAL, "params is NULL");
+    if ((rc = cem_params_check(p))) return rc;
+    if (!actions_out || !states_out || !workspace) return fail(MBRL_EINVAL, "actions_out/states_out/workspace NULL");
+    if (!s0_in) return fail(MBRL_EINVAL, "s0 is NULL");
+    PlanWs w = plan_ws(g, p, workspace);
+    if (ws_bytes < w.bytes) return fail(MBRL_EWORKSPACE, "workspace %zu < %zu", ws_bytes, w.bytes);
+    if ((rc = pair_forced_check(g, p->N))) return rc;
+    return cem_plan_run(g, packed, norm, cost, s0_in, p, nullptr, nullptr, mu, sigma, actions_out, states_out,
+                        cost_hist, returns_hist, elite_hist, rollout_events, w, stream);
+}
+
+// ---- receding-horizon CEM (include/mbrl_cem.h mbrl_cem_plan_rh; kernels in cem_rh.hip): mbrl_cem_plan's
+// workspace first, then what kept rows need -- the two kept sets [Kc][H][a] (iteration i reads one and
+// writes the other), the best indices and the returns the carry's are read from.
+struct RhWs {
+    PlanWs plan;
+    float *kept[2], *rets;
+    int64_t* best;
+    size_t bytes;
+};
+
+static RhWs rh_ws(const Geometry& g, const mbrl_cem_rh_params* rp, void* base) {
+    RhWs w{};
+    w.plan = plan_ws(g, &rp->cem, base);
+    WsCursor c(base);
+    c.off = w.plan.bytes;
+    const size_t kb = (size_t)rp->keep * rp->cem.H * g.a * 4;
+    w.kept[0] = c.take<float>(kb); w.kept[1] = c.take<float>(kb);
+    w.best = c.take<int64_t>((size_t)rp->keep * 8);
+    w.rets = c.take<float>(rp->keep ? (size_t)rp->cem.N * 4 : 0);
+    w.bytes = c.off;
+    return w;
+}
+
+static int rh_params_check(const mbrl_cem_rh_params* rp) {
+    if (!rp) return fail(MBRL_EINVAL, "cem_plan_rh: params is NULL");
+    if (int rc = cem_params_check(&rp->cem)) return rc;
+    if (rp->keep < 0 || rp->keep > rp->cem.K)
+        return fail(MBRL_EINVAL, "cem_plan_rh: keep=%d outside [0, K=%d]", rp->keep, rp->cem.K);
+    return MBRL_OK;
+}
+
+size_t mbrl_cem_rh_workspace_bytes(const mbrl_mlp_shape* shape, const mbrl_cem_rh_params* params) {
+    Geometry g;
+    if (shape_geometry(shape, &g) != MBRL_OK || rh_params_check(params) != MBRL_OK) return 0;
+    return rh_ws(g, params, nullptr).bytes;
+}
+
+// keep > 0: every iteration is the rollout of the proposals in w.plan.actions, then five small launches --
+// the K elites, the Kc best (the same returns selected twice), the gather of both sets' action rows, the
+// refit over the gathered elites, and the next proposals (kept rows scattered into slots [0, Kc), the rest
+// drawn) or, on the last iteration, the plan outputs. kept_i lives in kept_hist's row i where the caller
+// records, else in the workspace's two buffers; iteration 0 reads carry_in where it is.
+static int cem_plan_rh_kept(const Geometry& g, const void* packed, const mbrl_norm* norm, const mbrl_cost* cost,
+                            const float* s0_in, const mbrl_cem_rh_params* rp, const float* mu_rows,
+                            const float* sigma_rows, const float* carry_in, float* mu, float* sigma,
+                            float* actions_out, float* states_out, float* carry_out, float* carry_returns_out,
+                            float* cost_hist, float* returns_hist, int64_t* elite_hist, float* kept_hist,
+                            mbrl_event_t* rollout_events, const RhWs& rw, hipStream_t stream) {
+    const mbrl_cem_params* p = &rp->cem;
+    const PlanWs& w = rw.plan;
+    const int Kc = rp->keep;
+    const size_t kept_floats = (size_t)Kc * p->H * g.a;
+    auto kept_at = [&](int i) { return kept_hist ? kept_hist + (size_t)i * kept_floats : rw.kept[i & 1]; };
+    int rc;
+    const InitZero z = plan_zero(g, p->N, w.pair, w.traj);
+    {
+        RhInitArgs A{};
+        A.seed = p->seed; A.init_mu = p->init_mu; A.init_sigma = p->init_sigma; A.lo = p->lo; A.hi = p->hi;
+        A.H = p->H; A.a = g.a; A.N = p->N; A.Kc = Kc; A.s = g.s;
+        A.mu_rows = mu_rows; A.sigma_rows = sigma_rows; A.carry_in = carry_in;
+        A.mu = w.mu[0]; A.sigma = w.sigma[0]; A.actions = w.actions; A.kept0 = kept_hist;
+        A.s0_src = s0_in; A.s0_dst = w.s0; A.zero = z;
+        if ((rc = hip_check(launch_rh_init(A, stream), "init launch"))) return rc;
+    }
+    unsigned pair_epoch = 0;
+    const float* s0 = w.s0;   // the workspace copy (s0_in may be mapped host memory)
+    int cur = 0;
+    for (int it = 0; it < p->iterations; ++it) {
+        const bool last = it + 1 == p->iterations;
+        float* costs = cost_hist ? cost_hist + (size_t)it * g.E * p->N : w.costs;
+        int64_t* elites = elite_hist ? elite_hist + (size_t)it * p->K : w.elites;
+        float* rets = returns_hist ? returns_hist + (size_t)it * p->N : rw.rets;
+        if ((rc = record_rollout_event(rollout_events, 2 * it, stream))) return rc;
+        rc = rollout_impl(g, packed, norm, cost, s0, 0, w.actions, nullptr, p->N, p->H, 0, costs, w.actions, nullptr,
+                          stream, pair_area_bytes(g, p->N) ? w.pair : nullptr, z.ptr[0] ? &pair_epoch : nullptr);
+        if (rc) return rc;
+        if ((rc = record_rollout_event(rollout_events, 2 * it + 1, stream))) return rc;
+        const size_t keys_bytes = align256((size_t)p->N * 4);
+        if ((rc = select_impl(costs, g.E, p->N, p->K, MBRL_NAN_LAST, elites, rets, w.keys, keys_bytes, stream))) return rc;
+        if ((rc = select_impl(costs, g.E, p->N, Kc, MBRL_NAN_LAST, rw.best, nullptr, w.keys, keys_bytes, stream)))
+            return rc;
+        RhGatherArgs G{};
+        G.seed = p->seed; G.iteration = it; G.N = p->N; G.H = p->H; G.a = g.a; G.K = p->K; G.Kc = Kc;
+        G.from_kept = it > 0 || carry_in; G.lo = p->lo; G.hi = p->hi;
+        G.mu = w.mu[cur]; G.sigma = w.sigma[cur]; G.kept_cur = it == 0 ? carry_in : kept_at(it); G.returns = rets;
+        G.elites = elites; G.best = rw.best; G.aelite = w.aelite; G.kept_next = kept_at(it + 1);
+        G.kept_copy = last ? carry_out : nullptr; G.best_returns = last ? carry_returns_out : nullptr;
+        if ((rc = hip_check(launch_rh_gather(G, stream), "gather launch"))) return rc;
+        rc = refit_staged_impl(w.aelite, p->H, g.a, p->K, p->alpha, w.mu[cur], w.sigma[cur], w.mu[cur ^ 1],
+                               w.sigma[cur ^ 1], stream);
+        if (rc) return rc;
+        RhDrawArgs D{};
+        D.seed = p->seed; D.iteration = it + 1; D.H = p->H; D.a = g.a; D.N = p->N; D.Kc = Kc; D.lo = p->lo; D.hi = p->hi;
+        D.mu = w.mu[cur ^ 1]; D.sigma = w.sigma[cur ^ 1]; D.kept = kept_at(it + 1);
+        D.actions = last ? nullptr : w.actions;
+        D.fin_mu = last ? mu : nullptr; D.fin_sigma = last ? sigma : nullptr; D.fin_actions = last ? actions_out : nullptr;
+        if ((rc = hip_check(launch_rh_draw(D, stream), "draw launch"))) return rc;
+        cur ^= 1;
+    }
+    rc = final_trajectory(g, packed, norm, s0, actions_out, p->H, states_out, w.states, w.traj, stream,
+                          z.ptr[1] != nullptr);
+    if (rc) return rc;
+    return hip_check(hipGetLastError(), "plan launch");
+}
+
+int mbrl_cem_plan_rh(const mbrl_mlp_shape* shape, const void* packed, const mbrl_norm* norm, const mbrl_cost* cost,
+                     const float* s0_in, const mbrl_cem_rh_params* rp, const float* init_mu_rows,
+                     const float* init_sigma_rows, const float* carry_in, float* mu, float* sigma, float* actions_out,
+                     float* states_out, float* carry_out, float* carry_returns_out, float* cost_hist,
+                     float* returns_hist, int64_t* elite_hist, float* kept_hist, mbrl_event_t* rollout_events,
+                     void* workspace, size_t ws_bytes, mbrl_stream_t stream_) {
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    Geometry g;
+    int rc = shape_geometry(shape, &g);
+    if (rc) return rc;
+    if ((rc = rh_params_check(rp))) return rc;
+    if (carry_in && rp->keep == 0) return fail(MBRL_EINVAL, "cem_plan_rh: carry_in given with keep == 0");
+    if (!packed || !actions_out || !states_out || !workspace)
+        return fail(MBRL_EINVAL, "cem_plan_rh: packed/actions_out/states_out/workspace NULL");
+    if (!s0_in) return fail(MBRL_EINVAL, "cem_plan_rh: s0 is NULL");
+    const RhWs w = rh_ws(g, rp, workspace);
+    if (ws_bytes < w.bytes) return fail(MBRL_EINVAL, "cem_plan_rh: workspace %zu < %zu", ws_bytes, w.bytes);
+    if (rp->cem.N > 32768) return fail(MBRL_EUNSUPPORTED, "cem_plan_rh: N=%d exceeds 32768", rp->cem.N);
+    if ((rc = pair_forced_check(g, rp->cem.N))) return rc;
+    if (rp->keep == 0)
+        return cem_plan_run(g, packed, norm, cost, s0_in, &rp->cem, init_mu_rows, init_sigma_rows, mu, sigma,
+                            actions_out, states_out, cost_hist, returns_hist, elite_hist, rollout_events, w.plan, stream);
+    if ((rc = refit_staged_check(g.a, rp->cem.K))) return rc;
+    return cem_plan_rh_kept(g, packed, norm, cost, s0_in, rp, init_mu_rows, init_sigma_rows, carry_in, mu, sigma,
+                            actions_out, states_out, carry_out, carry_returns_out, cost_hist, returns_hist, elite_hist,
+                            kept_hist, rollout_events, w, stream);
 }
 
 // Workspace layout for mbrl_mppi_plan (PlanWs without the selection's and the elites' scratch).

@@ -67,6 +67,7 @@ EXPORTED = (
     "mbrl_build_info", "mbrl_event_create", "mbrl_event_record", "mbrl_stream_wait_event", "mbrl_event_synchronize",
     "mbrl_event_destroy",
     "mbrl_mppi_update", "mbrl_mppi_workspace_bytes", "mbrl_mppi_plan",
+    "mbrl_cem_rh_workspace_bytes", "mbrl_cem_plan_rh",
 )
 
 
@@ -97,6 +98,11 @@ class CemParams(ctypes.Structure):
     _fields_ = [("N", c_int32), ("H", c_int32), ("K", c_int32), ("iterations", c_int32),
                 ("alpha", c_float), ("lo", c_float), ("hi", c_float), ("init_mu", c_float),
                 ("init_sigma", c_float), ("_pad", c_int32), ("seed", c_uint64)]
+
+
+class CemRhParams(ctypes.Structure):
+    """mbrl_cem_rh_params (include/mbrl_cem.h; added within ABI v13): a CemParams and the keep count Kc."""
+    _fields_ = [("cem", CemParams), ("keep", c_int32), ("_pad", c_int32)]
 
 
 class MppiParams(ctypes.Structure):
@@ -195,6 +201,9 @@ def load():
         "mbrl_mppi_workspace_bytes": (c_size_t, [POINTER(MlpShape), POINTER(MppiParams)]),
         "mbrl_mppi_plan": (c_int32, [POINTER(MlpShape), P, POINTER(Norm), POINTER(Cost), P, POINTER(MppiParams), P,
                                      P, P, P, P, P, P, P, P, P, P, c_size_t, P]),
+        "mbrl_cem_rh_workspace_bytes": (c_size_t, [POINTER(MlpShape), POINTER(CemRhParams)]),
+        "mbrl_cem_plan_rh": (c_int32, [POINTER(MlpShape), P, POINTER(Norm), POINTER(Cost), P, POINTER(CemRhParams),
+                                       P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, c_size_t, P]),
         "mbrl_comm_unique_id": (c_int32, [P]),
         "mbrl_comm_init": (c_int32, [P, c_int32, c_int32, POINTER(c_void_p)]),
         "mbrl_comm_destroy": (c_int32, [P]),
@@ -353,7 +362,7 @@ def require_gpu(t):
         raise RuntimeError("mbrl_amd fused path needs CUDA (HIP) tensors; got a CPU tensor")
 
 
-__all__ = ["load", "check", "ptr", "stream_handle", "MlpShape", "Norm", "Cost", "Sampler", "CemParams", "MppiParams",
+__all__ = ["load", "check", "ptr", "stream_handle", "MlpShape", "Norm", "Cost", "Sampler", "CemParams", "CemRhParams", "MppiParams",
            "EXPORTED", "MBRL_NAN_LAST", "MBRL_NAN_FIRST", "MBRL_COST_GOAL_STATE", "MBRL_COST_MODEL_REWARD",
            "ABI_VERSION", "c_int64", "MBRL_PRECISION_F32", "MBRL_PRECISION_F16X3", "MBRL_PRECISION_F16X6",
            "precision_code", "option", "OPTIONS", "AdamTensor", "AdamHparams",

@@ -320,9 +320,27 @@ class CEMPlanner(ModelPlanner):
     with 33 / 22 significant operand bits, see include/mbrl_cem.h). Timing hooks (bench.py):
     rollout_events (per-iteration event pairs around the rollout launch), plan_events (one pair
     recorded on the plan's stream just before and just after the C call that enqueues the plan).
-    Returns the final Gaussian mean (clipped) and its predicted states (ensemble mean)."""
+    Returns the final Gaussian mean (clipped) and its predicted states (ensemble mean).
+
+    Receding horizon (mbrl_cem_plan_rh; the two iCEM ingredients, all off by default -- the defaults plan
+    exactly as above, bit for bit):
+    warm_start (False): honour `initial_trajectory` -- its action rows after dropping the first `shift`
+        (1) and repeating the last to keep `horizon` rows, clipped to the bounds, are the initial mean
+        (mppi_warm_start_rows), so MPCPolicy(..., warm_start=True) plans from the previous plan's tail.
+    warm_std (None): the initial std of a warm-started plan. None: init_std on every row; a float: that
+        value; "keep": the previous plan's sigma shifted like the mean, given as plan_detailed(...,
+        prev_sigma=) (every entry finite and > 0, checked here on the host: the C call cannot).
+    keep_elites (0): Kc, the best rows kept from each iteration into the next one's candidate slots
+        [0, Kc) -- an int, or a float in (0, 1) as a fraction of num_elites (rounded down, at least 1).
+    carry (None): a [Kc, H, a] tensor, the previous plan's result["carry"] shifted (cem_shift_carry), which
+        fills those slots in iteration 0.
+    With keep_elites > 0 plan_detailed also returns carry [Kc, H, a] and carry_returns [Kc] (record=True:
+    kept_hist [I + 1, Kc, H, a]; record=True also returns the rows a warm-started plan began from as
+    init_mu / init_sigma). These kwargs raise NotImplementedError with distributed=True, in
+    plan_batch and with callables the fused path does not recognise."""
     defaults = dict(num_candidates=1000, num_elites=None, num_iterations=5, alpha=0.1, seed=None, init_std=None,
-                    action_bounds=None, distributed=False, return_device=False, precision="f32")
+                    action_bounds=None, distributed=False, return_device=False, precision="f32",
+                    warm_start=False, shift=1, warm_std=None, keep_elites=0, carry=None)
 
     @staticmethod
     def plan(initial_state, model, cost, sample_action, horizon, initial_trajectory=None, **kwargs):
@@ -333,10 +351,11 @@ class CEMPlanner(ModelPlanner):
     @staticmethod
     def plan_batch(initial_states, model, cost, sample_action, horizon, **kwargs):
         """B plans at once, one per row of initial_states [B, s] (see cem_plan_batch)."""
+        _rh_refuse(kwargs, "CEMPlanner.plan_batch")
         return cem_plan_batch(initial_states, model, cost, sample_action, horizon, **kwargs)
 
     _SETTINGS = {}
-    _HOOKS = ("rollout_events", "plan_events")
+    _HOOKS = ("rollout_events", "plan_events", "carry", "prev_sigma")   # per-plan values: not settings
 
     @staticmethod
     def _settings(sample_action, horizon, kwargs):
@@ -378,17 +397,27 @@ class CEMPlanner(ModelPlanner):
 
     @staticmethod
     def plan_detailed(initial_state, model, cost, sample_action, horizon, initial_trajectory=None, **kwargs):
-        """plan() plus diagnostics: dict(states, actions, mu, sigma[, costs, returns, elites per iteration])."""
+        """plan() plus diagnostics: dict(states, actions, mu, sigma[, costs, returns, elites per iteration]
+        [, carry, carry_returns[, kept_hist]])."""
+        if kwargs.get("distributed", False):
+            _rh_refuse(kwargs, "CEMPlanner with distributed=True")   # (before anything needs a device)
         dev = _device(kwargs)
         st = CEMPlanner._settings(sample_action, horizon, kwargs)
+        # (the settings dict does not carry the receding-horizon kwargs: a plan that names none of them
+        # takes the plain path with nothing added to its host turn)
+        rh = _rh_inputs(st, initial_trajectory, kwargs) if any(k in kwargs for k in _RH_KWARGS) else None
         with _on_device(dev):
             mdesc, cdesc, prob = fused.describe_problem(model, cost, dev, st["precision"])
             ws = None
             if st["distributed"] and torch.distributed.is_available() and torch.distributed.is_initialized() \
                     and torch.distributed.get_world_size() > 1:
                 ws = torch.distributed.get_world_size()
+            if rh is not None and (mdesc is None or cdesc is None):
+                _rh_refuse(kwargs, "CEMPlanner with callables the fused path does not recognise")
             if mdesc is not None and cdesc is not None:
-                if ws is None:
+                if rh is not None:
+                    res = _cem_fused_rh(prob, initial_state, st, rh)
+                elif ws is None:
                     res = _cem_fused_single(prob, initial_state, st)
                 else:
                     res = _cem_fused_sharded(prob, initial_state, st, ws)
@@ -403,6 +432,95 @@ class CEMPlanner(ModelPlanner):
             return _finish(res, st["keep"])
 
 
+_RH_KWARGS = ("warm_start", "warm_std", "keep_elites", "carry")
+
+
+def _rh_refuse(kwargs, where):
+    """NotImplementedError naming the first receding-horizon kwarg that is switched on: `where` (sharded
+    and batched plans, the generic path) has no receding-horizon form."""
+    d = CEMPlanner.defaults
+    for k in _RH_KWARGS:
+        v = kwargs.get(k, d[k])
+        if v is not None and v is not False and not (k == "keep_elites" and not isinstance(v, bool) and v == 0):
+            raise NotImplementedError(f"{where}: {k}={v!r} is not implemented (receding-horizon CEM plans are "
+                                      "single-GPU, single-problem, fused-path plans)")
+
+
+def _rh_settings(kwargs, K):
+    """The receding-horizon settings of a plan with K elites: warm_start, shift, warm_std (None, a float > 0
+    or "keep") and Kc, keep_elites resolved to a count in [0, K]."""
+    d = CEMPlanner.defaults
+    g = lambda k: kwargs.get(k, d[k])  # noqa: E731
+    ke = g("keep_elites")
+    if isinstance(ke, bool) or ke is None:
+        raise ValueError(f"keep_elites must be a count or a fraction in (0, 1), got {ke!r}")
+    if isinstance(ke, float) and not ke.is_integer():
+        if not 0.0 < ke < 1.0:
+            raise ValueError(f"a fractional keep_elites must lie in (0, 1), got {ke}")
+        Kc = max(1, int(ke * K))
+    else:
+        Kc = int(ke)
+    if not 0 <= Kc <= K:
+        raise ValueError(f"need 0 <= keep_elites ({Kc}) <= num_elites ({K})")
+    warm_std = g("warm_std")
+    if warm_std is not None and warm_std != "keep":
+        warm_std = float(warm_std)
+        if not (warm_std > 0.0 and np.isfinite(warm_std)):
+            raise ValueError(f"warm_std must be finite and > 0, got {warm_std}")
+    shift = int(g("shift"))
+    if shift < 0:
+        raise ValueError(f"shift must be >= 0, got {shift}")
+    return dict(warm_start=bool(g("warm_start")), shift=shift, warm_std=warm_std, Kc=Kc)
+
+
+def cem_shift_carry(carry, shift, lo=-1.0, hi=1.0):
+    """The kept rows of one plan ([Kc, H, a], its result["carry"]) as the next control step's `carry`: what
+    mppi_warm_start_rows does to the mean, for every kept row -- the first `shift` steps dropped, the last
+    step repeated to keep H, clipped to [lo, hi]. Host only; float32 [Kc, H, a]."""
+    x = carry.detach().cpu().numpy() if isinstance(carry, torch.Tensor) else np.asarray(carry)
+    x = np.asarray(x, dtype=np.float32)
+    if x.ndim != 3:
+        raise ValueError(f"carry must be [Kc, H, a], got shape {x.shape}")
+    H = x.shape[1]
+    if x.shape[0] == 0:
+        return x.copy()
+    return np.stack([mppi_warm_start_rows(row, H, shift, lo, hi) for row in x])
+
+
+def _rh_inputs(st, initial_trajectory, kwargs):
+    """The receding-horizon inputs of one plan as host arrays, dict(mu_rows, sigma_rows, carry) with None for
+    what is absent, and Kc -- or None when nothing is switched on (the plan then takes the plain path untouched)."""
+    rs = _rh_settings(kwargs, st["K"])
+    H, Kc = st["H"], rs["Kc"]
+    carry = kwargs.get("carry")
+    if carry is not None and Kc == 0:
+        raise ValueError("carry given with keep_elites == 0")
+    rows = sig = None
+    if rs["warm_start"] and initial_trajectory is not None:
+        rows = mppi_warm_start_rows(initial_trajectory[1], H, rs["shift"], st["lo"], st["hi"])
+        ws = rs["warm_std"]
+        if ws == "keep":
+            prev = kwargs.get("prev_sigma")
+            if prev is None:
+                raise ValueError('warm_std="keep" needs the previous plan\'s sigma: plan_detailed(..., prev_sigma=)')
+            sig = mppi_warm_start_rows(prev, H, rs["shift"], 0.0, np.inf)
+        elif ws is not None:
+            sig = np.full(rows.shape, ws, np.float32)
+        if sig is not None:
+            if sig.shape != rows.shape:
+                raise ValueError(f"prev_sigma gives {sig.shape} rows, the warm start {rows.shape}")
+            if not (np.isfinite(sig).all() and (sig > 0).all()):   # MBRL_EINVAL of mbrl_cem_plan_rh, made here
+                raise ValueError("initial sigma rows must be finite and > 0")
+    if carry is not None:
+        c = carry.detach().cpu().numpy() if isinstance(carry, torch.Tensor) else carry
+        carry = np.ascontiguousarray(c, dtype=np.float32)
+        if carry.ndim != 3 or carry.shape[:2] != (Kc, H):
+            raise ValueError(f"carry must be [keep_elites={Kc}, horizon={H}, a], got {carry.shape}")
+    if rows is None and carry is None and Kc == 0:
+        return None
+    return dict(mu_rows=rows, sigma_rows=sig, carry=carry, Kc=Kc)
+
+
 def cem_plan_batch(initial_states, model, cost, sample_action, horizon, **kwargs):
     """B independent CEM plans in shared launches (mbrl_cem_plan_batch): one per row of
     initial_states [B, s], e.g. the observations of B parallel environments (parallel.py:20-52
@@ -411,6 +529,7 @@ def cem_plan_batch(initial_states, model, cost, sample_action, horizon, **kwargs
     [b*N, (b+1)*N) of one Philox stream. Returns (states [B, H, s], actions [B, H, a]).
 
     Closures the fused path does not recognise fall back to one CEMPlanner.plan per row."""
+    _rh_refuse(kwargs, "cem_plan_batch")
     dev = _device(kwargs)
     st = CEMPlanner._settings(sample_action, horizon, kwargs)
     B = int(initial_states.shape[0])
@@ -610,6 +729,54 @@ def _cem_fused_single(prob, initial_state, st):
     _mark(pev, 1)
     if rec:
         out.update(costs=cost_hist, returns=ret_hist, elites=elite_hist)
+    return out
+
+
+def _cem_fused_rh(prob, initial_state, st, rh):
+    """One C-ABI call: mbrl_cem_plan_rh (every iteration stream-ordered, no host sync). rh: _rh_inputs."""
+    lib = _lib.load()
+    dev = prob.device
+    md = prob.mdesc
+    N, K, H, I, Kc = st["N"], st["K"], st["H"], st["I"], rh["Kc"]
+    a, s, E = md["a"], md["s"], md["E"]
+    for k in ("mu_rows", "sigma_rows", "carry"):
+        if rh[k] is not None and rh[k].shape[-1] != a:
+            raise ValueError(f"{k} has {rh[k].shape[-1]} action dims, the model {a}")
+    pkey = ("rh", N, H, K, I, Kc, st["alpha"], st["lo"], st["hi"], st["init_std"], int(st["seed"]) & 0xFFFFFFFFFFFFFFFF)
+    _, pref, need = _plan_params(prob, pkey, lambda: _lib.CemRhParams(_cem_params(st, pkey[-1]), Kc, 0),
+                                 lib.mbrl_cem_rh_workspace_bytes)
+    if need == 0:
+        _lib.check(_lib.MBRL_EINVAL, "mbrl_cem_rh_workspace_bytes")
+    ws = _workspace(("cem_rh", str(dev)), need, dev)
+    s0 = initial_state.to(device=dev, dtype=torch.float32).contiguous()
+    rows_d, sig_d, carry_d = [None if rh[k] is None else torch.from_numpy(np.ascontiguousarray(rh[k])).to(dev)
+                              for k in ("mu_rows", "sigma_rows", "carry")]
+    out = _device_outputs(dev, H, s, a)
+    rec = st["record"]
+    cost_hist, ret_hist, elite_hist = _cem_record_buffers(dev, rec, I, E, N, K)
+    carry_out = carry_ret = kept_hist = None
+    if Kc:
+        carry_out = torch.empty((Kc, H, a), dtype=torch.float32, device=dev)
+        carry_ret = torch.empty((Kc,), dtype=torch.float32, device=dev)
+        kept_hist = torch.empty((I + 1, Kc, H, a), dtype=torch.float32, device=dev) if rec else None
+    pev = st["plan_events"]
+    _mark(pev, 0)
+    _lib.check(lib.mbrl_cem_plan_rh(*prob.refs, _lib.ptr(s0), pref, _lib.ptr(rows_d), _lib.ptr(sig_d),
+                                    _lib.ptr(carry_d), *_output_ptrs(out), _lib.ptr(carry_out), _lib.ptr(carry_ret),
+                                    _lib.ptr(cost_hist), _lib.ptr(ret_hist), _lib.ptr(elite_hist),
+                                    _lib.ptr(kept_hist), _events(st, I), _lib.ptr(ws), ws.numel(),
+                                    _lib.stream_handle(dev)), "mbrl_cem_plan_rh")
+    _mark(pev, 1)
+    if rec:
+        out.update(costs=cost_hist, returns=ret_hist, elites=elite_hist)
+        if Kc:
+            out.update(kept_hist=kept_hist)
+        if rows_d is not None:       # the rows the plan started from (already clipped on the host)
+            out.update(init_mu=rows_d)
+        if sig_d is not None:
+            out.update(init_sigma=sig_d)
+    if Kc:
+        out.update(carry=carry_out, carry_returns=carry_ret)
     return out
 
 
