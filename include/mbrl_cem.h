@@ -31,7 +31,8 @@ extern "C" {
 /* v13 also carries the MPPI calls (mbrl_mppi_update, mbrl_mppi_workspace_bytes, mbrl_mppi_plan and
  * mbrl_mppi_params): they were added within v13, purely additively -- no existing entry point, struct
  * or option changed, so the version did not move. The receding-horizon CEM plan (mbrl_cem_rh_params,
- * mbrl_cem_rh_workspace_bytes, mbrl_cem_plan_rh) joined them the same way. */
+ * mbrl_cem_rh_workspace_bytes, mbrl_cem_plan_rh) joined them the same way, and its batched form
+ * (mbrl_cem_rh_batch_workspace_bytes, mbrl_cem_plan_rh_batch) after it. */
 #define MBRL_ABI_VERSION 13
 
 typedef struct ihipStream_t* mbrl_stream_t; /* == hipStream_t */
@@ -465,7 +466,7 @@ int mbrl_mppi_plan(const mbrl_mlp_shape* shape, const void* packed, const mbrl_n
  * Before any launch: MBRL_EINVAL for bad mbrl_cem_params, keep outside [0, K], carry_in with keep == 0,
  * NULL packed / s0 / actions_out / states_out / workspace or a workspace below
  * mbrl_cem_rh_workspace_bytes (which returns 0 for a bad shape or bad params); MBRL_EUNSUPPORTED for
- * N > 32768. Batched and sharded receding-horizon plans do not exist. */
+ * N > 32768. Sharded receding-horizon plans do not exist; B plans at once: mbrl_cem_plan_rh_batch below. */
 typedef struct {
     mbrl_cem_params cem;
     int32_t keep;  /* Kc */
@@ -478,6 +479,43 @@ int mbrl_cem_plan_rh(const mbrl_mlp_shape* shape, const void* packed, const mbrl
                      float* actions_out, float* states_out, float* carry_out, float* carry_returns_out,
                      float* cost_hist, float* returns_hist, int64_t* elite_hist, float* kept_hist,
                      mbrl_event_t* rollout_events, void* workspace, size_t ws_bytes, mbrl_stream_t stream);
+
+/* ---- batched receding-horizon CEM plan (added within ABI v13, additively): B independent mbrl_cem_plan_rh
+ * plans, one per initial state s0[b], in shared launches -- what mbrl_cem_plan_batch is to mbrl_cem_plan, for
+ * parallel environments that each carry their own warm start and kept rows from control step to control step.
+ * Problem b is mbrl_cem_plan_rh's plan on s0[b] with its own rows and carry; the one difference is the Philox
+ * candidate index, b*N + n, as in mbrl_cem_plan_batch. params->cem.N, K and keep are PER problem. Problem 0
+ * of any batch, and all of a B == 1 batch, is mbrl_cem_plan_rh bit for bit (outputs, carry and records).
+ *   s0 [B][s]; init_mu_rows / init_sigma_rows [B][H][a] device or NULL; carry_in [B][Kc][H][a] device or NULL;
+ *   input_flags [B] int32 device or NULL: which of the given inputs apply to problem b -- bit 0 init_mu_rows,
+ *   bit 1 init_sigma_rows, bit 2 carry_in. A clear bit: problem b plans as if that pointer were NULL (it uses
+ *   params->cem.init_mu / init_sigma, has no kept set at iteration 0 -- all N slots drawn -- and its
+ *   kept_hist row 0 is zeros), so one batch mixes problems at their first control step with problems mid-
+ *   episode. NULL flags: every given pointer applies to every problem. A set bit whose pointer is NULL is
+ *   ignored. Positive finite sigma rows remain the caller's check.
+ * Kept slots, the NaN-stays-NaN clip, the two selections, the refit over the elites' rows, the read-back-or-
+ * regenerate rule and the unmoved counter space are mbrl_cem_plan_rh's, per problem.
+ * Outputs: mu, sigma (optional), actions_out [B][H][a]; states_out [B][H][s]; optional carry_out
+ * [B][Kc][H][a], carry_returns_out [B][Kc]; optional records cost_hist [I][E][B*N], returns_hist [I][B][N],
+ * elite_hist [I][B][K] (indices local to the problem), kept_hist [I + 1][B][Kc][H][a].
+ * keep == 0 without rows enqueues exactly mbrl_cem_plan_batch's launches (bit-identical); with rows only the
+ * first launch differs. keep > 0: each iteration is the one rollout over B*N candidates plus the single
+ * plan's five small launches, each over all B problems (no per-problem launch inside the iteration loop; the
+ * first launch also expands s0 to the per-candidate start states); the B final trajectories are one launch
+ * each, as in mbrl_cem_plan_batch.
+ * Before any launch: MBRL_EINVAL for B < 1, bad params, keep outside [0, K], carry_in with keep == 0, NULL
+ * packed / s0 / actions_out / states_out / workspace; MBRL_EUNSUPPORTED for N > 32768, B*N beyond
+ * mbrl_cem_plan_batch's bound, and with keep > 0 a K x a the staged refit cannot hold or B > 65535;
+ * MBRL_EWORKSPACE for a workspace below mbrl_cem_rh_batch_workspace_bytes (which returns 0 for a bad shape,
+ * bad params or B < 1). */
+size_t mbrl_cem_rh_batch_workspace_bytes(const mbrl_mlp_shape* shape, const mbrl_cem_rh_params* params, int32_t B);
+int mbrl_cem_plan_rh_batch(const mbrl_mlp_shape* shape, const void* packed, const mbrl_norm* norm,
+                           const mbrl_cost* cost, const float* s0, int32_t B, const mbrl_cem_rh_params* params,
+                           const float* init_mu_rows, const float* init_sigma_rows, const float* carry_in,
+                           const int32_t* input_flags, float* mu, float* sigma, float* actions_out,
+                           float* states_out, float* carry_out, float* carry_returns_out, float* cost_hist,
+                           float* returns_hist, int64_t* elite_hist, float* kept_hist, void* workspace,
+                           size_t ws_bytes, mbrl_stream_t stream);
 
 /* ---- gradient-descent planner: replaces GradientDescentPlanner's
  * _optimize_trajectory (planners.py:103-137) -- Adam(lr) on the action sequence through the dynamics

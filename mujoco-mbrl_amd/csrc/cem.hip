@@ -573,7 +573,7 @@ __global__ void refit_kernel(const float* __restrict__ aelite, int a, int K, flo
 #pragma clang fp contract(off)
     extern __shared__ float part[];  // [nch][a]
     __shared__ float mean[64];
-    const int t = blockIdx.x;
+    const int t = blockIdx.y * gridDim.x + blockIdx.x;   // row t of problem blockIdx.y: [B][H] rows
     const int nch = (K + ELITE_CHUNK - 1) / ELITE_CHUNK;
     const float* A = aelite + (size_t)t * K * a;
     for (int pass = 0; pass < 2; ++pass) {
@@ -1119,10 +1119,11 @@ int refit_staged_check(int a, int K) {
 }
 
 int refit_staged_impl(const float* aelite, int H, int a, int K, float alpha, const float* mu, const float* sigma,
-                      float* mu_out, float* sigma_out, hipStream_t stream) {
+                      float* mu_out, float* sigma_out, hipStream_t stream, int B) {
     if (int rc = refit_staged_check(a, K)) return rc;
+    if (B < 1 || B > 65535) return fail(MBRL_EINVAL, "refit: B=%d", B);
     const int nch = (K + ELITE_CHUNK - 1) / ELITE_CHUNK;
-    hipLaunchKernelGGL(refit_kernel, dim3(H), dim3(256), (size_t)nch * a * sizeof(float), stream, aelite, a, K, alpha,
+    hipLaunchKernelGGL(refit_kernel, dim3(H, B), dim3(256), (size_t)nch * a * sizeof(float), stream, aelite, a, K, alpha,
                        1.0f - alpha, mu, sigma, mu_out, sigma_out);
     return hip_check(hipGetLastError(), "refit launch");
 }

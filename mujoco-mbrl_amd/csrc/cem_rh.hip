@@ -3,8 +3,11 @@
 // the plan's first launch, the gather of the elites' and the best rows' actions, and the next proposals'
 // scatter and draw -- with their launchers (mbrl_internal.h). The plan loop is in plan.hip.
 //
-// Layouts: proposals `actions` [H][N][a] time-major (the rollout's), kept rows [Kc][H][a] row-contiguous
-// (what a caller carries from plan to plan), the elites' actions [H][K][a] (refit_kernel's). Every kernel
+// Layouts, for B problems planned at once (B = 1: mbrl_cem_plan_rh; B > 1: mbrl_cem_plan_rh_batch): proposals
+// `actions` [H][B N][a] time-major (the rollout's; problem b's candidate n is candidate b N + n, its Philox
+// index), kept rows [B][Kc][H][a] row-contiguous (what a caller carries from plan to plan), the elites'
+// actions [B][H][K][a] (refit_kernel's), mu / sigma [B][H][a], elites [B][K], best [B][Kc], returns [B][N].
+// `flags` ([B] or NULL) say which optional inputs apply to a problem (rh_flags). Every kernel
 // is a grid-stride loop of one thread per (row, t, d >> 2) -- a Philox block's four dimensions -- ordered
 // so that consecutive threads write consecutive addresses of the buffer they fill, with 16-byte loads and
 // stores where a is a multiple of 4 and the buffers are 16-byte aligned (VEC). Plain loads and stores
@@ -65,82 +68,102 @@ __device__ __forceinline__ void store4(float* __restrict__ dst, int g, int a, co
     }
 }
 
+// Which of the optional inputs apply to problem b (bit 0: mu rows, 1: sigma rows, 2: carry_in); no flags:
+// every given pointer applies to every problem.
+__device__ __forceinline__ int rh_flags(const int32_t* __restrict__ flags, int b) { return flags ? flags[b] : 7; }
+
 template <bool VEC>
 __global__ void __launch_bounds__(256) rh_init_kernel(const RhInitArgs A) {
     const size_t gid = blockIdx.x * (size_t)blockDim.x + threadIdx.x, gsz = (size_t)gridDim.x * blockDim.x;
 #pragma unroll
     for (int r = 0; r < 2; ++r)
         for (size_t i = gid; A.zero.ptr[r] && i < A.zero.words[r]; i += gsz) A.zero.ptr[r][i] = 0u;
-    if (A.s0_src)
-        for (size_t i = gid; i < (size_t)A.s; i += gsz) A.s0_dst[i] = A.s0_src[i];
-    const int a = A.a;
+    const int a = A.a, B = A.B, N = A.N;
+    if (A.s0_src) {   // problem b's state to each of its s0_rep rows (a single plan: the one copy)
+        const size_t s = (size_t)A.s, rep = (size_t)A.s0_rep;
+        for (size_t i = gid; i < (size_t)B * rep * s; i += gsz) {
+            const size_t row = i / s;
+            A.s0_dst[i] = A.s0_src[(row / rep) * s + (i - row * s)];
+        }
+    }
     const size_t Ha = (size_t)A.H * a;
     // the initial distribution: what the draws below use, whether or not this thread also stores it
-    auto mu0 = [&](size_t i) { return A.mu_rows ? fminf(fmaxf(A.mu_rows[i], A.lo), A.hi) : A.init_mu; };
-    auto sg0 = [&](size_t i) { return A.sigma_rows ? A.sigma_rows[i] : A.init_sigma; };
-    for (size_t i = gid; i < Ha; i += gsz) {
-        A.mu[i] = mu0(i);
-        A.sigma[i] = sg0(i);
+    // (i: an index into [B][H][a], f: its problem's flags)
+    auto mu0 = [&](size_t i, int f) { return A.mu_rows && (f & 1) ? fminf(fmaxf(A.mu_rows[i], A.lo), A.hi) : A.init_mu; };
+    auto sg0 = [&](size_t i, int f) { return A.sigma_rows && (f & 2) ? A.sigma_rows[i] : A.init_sigma; };
+    for (size_t i = gid; i < (size_t)B * Ha; i += gsz) {
+        const int f = rh_flags(A.flags, (int)(i / Ha));
+        A.mu[i] = mu0(i, f);
+        A.sigma[i] = sg0(i, f);
     }
-    if (A.kept0)
-        for (size_t i = gid; i < (size_t)A.Kc * Ha; i += gsz) A.kept0[i] = A.carry_in ? A.carry_in[i] : 0.f;
+    if (A.kept0) {
+        const size_t per = (size_t)A.Kc * Ha;
+        for (size_t i = gid; i < (size_t)B * per; i += gsz)
+            A.kept0[i] = A.carry_in && (rh_flags(A.flags, (int)(i / per)) & 4) ? A.carry_in[i] : 0.f;
+    }
     if (!A.actions) return;
-    const int G = (a + 3) >> 2, N = A.N;
-    const size_t total = (size_t)A.H * N * G;
+    const int G = (a + 3) >> 2;
+    const size_t BN = (size_t)B * N, total = (size_t)A.H * BN * G;
     for (size_t i = gid; i < total; i += gsz) {
-        const int g = (int)(i % G), n = (int)((i / G) % N), t = (int)(i / G / N);
+        const int g = (int)(i % G), t = (int)(i / G / BN);
+        const size_t c = (i / G) % BN;   // the candidate's Philox index: problem b's candidate n is b N + n
+        const int b = (int)(c / N), n = (int)(c - (size_t)b * N), f = rh_flags(A.flags, b);
         float v[4];
-        if (A.carry_in && n < A.Kc) {
-            kept_load4<VEC>(A.carry_in + ((size_t)n * A.H + t) * a, g, a, A.lo, A.hi, v);
+        if (A.carry_in && (f & 4) && n < A.Kc) {
+            kept_load4<VEC>(A.carry_in + (((size_t)b * A.Kc + n) * A.H + t) * a, g, a, A.lo, A.hi, v);
         } else {
             float z[4];
-            cem_normal4(A.seed, (uint32_t)n, (uint32_t)t, 0u, (uint32_t)g, z);
+            cem_normal4(A.seed, (uint32_t)c, (uint32_t)t, 0u, (uint32_t)g, z);
+            const size_t row = (size_t)b * Ha + (size_t)t * a;
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const int d = 4 * g + j;
-                v[j] = d < a ? cem_action(mu0((size_t)t * a + d), sg0((size_t)t * a + d), z[j], A.lo, A.hi) : 0.f;
+                v[j] = d < a ? cem_action(mu0(row + d, f), sg0(row + d, f), z[j], A.lo, A.hi) : 0.f;
             }
         }
-        store4<VEC>(A.actions + ((size_t)t * N + n) * a, g, a, v);
+        store4<VEC>(A.actions + ((size_t)t * BN + c) * a, g, a, v);
     }
 }
 
 template <bool VEC>
 __global__ void __launch_bounds__(256) rh_gather_kernel(const RhGatherArgs A) {
     const size_t gid = blockIdx.x * (size_t)blockDim.x + threadIdx.x, gsz = (size_t)gridDim.x * blockDim.x;
-    const int a = A.a, H = A.H, K = A.K, Kc = A.Kc, G = (a + 3) >> 2;
+    const int a = A.a, H = A.H, K = A.K, Kc = A.Kc, N = A.N, B = A.B, G = (a + 3) >> 2;
     if (A.best_returns)
-        for (size_t i = gid; i < (size_t)Kc; i += gsz) {
-            const int64_t b = A.best[i];   // (a candidate index; anything else reads nothing)
-            A.best_returns[i] = (uint64_t)b < (uint64_t)A.N ? A.returns[b] : __uint_as_float(0x7FC00000u);
+        for (size_t i = gid; i < (size_t)B * Kc; i += gsz) {
+            const int64_t n = A.best[i];   // (a candidate index; anything else reads nothing)
+            A.best_returns[i] = (uint64_t)n < (uint64_t)N ? A.returns[(i / Kc) * N + n] : __uint_as_float(0x7FC00000u);
         }
-    // threads [0, H K G): elite e's step t in (t, e, g) order, aelite's; then [0, Kc H G): best row j's step
-    // t in (j, t, g) order, the kept rows'
-    const size_t n_el = (size_t)H * K * G, total = n_el + (size_t)Kc * H * G;
+    // threads [0, B H K G): problem b's elite e's step t in (b, t, e, g) order, aelite's; then [0, B Kc H G):
+    // best row j's step t in (b, j, t, g) order, the kept rows'
+    const size_t n_el = (size_t)B * H * K * G, total = n_el + (size_t)B * Kc * H * G;
     for (size_t i = gid; i < total; i += gsz) {
-        int g, t, n;
+        int g, t, n, b;
         float *dst, *dst2 = nullptr;
         if (i < n_el) {
             g = (int)(i % G);
             const int e = (int)((i / G) % K);
-            t = (int)(i / G / K);
-            n = (int)A.elites[e];
-            dst = A.aelite + ((size_t)t * K + e) * a;
+            t = (int)((i / G / K) % H);
+            b = (int)(i / G / K / H);
+            n = (int)A.elites[(size_t)b * K + e];
+            dst = A.aelite + (((size_t)b * H + t) * K + e) * a;
         } else {
             const size_t q = i - n_el;
             g = (int)(q % G);
             t = (int)((q / G) % H);
-            const int j = (int)(q / G / H);
-            n = (int)A.best[j];
-            dst = A.kept_next + ((size_t)j * H + t) * a;
-            if (A.kept_copy) dst2 = A.kept_copy + ((size_t)j * H + t) * a;
+            const int j = (int)((q / G / H) % Kc);
+            b = (int)(q / G / H / Kc);
+            n = (int)A.best[(size_t)b * Kc + j];
+            const size_t o = (((size_t)b * Kc + j) * H + t) * a;
+            dst = A.kept_next + o;
+            if (A.kept_copy) dst2 = A.kept_copy + o;
         }
         float v[4];
-        if (A.from_kept && (unsigned)n < (unsigned)Kc)
-            kept_load4<VEC>(A.kept_cur + ((size_t)n * H + t) * a, g, a, A.lo, A.hi, v);
+        if (A.from_kept && (rh_flags(A.flags, b) & 4) && (unsigned)n < (unsigned)Kc)
+            kept_load4<VEC>(A.kept_cur + (((size_t)b * Kc + n) * H + t) * a, g, a, A.lo, A.hi, v);
         else
-            draw4(A.seed, (uint32_t)n, (uint32_t)t, (uint32_t)A.iteration, g, a, A.mu + (size_t)t * a,
-                  A.sigma + (size_t)t * a, A.lo, A.hi, v);
+            draw4(A.seed, (uint32_t)b * (uint32_t)N + (uint32_t)n, (uint32_t)t, (uint32_t)A.iteration, g, a,
+                  A.mu + ((size_t)b * H + t) * a, A.sigma + ((size_t)b * H + t) * a, A.lo, A.hi, v);
         store4<VEC>(dst, g, a, v);
         if (dst2) store4<VEC>(dst2, g, a, v);
     }
@@ -149,25 +172,27 @@ __global__ void __launch_bounds__(256) rh_gather_kernel(const RhGatherArgs A) {
 template <bool VEC>
 __global__ void __launch_bounds__(256) rh_draw_kernel(const RhDrawArgs A) {
     const size_t gid = blockIdx.x * (size_t)blockDim.x + threadIdx.x, gsz = (size_t)gridDim.x * blockDim.x;
-    const int a = A.a, H = A.H, N = A.N, G = (a + 3) >> 2;
+    const int a = A.a, H = A.H, N = A.N, B = A.B, G = (a + 3) >> 2;
     if (A.fin_actions)
-        for (size_t i = gid; i < (size_t)H * a; i += gsz) {
+        for (size_t i = gid; i < (size_t)B * H * a; i += gsz) {
             const float m = A.mu[i];
             if (A.fin_mu) A.fin_mu[i] = m;
             if (A.fin_sigma) A.fin_sigma[i] = A.sigma[i];
             A.fin_actions[i] = fminf(fmaxf(m, A.lo), A.hi);
         }
     if (!A.actions) return;
-    const size_t total = (size_t)H * N * G;
+    const size_t BN = (size_t)B * N, total = (size_t)H * BN * G;
     for (size_t i = gid; i < total; i += gsz) {
-        const int g = (int)(i % G), n = (int)((i / G) % N), t = (int)(i / G / N);
+        const int g = (int)(i % G), t = (int)(i / G / BN);
+        const size_t c = (i / G) % BN;
+        const int b = (int)(c / N), n = (int)(c - (size_t)b * N);
         float v[4];
         if (n < A.Kc)
-            kept_load4<VEC>(A.kept + ((size_t)n * H + t) * a, g, a, A.lo, A.hi, v);
+            kept_load4<VEC>(A.kept + (((size_t)b * A.Kc + n) * H + t) * a, g, a, A.lo, A.hi, v);
         else
-            draw4(A.seed, (uint32_t)n, (uint32_t)t, (uint32_t)A.iteration, g, a, A.mu + (size_t)t * a,
-                  A.sigma + (size_t)t * a, A.lo, A.hi, v);
-        store4<VEC>(A.actions + ((size_t)t * N + n) * a, g, a, v);
+            draw4(A.seed, (uint32_t)c, (uint32_t)t, (uint32_t)A.iteration, g, a, A.mu + ((size_t)b * H + t) * a,
+                  A.sigma + ((size_t)b * H + t) * a, A.lo, A.hi, v);
+        store4<VEC>(A.actions + ((size_t)t * BN + c) * a, g, a, v);
     }
 }
 
@@ -185,7 +210,7 @@ static bool aligned16(std::initializer_list<const void*> ps) {
 
 hipError_t launch_rh_init(const RhInitArgs& A, hipStream_t stream) {
     const size_t G = (size_t)(A.a + 3) / 4;
-    const size_t threads = A.actions ? (size_t)A.H * A.N * G : (size_t)A.H * A.a;
+    const size_t threads = (size_t)A.B * (A.actions ? (size_t)A.H * A.N * G : (size_t)A.H * A.a);
     const bool vec = (A.a & 3) == 0 && aligned16({A.carry_in, A.actions});
     if (vec) hipLaunchKernelGGL(rh_init_kernel<true>, rh_grid(threads), dim3(256), 0, stream, A);
     else hipLaunchKernelGGL(rh_init_kernel<false>, rh_grid(threads), dim3(256), 0, stream, A);
@@ -195,7 +220,7 @@ hipError_t launch_rh_init(const RhInitArgs& A, hipStream_t stream) {
 hipError_t launch_rh_gather(const RhGatherArgs& A, hipStream_t stream) {
     const size_t G = (size_t)(A.a + 3) / 4;
     const bool vec = (A.a & 3) == 0 && aligned16({A.kept_cur, A.aelite, A.kept_next, A.kept_copy});
-    const dim3 grid = rh_grid((size_t)A.H * ((size_t)A.K + A.Kc) * G);
+    const dim3 grid = rh_grid((size_t)A.B * A.H * ((size_t)A.K + A.Kc) * G);
     if (vec) hipLaunchKernelGGL(rh_gather_kernel<true>, grid, dim3(256), 0, stream, A);
     else hipLaunchKernelGGL(rh_gather_kernel<false>, grid, dim3(256), 0, stream, A);
     return hipGetLastError();
@@ -203,7 +228,7 @@ hipError_t launch_rh_gather(const RhGatherArgs& A, hipStream_t stream) {
 
 hipError_t launch_rh_draw(const RhDrawArgs& A, hipStream_t stream) {
     const size_t G = (size_t)(A.a + 3) / 4;
-    const size_t threads = A.actions ? (size_t)A.H * A.N * G : (size_t)A.H * A.a;
+    const size_t threads = (size_t)A.B * (A.actions ? (size_t)A.H * A.N * G : (size_t)A.H * A.a);
     const bool vec = (A.a & 3) == 0 && aligned16({A.kept, A.actions});
     if (vec) hipLaunchKernelGGL(rh_draw_kernel<true>, rh_grid(threads), dim3(256), 0, stream, A);
     else hipLaunchKernelGGL(rh_draw_kernel<false>, rh_grid(threads), dim3(256), 0, stream, A);

@@ -379,22 +379,30 @@ struct InitZero {
 void launch_cem_init(dim3 grid, hipStream_t stream, uint64_t seed, float init_mu, float init_sigma, float lo, float hi,
                      int H, int a, int N, float* mu, float* sigma, float* actions, const float* s0_src, int s,
                      float* s0_dst, int draw_off, const InitZero& zero, const float* mu_rows);
-// refit_kernel alone over elite actions already staged as aelite [H][K][a] (the second launch of
-// refit_impl's staged path): the receding-horizon plan gathers them itself (cem_rh.hip).
+// refit_kernel alone over elite actions already staged as aelite [B][H][K][a] (the second launch of
+// refit_impl's staged path; grid (H, B), mu / sigma [B][H][a]): the receding-horizon plans gather them
+// themselves (cem_rh.hip).
 int refit_staged_check(int a, int K);
 int refit_staged_impl(const float* aelite, int H, int a, int K, float alpha, const float* mu, const float* sigma,
-                      float* mu_out, float* sigma_out, hipStream_t stream);
+                      float* mu_out, float* sigma_out, hipStream_t stream, int B = 1);
 
-// ---- receding-horizon CEM (cem_rh.hip; include/mbrl_cem.h mbrl_cem_plan_rh). kept rows are [Kc][H][a].
+// ---- receding-horizon CEM (cem_rh.hip; include/mbrl_cem.h mbrl_cem_plan_rh, mbrl_cem_plan_rh_batch). Every
+// struct describes B problems (B = 1: the single plan): proposals [H][B N][a], mu / sigma and the rows
+// [B][H][a], kept rows [B][Kc][H][a], elites [B][K], best [B][Kc], returns [B][N], aelite [B][H][K][a].
+// flags: [B] device words or NULL -- bit 0 / 1 / 2 set: mu_rows / sigma_rows / carry_in apply to that problem
+// (NULL: every given pointer applies to every problem).
 // The plan's first launch where cem_init_kernel does not apply (sigma rows, or kept rows): the hand-off
 // words zeroed, the s0 copy, the distribution rows (mu_rows / sigma_rows, each or NULL), kept_0 (carry_in
 // or zeros, when kept0 is given) and, with `actions`, iteration 0's proposals: slots [0, Kc) from
-// carry_in where given, every other candidate drawn as cem_init_kernel draws it.
+// carry_in where given, every other candidate drawn as cem_init_kernel draws it. The s0 copy writes each
+// problem's state s0_rep times: s0_src [B][s] -> s0_dst [B s0_rep][s] (1: a copy; N: the batched rollout's
+// per-candidate start states).
 struct RhInitArgs {
     uint64_t seed;
     float init_mu, init_sigma, lo, hi;
-    int H, a, N, Kc, s;
+    int H, a, N, Kc, s, B, s0_rep;
     const float *mu_rows, *sigma_rows, *carry_in;
+    const int32_t* flags;
     float *mu, *sigma, *actions, *kept0;
     const float* s0_src;
     float* s0_dst;
@@ -403,12 +411,14 @@ struct RhInitArgs {
 hipError_t launch_rh_init(const RhInitArgs& A, hipStream_t stream);
 // After iteration `iteration`'s two selections: the elites' action rows into aelite [H][K][a] (refit_kernel's
 // layout) and the best rows into kept_next [Kc][H][a] (and kept_copy, best_returns where given). A row of
-// candidate n < Kc is read from kept_cur when from_kept, else regenerated from the counter RNG.
+// candidate n < Kc is read from kept_cur when from_kept (and, with flags, the problem's bit 2), else
+// regenerated from the counter RNG. elites / best hold indices local to their problem.
 struct RhGatherArgs {
     uint64_t seed;
-    int iteration, N, H, a, K, Kc, from_kept;
+    int iteration, N, H, a, K, Kc, from_kept, B;
     float lo, hi;
     const float *mu, *sigma, *kept_cur, *returns;
+    const int32_t* flags;
     const int64_t *elites, *best;
     float *aelite, *kept_next, *kept_copy, *best_returns;
 };
@@ -418,7 +428,7 @@ hipError_t launch_rh_gather(const RhGatherArgs& A, hipStream_t stream);
 // fin_actions is given.
 struct RhDrawArgs {
     uint64_t seed;
-    int iteration, H, a, N, Kc;
+    int iteration, H, a, N, Kc, B;
     float lo, hi;
     const float *mu, *sigma, *kept;
     float *actions, *fin_mu, *fin_sigma, *fin_actions;

@@ -1,7 +1,7 @@
 // The plans: host dispatch of the rollout and trajectory kernels (rollout_impl, traj_impl), the plan
 // workspaces, the helpers the plan loops share (mbrl_plan.h) and the single-GPU plan entries
 // (include/mbrl_cem.h): rollout cost, trajectory, CEM plan, receding-horizon CEM plan, MPPI plan, batched
-// CEM plan.
+// CEM plan, batched receding-horizon CEM plan.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -509,7 +509,7 @@ static int cem_plan_run(const Geometry& g, const void* packed, const mbrl_norm* 
     if (sigma_rows) {   // (cem_init_kernel has no sigma rows: rh_init_kernel, the same values)
         RhInitArgs A{};
         A.seed = p->seed; A.init_mu = p->init_mu; A.init_sigma = p->init_sigma; A.lo = p->lo; A.hi = p->hi;
-        A.H = p->H; A.a = g.a; A.N = p->N; A.s = g.s; A.mu_rows = mu_rows; A.sigma_rows = sigma_rows;
+        A.H = p->H; A.a = g.a; A.N = p->N; A.s = g.s; A.B = 1; A.s0_rep = 1; A.mu_rows = mu_rows; A.sigma_rows = sigma_rows;
         A.mu = w.mu[0]; A.sigma = w.sigma[0]; A.actions = f.fuse_draw ? w.actions : nullptr;
         A.s0_src = s0_in; A.s0_dst = w.s0; A.zero = z;
         if ((rc = hip_check(launch_rh_init(A, stream), "init launch"))) return rc;
@@ -632,7 +632,7 @@ static int cem_plan_rh_kept(const Geometry& g, const void* packed, const mbrl_no
     {
         RhInitArgs A{};
         A.seed = p->seed; A.init_mu = p->init_mu; A.init_sigma = p->init_sigma; A.lo = p->lo; A.hi = p->hi;
-        A.H = p->H; A.a = g.a; A.N = p->N; A.Kc = Kc; A.s = g.s;
+        A.H = p->H; A.a = g.a; A.N = p->N; A.Kc = Kc; A.s = g.s; A.B = 1; A.s0_rep = 1;
         A.mu_rows = mu_rows; A.sigma_rows = sigma_rows; A.carry_in = carry_in;
         A.mu = w.mu[0]; A.sigma = w.sigma[0]; A.actions = w.actions; A.kept0 = kept_hist;
         A.s0_src = s0_in; A.s0_dst = w.s0; A.zero = z;
@@ -656,7 +656,7 @@ static int cem_plan_rh_kept(const Geometry& g, const void* packed, const mbrl_no
         if ((rc = select_impl(costs, g.E, p->N, Kc, MBRL_NAN_LAST, rw.best, nullptr, w.keys, keys_bytes, stream)))
             return rc;
         RhGatherArgs G{};
-        G.seed = p->seed; G.iteration = it; G.N = p->N; G.H = p->H; G.a = g.a; G.K = p->K; G.Kc = Kc;
+        G.seed = p->seed; G.iteration = it; G.N = p->N; G.H = p->H; G.a = g.a; G.K = p->K; G.Kc = Kc; G.B = 1;
         G.from_kept = it > 0 || carry_in; G.lo = p->lo; G.hi = p->hi;
         G.mu = w.mu[cur]; G.sigma = w.sigma[cur]; G.kept_cur = it == 0 ? carry_in : kept_at(it); G.returns = rets;
         G.elites = elites; G.best = rw.best; G.aelite = w.aelite; G.kept_next = kept_at(it + 1);
@@ -666,7 +666,8 @@ static int cem_plan_rh_kept(const Geometry& g, const void* packed, const mbrl_no
                                w.sigma[cur ^ 1], stream);
         if (rc) return rc;
         RhDrawArgs D{};
-        D.seed = p->seed; D.iteration = it + 1; D.H = p->H; D.a = g.a; D.N = p->N; D.Kc = Kc; D.lo = p->lo; D.hi = p->hi;
+        D.seed = p->seed; D.iteration = it + 1; D.H = p->H; D.a = g.a; D.N = p->N; D.Kc = Kc; D.B = 1;
+        D.lo = p->lo; D.hi = p->hi;
         D.mu = w.mu[cur ^ 1]; D.sigma = w.sigma[cur ^ 1]; D.kept = kept_at(it + 1);
         D.actions = last ? nullptr : w.actions;
         D.fin_mu = last ? mu : nullptr; D.fin_sigma = last ? sigma : nullptr; D.fin_actions = last ? actions_out : nullptr;
@@ -843,6 +844,88 @@ size_t mbrl_cem_plan_batch_workspace_bytes(const mbrl_mlp_shape* shape, const mb
     return batch_ws(g, params, B, nullptr).bytes;
 }
 
+// B * N, the candidates of one batched rollout, as mbrl_cem_plan_batch bounds it.
+static int batch_size_check(int B, const mbrl_cem_params* p) {
+    if ((int64_t)B * p->N > INT32_MAX / 2) return fail(MBRL_EUNSUPPORTED, "B*N too large");
+    return MBRL_OK;
+}
+
+// Each problem's final mean rolled out: its states (the cooperative trajectory kernel), one launch each.
+static int batch_final_trajectories(const Geometry& g, const void* packed, const mbrl_norm* norm, const float* s0, int B,
+                                    int H, const float* actions_out, float* states_out, const BatchWs& w,
+                                    hipStream_t stream) {
+    const size_t Hs = (size_t)H * g.s;
+    for (int b = 0; b < B; ++b) {
+        int rc = final_trajectory(g, packed, norm, s0 + (size_t)b * g.s, actions_out + (size_t)b * H * g.a, H,
+                                  states_out + b * Hs, w.states, w.traj, stream, 0);
+        if (rc) return rc;
+    }
+    return hip_check(hipGetLastError(), "batched plan launch");
+}
+
+// mbrl_cem_plan_batch's launches, the arguments checked and the workspace carved: shared with the batched
+// receding-horizon plan that keeps no rows (mbrl_cem_plan_rh_batch, keep == 0), which differs in the first
+// launch alone where rows are given -- the initial distribution's rows (mu_rows / sigma_rows [B][H][a],
+// each or NULL; flags: which apply to a problem) -- and may record (cost_hist [I][E][B N], returns_hist
+// [I][B][N], elite_hist [I][B][K]).
+static int cem_batch_run(const Geometry& g, const void* packed, const mbrl_norm* norm, const mbrl_cost* cost,
+                         const float* s0, int B, const mbrl_cem_params* p, const float* mu_rows,
+                         const float* sigma_rows, const int32_t* flags, float* mu, float* sigma, float* actions_out,
+                         float* states_out, float* cost_hist, float* returns_hist, int64_t* elite_hist,
+                         const BatchWs& w, hipStream_t stream) {
+    int rc;
+    const int BN = B * p->N, BHa = B * p->H * g.a;
+    // as mbrl_cem_plan: one fused update launch per iteration where it fits (grid (H, B))
+    const FusePlan f = fuse_plan(p->N, p->N, p->K, g.a);
+    if (mu_rows || sigma_rows) {   // (cem_init_kernel has no per-problem rows: rh_init_kernel, the same values)
+        RhInitArgs A{};
+        A.seed = p->seed; A.init_mu = p->init_mu; A.init_sigma = p->init_sigma; A.lo = p->lo; A.hi = p->hi;
+        A.H = p->H; A.a = g.a; A.N = p->N; A.s = g.s; A.B = B; A.mu_rows = mu_rows; A.sigma_rows = sigma_rows;
+        A.flags = flags; A.mu = w.mu[0]; A.sigma = w.sigma[0]; A.actions = f.fuse_draw ? w.actions : nullptr;
+        if ((rc = hip_check(launch_rh_init(A, stream), "init launch"))) return rc;
+    } else if (f.fuse_draw) {
+        launch_cem_init(dim3(p->H * draw_slices(p->H, B, p->N, g.a), B), stream, p->seed, p->init_mu, p->init_sigma, p->lo,
+                        p->hi, p->H, g.a, p->N, w.mu[0], w.sigma[0], w.actions, nullptr, 0, nullptr, 0, InitZero{}, nullptr);
+    } else {
+        hipLaunchKernelGGL(fill2_kernel, dim3((BHa + 255) / 256), dim3(256), 0, stream, w.mu[0], p->init_mu,
+                           w.sigma[0], p->init_sigma, BHa);
+    }
+    hipLaunchKernelGGL(expand_rows_kernel, dim3(256), dim3(256), 0, stream, s0, B, p->N, g.s, w.s0x);
+    int cur = 0;
+    for (int it = 0; it < p->iterations; ++it) {
+        const mbrl_sampler sp = make_sampler(p, it, w.mu[cur], w.sigma[cur]);
+        float* costs = cost_hist ? cost_hist + (size_t)it * g.E * BN : w.costs;
+        int64_t* elites = elite_hist ? elite_hist + (size_t)it * B * p->K : w.elites;
+        float* rets = returns_hist ? returns_hist + (size_t)it * BN : nullptr;
+        // problem b's candidate n is global candidate b*N + n (its Philox counter)
+        if (!f.fuse_draw) {
+            rc = sample_impl(&sp, p->H, g.a, BN, 0, w.actions, stream, p->N);
+            if (rc) return rc;
+        }
+        rc = rollout_impl(g, packed, norm, cost, w.s0x, 1, w.actions, nullptr, BN, p->H, 0, costs, nullptr, nullptr,
+                          stream);
+        if (rc) return rc;
+        if (f.fuse) {
+            UpdateArgs U = make_update_args(g, p, it, costs, w.mu[cur], w.sigma[cur], w.mu[cur ^ 1], w.sigma[cur ^ 1],
+                                            mu, sigma, actions_out, f.fuse_draw ? w.actions : nullptr);
+            U.member_stride = BN;
+            if (elite_hist) U.elite_out = elites;
+            U.returns_out = rets;
+            rc = update_impl(U, B, stream);
+        } else {
+            const bool last = it + 1 == p->iterations;
+            rc = select_impl(costs, g.E, p->N, p->K, MBRL_NAN_LAST, elites, rets, w.keys, align256((size_t)BN * 4),
+                             stream, B);
+            if (rc) return rc;
+            rc = refit_impl(&sp, p->H, g.a, elites, p->K, p->alpha, nullptr, w.mu[cur ^ 1], w.sigma[cur ^ 1], stream,
+                            last ? mu : nullptr, last ? sigma : nullptr, last ? actions_out : nullptr, B, p->N);
+        }
+        if (rc) return rc;
+        cur ^= 1;
+    }
+    return batch_final_trajectories(g, packed, norm, s0, B, p->H, actions_out, states_out, w, stream);
+}
+
 int mbrl_cem_plan_batch(const mbrl_mlp_shape* shape, const void* packed, const mbrl_norm* norm, const mbrl_cost* cost,
                         const float* s0, int32_t B, const mbrl_cem_params* p, float* mu, float* sigma,
                         float* actions_out, float* states_out, void* workspace, size_t ws_bytes,
@@ -853,54 +936,135 @@ int mbrl_cem_plan_batch(const mbrl_mlp_shape* shape, const void* packed, const m
     if (rc) return rc;
     if (!p || B < 1) return fail(MBRL_EINVAL, "params NULL or B=%d", B);
     if ((rc = cem_params_check(p))) return rc;
-    if ((int64_t)B * p->N > INT32_MAX / 2) return fail(MBRL_EUNSUPPORTED, "B*N too large");
+    if ((rc = batch_size_check(B, p))) return rc;
     if (!s0 || !actions_out || !states_out || !workspace) return fail(MBRL_EINVAL, "s0/actions_out/states_out/workspace NULL");
     BatchWs w = batch_ws(g, p, B, workspace);
     if (ws_bytes < w.bytes) return fail(MBRL_EWORKSPACE, "workspace %zu < %zu", ws_bytes, w.bytes);
-    const int BN = B * p->N, BHa = B * p->H * g.a;
-    // as mbrl_cem_plan: one fused update launch per iteration where it fits (grid (H, B))
-    const FusePlan f = fuse_plan(p->N, p->N, p->K, g.a);
-    if (f.fuse_draw)
-        launch_cem_init(dim3(p->H * draw_slices(p->H, B, p->N, g.a), B), stream, p->seed, p->init_mu, p->init_sigma, p->lo,
-                        p->hi, p->H, g.a, p->N, w.mu[0], w.sigma[0], w.actions, nullptr, 0, nullptr, 0, InitZero{}, nullptr);
-    else
-        hipLaunchKernelGGL(fill2_kernel, dim3((BHa + 255) / 256), dim3(256), 0, stream, w.mu[0], p->init_mu,
-                           w.sigma[0], p->init_sigma, BHa);
-    hipLaunchKernelGGL(expand_rows_kernel, dim3(256), dim3(256), 0, stream, s0, B, p->N, g.s, w.s0x);
+    return cem_batch_run(g, packed, norm, cost, s0, B, p, nullptr, nullptr, nullptr, mu, sigma, actions_out, states_out,
+                         nullptr, nullptr, nullptr, w, stream);
+}
+
+// ---- batched receding-horizon CEM (include/mbrl_cem.h mbrl_cem_plan_rh_batch): mbrl_cem_plan_batch's
+// workspace first, then what kept rows need for B problems -- the staged elites' actions [B][H][K][a], the
+// two kept sets [B][Kc][H][a], the best indices [B][Kc] and the returns [B][N].
+struct RhBatchWs {
+    BatchWs plan;
+    float *aelite, *kept[2], *rets;
+    int64_t* best;
+    size_t bytes;
+};
+
+static RhBatchWs rh_batch_ws(const Geometry& g, const mbrl_cem_rh_params* rp, int B, void* base) {
+    RhBatchWs w{};
+    const mbrl_cem_params* p = &rp->cem;
+    w.plan = batch_ws(g, p, B, base);
+    WsCursor c(base);
+    c.off = w.plan.bytes;
+    const size_t kb = (size_t)B * rp->keep * p->H * g.a * 4;
+    w.aelite = c.take<float>(rp->keep ? (size_t)B * p->H * p->K * g.a * 4 : 0);
+    w.kept[0] = c.take<float>(kb); w.kept[1] = c.take<float>(kb);
+    w.best = c.take<int64_t>((size_t)B * rp->keep * 8);
+    w.rets = c.take<float>(rp->keep ? (size_t)B * p->N * 4 : 0);
+    w.bytes = c.off;
+    return w;
+}
+
+size_t mbrl_cem_rh_batch_workspace_bytes(const mbrl_mlp_shape* shape, const mbrl_cem_rh_params* params, int32_t B) {
+    Geometry g;
+    if (shape_geometry(shape, &g) != MBRL_OK || rh_params_check(params) != MBRL_OK || B < 1) return 0;
+    return rh_batch_ws(g, params, B, nullptr).bytes;
+}
+
+// keep > 0, B problems: cem_plan_rh_kept's launches with a problem dimension -- per iteration the one rollout
+// of the B N proposals, then the same five small launches, each over all B problems (segmented selections,
+// grid (H, B) refit); the first launch also expands s0 to the rollout's per-candidate start states.
+// Iteration 0 honours the problems' input flags; from iteration 1 on every problem has a kept set.
+static int cem_plan_rh_batch_kept(const Geometry& g, const void* packed, const mbrl_norm* norm, const mbrl_cost* cost,
+                                  const float* s0, int B, const mbrl_cem_rh_params* rp, const float* mu_rows,
+                                  const float* sigma_rows, const float* carry_in, const int32_t* flags, float* mu,
+                                  float* sigma, float* actions_out, float* states_out, float* carry_out,
+                                  float* carry_returns_out, float* cost_hist, float* returns_hist, int64_t* elite_hist,
+                                  float* kept_hist, const RhBatchWs& rw, hipStream_t stream) {
+    const mbrl_cem_params* p = &rp->cem;
+    const BatchWs& w = rw.plan;
+    const int Kc = rp->keep, BN = B * p->N;
+    const size_t kept_floats = (size_t)B * Kc * p->H * g.a;
+    auto kept_at = [&](int i) { return kept_hist ? kept_hist + (size_t)i * kept_floats : rw.kept[i & 1]; };
+    int rc;
+    {
+        RhInitArgs A{};
+        A.seed = p->seed; A.init_mu = p->init_mu; A.init_sigma = p->init_sigma; A.lo = p->lo; A.hi = p->hi;
+        A.H = p->H; A.a = g.a; A.N = p->N; A.Kc = Kc; A.s = g.s; A.B = B; A.s0_rep = p->N;
+        A.mu_rows = mu_rows; A.sigma_rows = sigma_rows; A.carry_in = carry_in; A.flags = flags;
+        A.mu = w.mu[0]; A.sigma = w.sigma[0]; A.actions = w.actions; A.kept0 = kept_hist;
+        A.s0_src = s0; A.s0_dst = w.s0x;
+        if ((rc = hip_check(launch_rh_init(A, stream), "init launch"))) return rc;
+    }
+    const size_t keys_bytes = align256((size_t)BN * 4);
     int cur = 0;
     for (int it = 0; it < p->iterations; ++it) {
-        const mbrl_sampler sp = make_sampler(p, it, w.mu[cur], w.sigma[cur]);
-        // problem b's candidate n is global candidate b*N + n (its Philox counter)
-        if (!f.fuse_draw) {
-            rc = sample_impl(&sp, p->H, g.a, BN, 0, w.actions, stream, p->N);
-            if (rc) return rc;
-        }
-        rc = rollout_impl(g, packed, norm, cost, w.s0x, 1, w.actions, nullptr, BN, p->H, 0, w.costs, nullptr, nullptr,
+        const bool last = it + 1 == p->iterations;
+        float* costs = cost_hist ? cost_hist + (size_t)it * g.E * BN : w.costs;
+        int64_t* elites = elite_hist ? elite_hist + (size_t)it * B * p->K : w.elites;
+        float* rets = returns_hist ? returns_hist + (size_t)it * BN : rw.rets;
+        rc = rollout_impl(g, packed, norm, cost, w.s0x, 1, w.actions, nullptr, BN, p->H, 0, costs, nullptr, nullptr,
                           stream);
         if (rc) return rc;
-        if (f.fuse) {
-            UpdateArgs U = make_update_args(g, p, it, w.costs, w.mu[cur], w.sigma[cur], w.mu[cur ^ 1], w.sigma[cur ^ 1],
-                                            mu, sigma, actions_out, f.fuse_draw ? w.actions : nullptr);
-            U.member_stride = BN;
-            rc = update_impl(U, B, stream);
-        } else {
-            const bool last = it + 1 == p->iterations;
-            rc = select_impl(w.costs, g.E, p->N, p->K, MBRL_NAN_LAST, w.elites, nullptr, w.keys,
-                             align256((size_t)BN * 4), stream, B);
-            if (rc) return rc;
-            rc = refit_impl(&sp, p->H, g.a, w.elites, p->K, p->alpha, nullptr, w.mu[cur ^ 1], w.sigma[cur ^ 1], stream,
-                            last ? mu : nullptr, last ? sigma : nullptr, last ? actions_out : nullptr, B, p->N);
-        }
+        if ((rc = select_impl(costs, g.E, p->N, p->K, MBRL_NAN_LAST, elites, rets, w.keys, keys_bytes, stream, B)))
+            return rc;
+        if ((rc = select_impl(costs, g.E, p->N, Kc, MBRL_NAN_LAST, rw.best, nullptr, w.keys, keys_bytes, stream, B)))
+            return rc;
+        RhGatherArgs G{};
+        G.seed = p->seed; G.iteration = it; G.N = p->N; G.H = p->H; G.a = g.a; G.K = p->K; G.Kc = Kc; G.B = B;
+        G.from_kept = it > 0 || carry_in; G.flags = it == 0 ? flags : nullptr; G.lo = p->lo; G.hi = p->hi;
+        G.mu = w.mu[cur]; G.sigma = w.sigma[cur]; G.kept_cur = it == 0 ? carry_in : kept_at(it); G.returns = rets;
+        G.elites = elites; G.best = rw.best; G.aelite = rw.aelite; G.kept_next = kept_at(it + 1);
+        G.kept_copy = last ? carry_out : nullptr; G.best_returns = last ? carry_returns_out : nullptr;
+        if ((rc = hip_check(launch_rh_gather(G, stream), "gather launch"))) return rc;
+        rc = refit_staged_impl(rw.aelite, p->H, g.a, p->K, p->alpha, w.mu[cur], w.sigma[cur], w.mu[cur ^ 1],
+                               w.sigma[cur ^ 1], stream, B);
         if (rc) return rc;
+        RhDrawArgs D{};
+        D.seed = p->seed; D.iteration = it + 1; D.H = p->H; D.a = g.a; D.N = p->N; D.Kc = Kc; D.B = B;
+        D.lo = p->lo; D.hi = p->hi;
+        D.mu = w.mu[cur ^ 1]; D.sigma = w.sigma[cur ^ 1]; D.kept = kept_at(it + 1);
+        D.actions = last ? nullptr : w.actions;
+        D.fin_mu = last ? mu : nullptr; D.fin_sigma = last ? sigma : nullptr; D.fin_actions = last ? actions_out : nullptr;
+        if ((rc = hip_check(launch_rh_draw(D, stream), "draw launch"))) return rc;
         cur ^= 1;
     }
-    const size_t Hs = (size_t)p->H * g.s;
-    for (int b = 0; b < B; ++b) {   // each final mean's states (the cooperative trajectory kernel)
-        rc = final_trajectory(g, packed, norm, s0 + (size_t)b * g.s, actions_out + (size_t)b * p->H * g.a, p->H,
-                              states_out + b * Hs, w.states, w.traj, stream, 0);
-        if (rc) return rc;
-    }
-    return hip_check(hipGetLastError(), "batched plan launch");
+    return batch_final_trajectories(g, packed, norm, s0, B, p->H, actions_out, states_out, w, stream);
+}
+
+int mbrl_cem_plan_rh_batch(const mbrl_mlp_shape* shape, const void* packed, const mbrl_norm* norm,
+                           const mbrl_cost* cost, const float* s0, int32_t B, const mbrl_cem_rh_params* rp,
+                           const float* init_mu_rows, const float* init_sigma_rows, const float* carry_in,
+                           const int32_t* input_flags, float* mu, float* sigma, float* actions_out, float* states_out,
+                           float* carry_out, float* carry_returns_out, float* cost_hist, float* returns_hist,
+                           int64_t* elite_hist, float* kept_hist, void* workspace, size_t ws_bytes,
+                           mbrl_stream_t stream_) {
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    Geometry g;
+    int rc = shape_geometry(shape, &g);
+    if (rc) return rc;
+    if (B < 1) return fail(MBRL_EINVAL, "cem_plan_rh_batch: B=%d", B);
+    if ((rc = rh_params_check(rp))) return rc;
+    if (carry_in && rp->keep == 0) return fail(MBRL_EINVAL, "cem_plan_rh_batch: carry_in given with keep == 0");
+    if (!packed || !s0 || !actions_out || !states_out || !workspace)
+        return fail(MBRL_EINVAL, "cem_plan_rh_batch: packed/s0/actions_out/states_out/workspace NULL");
+    if (rp->cem.N > 32768) return fail(MBRL_EUNSUPPORTED, "cem_plan_rh_batch: N=%d exceeds 32768", rp->cem.N);
+    if ((rc = batch_size_check(B, &rp->cem))) return rc;
+    // (the selections run one workgroup per problem, the staged refit a (H, B) grid)
+    if (rp->keep > 0 && B > 65535) return fail(MBRL_EUNSUPPORTED, "cem_plan_rh_batch: B=%d exceeds 65535", B);
+    if (rp->keep > 0 && (rc = refit_staged_check(g.a, rp->cem.K))) return rc;
+    const RhBatchWs w = rh_batch_ws(g, rp, B, workspace);
+    if (ws_bytes < w.bytes) return fail(MBRL_EWORKSPACE, "cem_plan_rh_batch: workspace %zu < %zu", ws_bytes, w.bytes);
+    if (rp->keep == 0)
+        return cem_batch_run(g, packed, norm, cost, s0, B, &rp->cem, init_mu_rows, init_sigma_rows, input_flags, mu,
+                             sigma, actions_out, states_out, cost_hist, returns_hist, elite_hist, w.plan, stream);
+    return cem_plan_rh_batch_kept(g, packed, norm, cost, s0, B, rp, init_mu_rows, init_sigma_rows, carry_in,
+                                  input_flags, mu, sigma, actions_out, states_out, carry_out, carry_returns_out,
+                                  cost_hist, returns_hist, elite_hist, kept_hist, w, stream);
 }
 
 }  // extern "C"

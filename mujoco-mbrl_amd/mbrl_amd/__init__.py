@@ -10,7 +10,7 @@ from .env_wrappers import EnvWrapper  # noqa: F401
 from .models import (CoshLoss, CostModel, DynamicsModel, EnsembleModel, LinearModel, Model,  # noqa: F401
                      ModelWithReward, QuadraticCost, SmoothAbsLoss, compose, goal_state_cost, state_action_cost)
 from .planners import (CEMPlanner, GradientDescentPlanner, ModelPlanner, MPPIPlanner,  # noqa: F401
-                       RandomShootingPlanner, cem_shift_carry)
+                       RandomShootingPlanner, RecedingHorizonCEMPlanner, cem_plan_batch_rh, cem_shift_carry)
 
 
 def load_extension():

@@ -15,7 +15,10 @@ from one GPU:
   * lockstep: it waits until every running worker has asked for an action;
   * it orders the requests by rollout index;
   * it answers them all with one `planner.plan_batch` call (CEMPlanner: mbrl_cem_plan_batch, one
-    rollout launch over B·N candidates per CEM iteration; DESIGN.md §9);
+    rollout launch over B·N candidates per CEM iteration). A planner whose `plan_memo` is
+    true (RecedingHorizonCEMPlanner) also gets `memos`, one per request -- None at timestep 0, else what
+    its plan_batch returned for the same rollout in the previous round -- and returns (states, actions,
+    memos): whatever the planner carries from one control step to the next stays with its rollout;
   * planners without plan_batch get one `get_action` per request on a per-rollout copy of the
     policy, so each rollout keeps its own warm start (agents.py:37-56).
 Rollouts are statically assigned (rollout i runs on worker i mod num_workers). So the batches, and
@@ -174,10 +177,11 @@ def _serve(policy, procs, req_q, conns, num_rollouts, on_batch, timeout):
     results = [None] * num_rollouts
     copies = {}                   # rollout index -> its policy copy (planners without plan_batch)
     last = {}                     # rollout index -> its previous plan (warm-starting planners)
+    memos = {}                    # rollout index -> its planner's memo of that plan (plan_memo planners)
     waited = 0.0
     while active:
         if pending and len(pending) == len(active):
-            _answer(policy, pending, conns, copies, on_batch, last)
+            _answer(policy, pending, conns, copies, on_batch, last, memos)
             pending.clear()
             continue
         try:
@@ -204,7 +208,7 @@ def _serve(policy, procs, req_q, conns, num_rollouts, on_batch, timeout):
     return results
 
 
-def _answer(policy, pending, conns, copies, on_batch, last):
+def _answer(policy, pending, conns, copies, on_batch, last, memos=None):
     """One planning round: every waiting worker's request, ordered by rollout index."""
     order = sorted(pending, key=lambda w: pending[w][0])
     indices = [pending[w][0] for w in order]
@@ -222,8 +226,17 @@ def _answer(policy, pending, conns, copies, on_batch, last):
                 prev = None if t == 0 else last.get(i)
                 inits.append(None if prev is None else (prev[0][1:], prev[1][0:]))
             kw["initial_trajectories"] = inits
-        states, actions = plan_batch(torch.stack(obs), policy.model, policy.cost, policy.sample_action,
-                                     policy.horizon, **kw)
+        memo = getattr(policy.planner, "plan_memo", False)
+        if memo:
+            memos = {} if memos is None else memos
+            kw["memos"] = [None if pending[w][1] == 0 else memos.get(pending[w][0]) for w in order]
+        out = plan_batch(torch.stack(obs), policy.model, policy.cost, policy.sample_action, policy.horizon, **kw)
+        if memo:
+            states, actions, new = out
+            for b, i in enumerate(indices):
+                memos[i] = new[b]
+        else:
+            states, actions = out
         if warm:
             for b, i in enumerate(indices):
                 last[i] = (list(states[b].split(1, 0)), list(actions[b].split(1, 0)))

@@ -16,6 +16,8 @@ CEMPlanner            -- the CEM hot path of BASELINE.json:
     one RCCL all-gather of the per-candidate returns per iteration; every rank then runs the same
     deterministic selection and refit (the refit regenerates elite actions from the counter RNG,
     so no moment collective is needed and the result is bit-identical for any rank count).
+RecedingHorizonCEMPlanner -- CEMPlanner with warm start and elite carry-over on by default; its plan_batch
+    (mbrl_cem_plan_rh_batch) keeps each problem's kept rows between control steps through memos.
 MPPIPlanner           -- CEM's loop with a softmax-weighted refit over every candidate in place of
     the elite cut (mbrl_mppi_plan), warm-started from the previous plan.
 GradientDescentPlanner -- the reference's Adam loop on one action sequence (planners.py:28-137).
@@ -337,7 +339,8 @@ class CEMPlanner(ModelPlanner):
     With keep_elites > 0 plan_detailed also returns carry [Kc, H, a] and carry_returns [Kc] (record=True:
     kept_hist [I + 1, Kc, H, a]; record=True also returns the rows a warm-started plan began from as
     init_mu / init_sigma). These kwargs raise NotImplementedError with distributed=True, in
-    plan_batch and with callables the fused path does not recognise."""
+    plan_batch and with callables the fused path does not recognise. B such plans at once, each with its own
+    warm start and carry: cem_plan_batch_rh and RecedingHorizonCEMPlanner.plan_batch."""
     defaults = dict(num_candidates=1000, num_elites=None, num_iterations=5, alpha=0.1, seed=None, init_std=None,
                     action_bounds=None, distributed=False, return_device=False, precision="f32",
                     warm_start=False, shift=1, warm_std=None, keep_elites=0, carry=None)
@@ -437,13 +440,13 @@ _RH_KWARGS = ("warm_start", "warm_std", "keep_elites", "carry")
 
 def _rh_refuse(kwargs, where):
     """NotImplementedError naming the first receding-horizon kwarg that is switched on: `where` (sharded
-    and batched plans, the generic path) has no receding-horizon form."""
+    plans, the plain batched entries, the generic path) has no receding-horizon form."""
     d = CEMPlanner.defaults
     for k in _RH_KWARGS:
         v = kwargs.get(k, d[k])
         if v is not None and v is not False and not (k == "keep_elites" and not isinstance(v, bool) and v == 0):
             raise NotImplementedError(f"{where}: {k}={v!r} is not implemented (receding-horizon CEM plans are "
-                                      "single-GPU, single-problem, fused-path plans)")
+                                      "single-GPU, fused-path plans; batched: cem_plan_batch_rh)")
 
 
 def _rh_settings(kwargs, K):
@@ -553,6 +556,173 @@ def cem_plan_batch(initial_states, model, cost, sample_action, horizon, **kwargs
                                                _lib.stream_handle(dev)), "mbrl_cem_plan_batch")
         keep = st["keep"]
         return _to_host(states, keep), _to_host(actions, keep)
+
+
+RH_FLAG_MU, RH_FLAG_SIGMA, RH_FLAG_CARRY = 1, 2, 4   # mbrl_cem_plan_rh_batch's input_flags bits
+
+
+def _per_row(x, B, name):
+    """A per-problem argument as a list of B entries (None: B Nones)."""
+    if x is None:
+        return [None] * B
+    x = list(x)
+    if len(x) != B:
+        raise ValueError(f"{name} has {len(x)} entries for {B} initial states")
+    return x
+
+
+def _rh_batch_inputs(st, B, initial_trajectories, carries, prev_sigmas, kwargs, a=None):
+    """The receding-horizon inputs of B plans as host arrays (host only, no device): each row built and
+    checked by _rh_inputs (the single plan's rules -- warm-start rows, sigma rows finite and > 0, the carry's
+    shape), then stacked. dict(mu_rows, sigma_rows [B, H, a], carry [B, Kc, H, a], each None when no row has
+    it; flags int32 [B], bit RH_FLAG_* set where row b has that input, None when nothing is given; Kc).
+    A row without an input holds filler the flags switch off (zeros; ones for sigma). a: the action
+    dimension every given row must have (None: the first given row's)."""
+    Kc = _rh_settings(kwargs, st["K"])["Kc"]
+    inits = _per_row(initial_trajectories, B, "initial_trajectories")
+    carries = _per_row(carries, B, "carries")
+    sigmas = _per_row(prev_sigmas, B, "prev_sigmas")
+    rows = []
+    for b in range(B):
+        kw = dict(kwargs, carry=carries[b], prev_sigma=sigmas[b])
+        rows.append(_rh_inputs(st, inits[b], kw) or dict(mu_rows=None, sigma_rows=None, carry=None))
+    given = [x for r in rows for x in (r["mu_rows"], r["sigma_rows"], r["carry"]) if x is not None]
+    if a is None and given:
+        a = given[0].shape[-1]
+    for b, r in enumerate(rows):
+        for k in ("mu_rows", "sigma_rows", "carry"):
+            if r[k] is not None and r[k].shape[-1] != a:
+                raise ValueError(f"row {b}: {k} has {r[k].shape[-1]} action dims, expected {a}")
+    H = st["H"]
+    out = dict(Kc=Kc, flags=None)
+    flags = np.zeros(B, np.int32)
+    for k, bit, shape, fill in (("mu_rows", RH_FLAG_MU, (H, a), 0.0), ("sigma_rows", RH_FLAG_SIGMA, (H, a), 1.0),
+                                ("carry", RH_FLAG_CARRY, (Kc, H, a), 0.0)):
+        if all(r[k] is None for r in rows):
+            out[k] = None
+            continue
+        out[k] = np.stack([np.full(shape, fill, np.float32) if r[k] is None else r[k] for r in rows])
+        flags |= np.array([0 if r[k] is None else bit for r in rows], np.int32)
+    if given:
+        out["flags"] = flags
+    return out
+
+
+def cem_plan_batch_rh(initial_states, model, cost, sample_action, horizon, initial_trajectories=None, carries=None,
+                      prev_sigmas=None, **kwargs):
+    """B independent receding-horizon CEM plans in shared launches (mbrl_cem_plan_rh_batch): cem_plan_batch
+    with each problem's own warm start and kept rows, so one GPU planner serves B environments that are each
+    somewhere in their own episode. kwargs as CEMPlanner.plan, including warm_start, shift, warm_std and
+    keep_elites (per problem). initial_trajectories, carries (each [Kc, H, a], already shifted:
+    cem_shift_carry) and prev_sigmas (warm_std="keep") are lists of B entries; a None entry plans that problem
+    without that input (its first control step). Problem b draws its proposals as candidates [b*N, (b+1)*N)
+    of one Philox stream.
+
+    Returns a dict: states [B, H, s], actions, mu, sigma [B, H, a]; with keep_elites > 0 also carry
+    [B, Kc, H, a] and carry_returns [B, Kc]; record=True adds costs [I, E, B*N], returns [I, B, N], elites
+    [I, B, K] and (keep_elites > 0) kept_hist [I + 1, B, Kc, H, a]. Host tensors unless return_device.
+    The per-row host checks (sigma rows finite and > 0, the carry's shape) raise ValueError before anything
+    touches the device; closures the fused path does not recognise raise NotImplementedError."""
+    if kwargs.get("distributed", False):
+        raise NotImplementedError("cem_plan_batch_rh: distributed=True is not implemented")
+    for k, lists in (("carry", "carries"), ("prev_sigma", "prev_sigmas")):
+        if kwargs.get(k) is not None:
+            raise TypeError(f"cem_plan_batch_rh takes per-problem lists ({lists}=...), not {k}=")
+    kwargs = {k: v for k, v in kwargs.items() if k not in ("carry", "prev_sigma")}
+    st = CEMPlanner._settings(sample_action, horizon, kwargs)
+    B = int(initial_states.shape[0])
+    if B < 1:
+        raise ValueError("cem_plan_batch_rh needs at least one initial state")
+    rh = _rh_batch_inputs(st, B, initial_trajectories, carries, prev_sigmas, kwargs)
+    dev = _device(kwargs)
+    with torch.cuda.device(dev):
+        mdesc, cdesc, prob = fused.describe_problem(model, cost, dev, st["precision"])
+        if mdesc is None or cdesc is None:
+            raise NotImplementedError("cem_plan_batch_rh: callables the fused path does not recognise are not "
+                                      "implemented (receding-horizon CEM plans are fused-path plans)")
+        lib = _lib.load()
+        N, K, H, I, Kc = st["N"], st["K"], st["H"], st["I"], rh["Kc"]
+        a, s, E = mdesc["a"], mdesc["s"], mdesc["E"]
+        for k in ("mu_rows", "sigma_rows", "carry"):
+            if rh[k] is not None and rh[k].shape[-1] != a:
+                raise ValueError(f"{k} has {rh[k].shape[-1]} action dims, the model {a}")
+        params = _lib.CemRhParams(_cem_params(st, int(st["seed"]) & 0xFFFFFFFFFFFFFFFF), Kc, 0)
+        need = lib.mbrl_cem_rh_batch_workspace_bytes(fused.ctypes_ref(prob.shape), fused.ctypes_ref(params), B)
+        if need == 0:
+            _lib.check(_lib.MBRL_EINVAL, "mbrl_cem_rh_batch_workspace_bytes")
+        ws = _workspace(("cem_rh_batch", str(dev)), need, dev)
+        s0 = initial_states.to(device=dev, dtype=torch.float32).reshape(B, s).contiguous()
+        rows_d, sig_d, carry_d, flags_d = [None if rh[k] is None else torch.from_numpy(np.ascontiguousarray(rh[k])).to(dev)
+                                           for k in ("mu_rows", "sigma_rows", "carry", "flags")]
+        e = lambda *sh, dt=torch.float32: torch.empty(sh, dtype=dt, device=dev)  # noqa: E731
+        out = dict(states=e(B, H, s), actions=e(B, H, a), mu=e(B, H, a), sigma=e(B, H, a))
+        rec = st["record"]
+        if Kc:
+            out.update(carry=e(B, Kc, H, a), carry_returns=e(B, Kc))
+        if rec:
+            out.update(costs=e(I, E, B * N), returns=e(I, B, N), elites=e(I, B, K, dt=torch.int64))
+            if Kc:
+                out.update(kept_hist=e(I + 1, B, Kc, H, a))
+        g = lambda k: _lib.ptr(out.get(k))  # noqa: E731
+        _lib.check(lib.mbrl_cem_plan_rh_batch(*prob.refs, _lib.ptr(s0), B, fused.ctypes_ref(params), _lib.ptr(rows_d),
+                                              _lib.ptr(sig_d), _lib.ptr(carry_d), _lib.ptr(flags_d), g("mu"),
+                                              g("sigma"), g("actions"), g("states"), g("carry"), g("carry_returns"),
+                                              g("costs"), g("returns"), g("elites"), g("kept_hist"), _lib.ptr(ws),
+                                              ws.numel(), _lib.stream_handle(dev)), "mbrl_cem_plan_rh_batch")
+        return {k: _to_host(v, st["keep"]) for k, v in out.items()}
+
+
+class RecedingHorizonCEMPlanner(CEMPlanner):
+    """CEMPlanner with the receding-horizon kwargs switched on -- warm_start=True and keep_elites=0.3 (a
+    fraction of num_elites) unless the caller says otherwise -- and a batched form that keeps each
+    problem's kept rows between control steps, so the planner service (parallel.get_rollouts_parallel) warm-
+    starts every rollout it serves.
+
+    plan() is CEMPlanner.plan with those defaults. plan_batch() answers B problems with one
+    cem_plan_batch_rh call and hands back one memo per problem: that plan's carry and sigma, unshifted. The
+    caller gives a problem's memo back at its next control step (None at its first), and plan_batch shifts
+    it: the carry with cem_shift_carry, the sigma (used with warm_std="keep") with mppi_warm_start_rows."""
+    rh_defaults = dict(warm_start=True, keep_elites=0.3)
+    # the planner service passes each rollout's previous plan (initial_trajectories) and its memo (memos)
+    warm_starts = True
+    plan_memo = True
+
+    @staticmethod
+    def _kwargs(kwargs):
+        return dict(RecedingHorizonCEMPlanner.rh_defaults, **kwargs)
+
+    @staticmethod
+    def plan(initial_state, model, cost, sample_action, horizon, initial_trajectory=None, **kwargs):
+        return CEMPlanner.plan(initial_state, model, cost, sample_action, horizon, initial_trajectory,
+                               **RecedingHorizonCEMPlanner._kwargs(kwargs))
+
+    @staticmethod
+    def _memo_inputs(memos, B, shift, lo, hi):
+        """(carries, prev_sigmas) for cem_plan_batch_rh from B memos (host only): a memo's carry shifted by
+        cem_shift_carry; its sigma as it is (the warm start shifts it with the mean). None stays None."""
+        memos = _per_row(memos, B, "memos")
+        carries = [None if m is None or m.get("carry") is None else cem_shift_carry(m["carry"], shift, lo, hi)
+                   for m in memos]
+        return carries, [None if m is None else m.get("sigma") for m in memos]
+
+    @staticmethod
+    def plan_batch(initial_states, model, cost, sample_action, horizon, initial_trajectories=None, memos=None,
+                   **kwargs):
+        """B plans at once; returns (states [B, H, s], actions [B, H, a], memos) -- memos[b] = dict(carry
+        [Kc, H, a] or None, sigma [H, a]) of problem b's plan, host tensors, to pass back at its next step."""
+        kw = RecedingHorizonCEMPlanner._kwargs(kwargs)
+        st = CEMPlanner._settings(sample_action, horizon, kw)
+        rs = _rh_settings(kw, st["K"])
+        B = int(initial_states.shape[0])
+        carries, sigmas = RecedingHorizonCEMPlanner._memo_inputs(memos, B, rs["shift"], st["lo"], st["hi"])
+        if rs["Kc"] == 0:
+            carries = None
+        res = cem_plan_batch_rh(initial_states, model, cost, sample_action, horizon, initial_trajectories, carries,
+                                sigmas if rs["warm_std"] == "keep" else None, **kw)
+        carry = res["carry"].cpu() if "carry" in res else None
+        sigma = res["sigma"].cpu()
+        out = [dict(carry=None if carry is None else carry[b], sigma=sigma[b]) for b in range(B)]
+        return res["states"], res["actions"], out
 
 
 _WS = threading.local()
