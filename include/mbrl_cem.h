@@ -517,6 +517,51 @@ int mbrl_cem_plan_rh_batch(const mbrl_mlp_shape* shape, const void* packed, cons
                            float* returns_hist, int64_t* elite_hist, float* kept_hist, void* workspace,
                            size_t ws_bytes, mbrl_stream_t stream);
 
+/* ---- coloured-noise proposals (the third iCEM ingredient: proposal noise correlated along the horizon; not in
+ * the reference; added within ABI v13, additively). A plan may be given a noise mix: noise_mix [H][H], fp32,
+ * row-major, device. With z[u][n][d], u = 0 .. H-1, the white normals every plan draws (Philox counter
+ * (n, u, i, d >> 2): the counter space does not move), the noise of step t is
+ *   e[t][n][d] = (..((C[t][0] z[0]) + C[t][1] z[1]) + ..) + C[t][H-1] z[H-1]
+ * -- every product rounded to fp32 before it is added, the additions sequential in u, round to nearest, no
+ * contraction -- and the action is clip(mu[t][d] + sigma[t][d] e[t][n][d]) as before. The matrix is the
+ * caller's: a power-law spectrum (Python: planners.colored_noise_mix), AR(1), action repeat. Rows of unit
+ * Euclidean norm keep e[t] marginally N(0, 1), so sigma keeps its meaning; the identity is the white draw.
+ * Every entry must be finite: the CALLER'S check, as for the sigma rows (Python makes it on the host).
+ * H > 64 with a mix is MBRL_EUNSUPPORTED before any launch (the kernels hold the matrix and one tile's normals
+ * in LDS; csrc/cem_noise.hip). A NULL mix forwards to the entry without one: the same launches, the same bits.
+ *
+ * mbrl_sample_actions_mixed: mbrl_sample_actions with the mix (RNG parity, step-by-step equivalents).
+ *
+ * mbrl_cem_plan_rh_mixed / mbrl_cem_plan_rh_batch_mixed: mbrl_cem_plan_rh / mbrl_cem_plan_rh_batch with
+ * noise_mix after carry_in / input_flags (one matrix serves all B problems). Every drawn row and every
+ * regenerated row uses the formula above; kept slots n < Kc, the NaN-stays-NaN clip, the two selections, the
+ * refit over the elites' rows and the read-back-or-regenerate rule are unchanged, per problem. With a mix the
+ * plan runs the unfused update whatever keep is: the first launch (rh's, coloured), then per iteration the
+ * rollout, the K selection, the Kc selection (only when Kc > 0), the coloured gather, the refit over the
+ * staged elites and the coloured draw -- 5 or 6 launches per iteration whatever B is -- then the final
+ * trajectories. The argument checks are the existing entries', before any launch, plus H > 64 and, also with
+ * keep == 0, a K x a the staged refit cannot hold (MBRL_EUNSUPPORTED).
+ * workspace >= mbrl_cem_rh_mixed_workspace_bytes(shape, params, B) (B = 1: the single plan, and a batch of
+ * one): a mixed plan with keep == 0 still stages the elites and keeps the returns, which the existing
+ * queries size for keep > 0 only (their values are unchanged). 0 for a bad shape, bad params, B < 1 or H > 64. */
+int mbrl_sample_actions_mixed(const mbrl_sampler* sampler, const float* mix, int32_t H, int32_t a, int32_t N,
+                              int32_t n_offset, float* actions_out, mbrl_stream_t stream);
+size_t mbrl_cem_rh_mixed_workspace_bytes(const mbrl_mlp_shape* shape, const mbrl_cem_rh_params* params, int32_t B);
+int mbrl_cem_plan_rh_mixed(const mbrl_mlp_shape* shape, const void* packed, const mbrl_norm* norm,
+                           const mbrl_cost* cost, const float* s0, const mbrl_cem_rh_params* params,
+                           const float* init_mu_rows, const float* init_sigma_rows, const float* carry_in,
+                           const float* noise_mix, float* mu, float* sigma, float* actions_out, float* states_out,
+                           float* carry_out, float* carry_returns_out, float* cost_hist, float* returns_hist,
+                           int64_t* elite_hist, float* kept_hist, mbrl_event_t* rollout_events, void* workspace,
+                           size_t ws_bytes, mbrl_stream_t stream);
+int mbrl_cem_plan_rh_batch_mixed(const mbrl_mlp_shape* shape, const void* packed, const mbrl_norm* norm,
+                                 const mbrl_cost* cost, const float* s0, int32_t B, const mbrl_cem_rh_params* params,
+                                 const float* init_mu_rows, const float* init_sigma_rows, const float* carry_in,
+                                 const int32_t* input_flags, const float* noise_mix, float* mu, float* sigma,
+                                 float* actions_out, float* states_out, float* carry_out, float* carry_returns_out,
+                                 float* cost_hist, float* returns_hist, int64_t* elite_hist, float* kept_hist,
+                                 void* workspace, size_t ws_bytes, mbrl_stream_t stream);
+
 /* ---- gradient-descent planner: replaces GradientDescentPlanner's
  * _optimize_trajectory (planners.py:103-137) -- Adam(lr) on the action sequence through the dynamics
  * with the goal-state cost (or, for a reward_head model, the MODEL_REWARD cost of RewardAgent,

@@ -435,6 +435,18 @@ struct RhDrawArgs {
 };
 hipError_t launch_rh_draw(const RhDrawArgs& A, hipStream_t stream);
 
+// ---- coloured-noise proposals (cem_noise.hip; include/mbrl_cem.h mbrl_cem_plan_rh_mixed): the three launches
+// above with every drawn or regenerated row's noise mixed along the horizon by `mix` [H][H] (device, non-NULL),
+// and the plain draw with it. The arg structs and their meaning are unchanged. H <= NOISE_MAX_H (the tile's
+// LDS); noise_check: MBRL_EUNSUPPORTED above it, for the entries to return before any launch.
+constexpr int NOISE_MAX_H = 64;
+int noise_check(int H);
+int noise_sample_impl(const mbrl_sampler* sp, const float* mix, int H, int a, int N, int n_offset, float* out,
+                      hipStream_t stream);
+hipError_t launch_noise_init(const RhInitArgs& A, const float* mix, hipStream_t stream);
+hipError_t launch_noise_gather(const RhGatherArgs& A, const float* mix, hipStream_t stream);
+hipError_t launch_noise_draw(const RhDrawArgs& A, const float* mix, hipStream_t stream);
+
 // MBRL_OPT_SHARD_EMULATE 2 (plan_sharded.hip): the all-gather's buffers in one launch. The kernel
 // stays in cem.hip with the stamp buffer it writes in the diagnostic build.
 void launch_emu_gather(const float* local, const float* kept, int G, int rank, size_t slot, const unsigned* own_status,

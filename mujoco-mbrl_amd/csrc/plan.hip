@@ -1,7 +1,7 @@
 // The plans: host dispatch of the rollout and trajectory kernels (rollout_impl, traj_impl), the plan
 // workspaces, the helpers the plan loops share (mbrl_plan.h) and the single-GPU plan entries
 // (include/mbrl_cem.h): rollout cost, trajectory, CEM plan, receding-horizon CEM plan, MPPI plan, batched
-// CEM plan, batched receding-horizon CEM plan.
+// CEM plan, batched receding-horizon CEM plan, and the two receding-horizon plans with a noise mix.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -584,7 +584,8 @@ struct RhWs {
     size_t bytes;
 };
 
-static RhWs rh_ws(const Geometry& g, const mbrl_cem_rh_params* rp, void* base) {
+// mixed (mbrl_cem_plan_rh_mixed): the returns also with keep == 0, where that plan selects unfused too.
+static RhWs rh_ws(const Geometry& g, const mbrl_cem_rh_params* rp, void* base, bool mixed = false) {
     RhWs w{};
     w.plan = plan_ws(g, &rp->cem, base);
     WsCursor c(base);
@@ -592,7 +593,7 @@ static RhWs rh_ws(const Geometry& g, const mbrl_cem_rh_params* rp, void* base) {
     const size_t kb = (size_t)rp->keep * rp->cem.H * g.a * 4;
     w.kept[0] = c.take<float>(kb); w.kept[1] = c.take<float>(kb);
     w.best = c.take<int64_t>((size_t)rp->keep * 8);
-    w.rets = c.take<float>(rp->keep ? (size_t)rp->cem.N * 4 : 0);
+    w.rets = c.take<float>(rp->keep || mixed ? (size_t)rp->cem.N * 4 : 0);
     w.bytes = c.off;
     return w;
 }
@@ -616,12 +617,15 @@ size_t mbrl_cem_rh_workspace_bytes(const mbrl_mlp_shape* shape, const mbrl_cem_r
 // refit over the gathered elites, and the next proposals (kept rows scattered into slots [0, Kc), the rest
 // drawn) or, on the last iteration, the plan outputs. kept_i lives in kept_hist's row i where the caller
 // records, else in the workspace's two buffers; iteration 0 reads carry_in where it is.
+// mix (mbrl_cem_plan_rh_mixed; NULL: none): the same loop for any keep >= 0 with the first launch, the gather
+// and the draw coloured (cem_noise.hip); the Kc selection runs only when Kc > 0.
 static int cem_plan_rh_kept(const Geometry& g, const void* packed, const mbrl_norm* norm, const mbrl_cost* cost,
                             const float* s0_in, const mbrl_cem_rh_params* rp, const float* mu_rows,
                             const float* sigma_rows, const float* carry_in, float* mu, float* sigma,
                             float* actions_out, float* states_out, float* carry_out, float* carry_returns_out,
                             float* cost_hist, float* returns_hist, int64_t* elite_hist, float* kept_hist,
-                            mbrl_event_t* rollout_events, const RhWs& rw, hipStream_t stream) {
+                            mbrl_event_t* rollout_events, const RhWs& rw, hipStream_t stream,
+                            const float* mix = nullptr) {
     const mbrl_cem_params* p = &rp->cem;
     const PlanWs& w = rw.plan;
     const int Kc = rp->keep;
@@ -636,7 +640,7 @@ static int cem_plan_rh_kept(const Geometry& g, const void* packed, const mbrl_no
         A.mu_rows = mu_rows; A.sigma_rows = sigma_rows; A.carry_in = carry_in;
         A.mu = w.mu[0]; A.sigma = w.sigma[0]; A.actions = w.actions; A.kept0 = kept_hist;
         A.s0_src = s0_in; A.s0_dst = w.s0; A.zero = z;
-        if ((rc = hip_check(launch_rh_init(A, stream), "init launch"))) return rc;
+        if ((rc = hip_check(mix ? launch_noise_init(A, mix, stream) : launch_rh_init(A, stream), "init launch"))) return rc;
     }
     unsigned pair_epoch = 0;
     const float* s0 = w.s0;   // the workspace copy (s0_in may be mapped host memory)
@@ -653,7 +657,7 @@ static int cem_plan_rh_kept(const Geometry& g, const void* packed, const mbrl_no
         if ((rc = record_rollout_event(rollout_events, 2 * it + 1, stream))) return rc;
         const size_t keys_bytes = align256((size_t)p->N * 4);
         if ((rc = select_impl(costs, g.E, p->N, p->K, MBRL_NAN_LAST, elites, rets, w.keys, keys_bytes, stream))) return rc;
-        if ((rc = select_impl(costs, g.E, p->N, Kc, MBRL_NAN_LAST, rw.best, nullptr, w.keys, keys_bytes, stream)))
+        if (Kc && (rc = select_impl(costs, g.E, p->N, Kc, MBRL_NAN_LAST, rw.best, nullptr, w.keys, keys_bytes, stream)))
             return rc;
         RhGatherArgs G{};
         G.seed = p->seed; G.iteration = it; G.N = p->N; G.H = p->H; G.a = g.a; G.K = p->K; G.Kc = Kc; G.B = 1;
@@ -661,7 +665,8 @@ static int cem_plan_rh_kept(const Geometry& g, const void* packed, const mbrl_no
         G.mu = w.mu[cur]; G.sigma = w.sigma[cur]; G.kept_cur = it == 0 ? carry_in : kept_at(it); G.returns = rets;
         G.elites = elites; G.best = rw.best; G.aelite = w.aelite; G.kept_next = kept_at(it + 1);
         G.kept_copy = last ? carry_out : nullptr; G.best_returns = last ? carry_returns_out : nullptr;
-        if ((rc = hip_check(launch_rh_gather(G, stream), "gather launch"))) return rc;
+        if ((rc = hip_check(mix ? launch_noise_gather(G, mix, stream) : launch_rh_gather(G, stream), "gather launch")))
+            return rc;
         rc = refit_staged_impl(w.aelite, p->H, g.a, p->K, p->alpha, w.mu[cur], w.sigma[cur], w.mu[cur ^ 1],
                                w.sigma[cur ^ 1], stream);
         if (rc) return rc;
@@ -671,7 +676,7 @@ static int cem_plan_rh_kept(const Geometry& g, const void* packed, const mbrl_no
         D.mu = w.mu[cur ^ 1]; D.sigma = w.sigma[cur ^ 1]; D.kept = kept_at(it + 1);
         D.actions = last ? nullptr : w.actions;
         D.fin_mu = last ? mu : nullptr; D.fin_sigma = last ? sigma : nullptr; D.fin_actions = last ? actions_out : nullptr;
-        if ((rc = hip_check(launch_rh_draw(D, stream), "draw launch"))) return rc;
+        if ((rc = hip_check(mix ? launch_noise_draw(D, mix, stream) : launch_rh_draw(D, stream), "draw launch"))) return rc;
         cur ^= 1;
     }
     rc = final_trajectory(g, packed, norm, s0, actions_out, p->H, states_out, w.states, w.traj, stream,
@@ -706,6 +711,40 @@ int mbrl_cem_plan_rh(const mbrl_mlp_shape* shape, const void* packed, const mbrl
     return cem_plan_rh_kept(g, packed, norm, cost, s0_in, rp, init_mu_rows, init_sigma_rows, carry_in, mu, sigma,
                             actions_out, states_out, carry_out, carry_returns_out, cost_hist, returns_hist, elite_hist,
                             kept_hist, rollout_events, w, stream);
+}
+
+static size_t mixed_ws_bytes(const Geometry& g, const mbrl_cem_rh_params* rp, int B);
+
+int mbrl_cem_plan_rh_mixed(const mbrl_mlp_shape* shape, const void* packed, const mbrl_norm* norm,
+                           const mbrl_cost* cost, const float* s0_in, const mbrl_cem_rh_params* rp,
+                           const float* init_mu_rows, const float* init_sigma_rows, const float* carry_in,
+                           const float* noise_mix, float* mu, float* sigma, float* actions_out, float* states_out,
+                           float* carry_out, float* carry_returns_out, float* cost_hist, float* returns_hist,
+                           int64_t* elite_hist, float* kept_hist, mbrl_event_t* rollout_events, void* workspace,
+                           size_t ws_bytes, mbrl_stream_t stream_) {
+    if (!noise_mix)
+        return mbrl_cem_plan_rh(shape, packed, norm, cost, s0_in, rp, init_mu_rows, init_sigma_rows, carry_in, mu, sigma,
+                                actions_out, states_out, carry_out, carry_returns_out, cost_hist, returns_hist,
+                                elite_hist, kept_hist, rollout_events, workspace, ws_bytes, stream_);
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    Geometry g;
+    int rc = shape_geometry(shape, &g);
+    if (rc) return rc;
+    if ((rc = rh_params_check(rp))) return rc;
+    if (carry_in && rp->keep == 0) return fail(MBRL_EINVAL, "cem_plan_rh_mixed: carry_in given with keep == 0");
+    if (!packed || !actions_out || !states_out || !workspace)
+        return fail(MBRL_EINVAL, "cem_plan_rh_mixed: packed/actions_out/states_out/workspace NULL");
+    if (!s0_in) return fail(MBRL_EINVAL, "cem_plan_rh_mixed: s0 is NULL");
+    if ((rc = noise_check(rp->cem.H))) return rc;
+    const RhWs w = rh_ws(g, rp, workspace, true);
+    if (const size_t need = mixed_ws_bytes(g, rp, 1); ws_bytes < need)
+        return fail(MBRL_EINVAL, "cem_plan_rh_mixed: workspace %zu < %zu", ws_bytes, need);
+    if (rp->cem.N > 32768) return fail(MBRL_EUNSUPPORTED, "cem_plan_rh_mixed: N=%d exceeds 32768", rp->cem.N);
+    if ((rc = pair_forced_check(g, rp->cem.N))) return rc;
+    if ((rc = refit_staged_check(g.a, rp->cem.K))) return rc;
+    return cem_plan_rh_kept(g, packed, norm, cost, s0_in, rp, init_mu_rows, init_sigma_rows, carry_in, mu, sigma,
+                            actions_out, states_out, carry_out, carry_returns_out, cost_hist, returns_hist, elite_hist,
+                            kept_hist, rollout_events, w, stream, noise_mix);
 }
 
 // Workspace layout for mbrl_mppi_plan (PlanWs without the selection's and the elites' scratch).
@@ -954,17 +993,18 @@ struct RhBatchWs {
     size_t bytes;
 };
 
-static RhBatchWs rh_batch_ws(const Geometry& g, const mbrl_cem_rh_params* rp, int B, void* base) {
+// mixed (mbrl_cem_plan_rh_batch_mixed): the staged elites and the returns also with keep == 0.
+static RhBatchWs rh_batch_ws(const Geometry& g, const mbrl_cem_rh_params* rp, int B, void* base, bool mixed = false) {
     RhBatchWs w{};
     const mbrl_cem_params* p = &rp->cem;
     w.plan = batch_ws(g, p, B, base);
     WsCursor c(base);
     c.off = w.plan.bytes;
     const size_t kb = (size_t)B * rp->keep * p->H * g.a * 4;
-    w.aelite = c.take<float>(rp->keep ? (size_t)B * p->H * p->K * g.a * 4 : 0);
+    w.aelite = c.take<float>(rp->keep || mixed ? (size_t)B * p->H * p->K * g.a * 4 : 0);
     w.kept[0] = c.take<float>(kb); w.kept[1] = c.take<float>(kb);
     w.best = c.take<int64_t>((size_t)B * rp->keep * 8);
-    w.rets = c.take<float>(rp->keep ? (size_t)B * p->N * 4 : 0);
+    w.rets = c.take<float>(rp->keep || mixed ? (size_t)B * p->N * 4 : 0);
     w.bytes = c.off;
     return w;
 }
@@ -979,12 +1019,14 @@ size_t mbrl_cem_rh_batch_workspace_bytes(const mbrl_mlp_shape* shape, const mbrl
 // of the B N proposals, then the same five small launches, each over all B problems (segmented selections,
 // grid (H, B) refit); the first launch also expands s0 to the rollout's per-candidate start states.
 // Iteration 0 honours the problems' input flags; from iteration 1 on every problem has a kept set.
+// mix: as cem_plan_rh_kept's.
 static int cem_plan_rh_batch_kept(const Geometry& g, const void* packed, const mbrl_norm* norm, const mbrl_cost* cost,
                                   const float* s0, int B, const mbrl_cem_rh_params* rp, const float* mu_rows,
                                   const float* sigma_rows, const float* carry_in, const int32_t* flags, float* mu,
                                   float* sigma, float* actions_out, float* states_out, float* carry_out,
                                   float* carry_returns_out, float* cost_hist, float* returns_hist, int64_t* elite_hist,
-                                  float* kept_hist, const RhBatchWs& rw, hipStream_t stream) {
+                                  float* kept_hist, const RhBatchWs& rw, hipStream_t stream,
+                                  const float* mix = nullptr) {
     const mbrl_cem_params* p = &rp->cem;
     const BatchWs& w = rw.plan;
     const int Kc = rp->keep, BN = B * p->N;
@@ -998,7 +1040,7 @@ static int cem_plan_rh_batch_kept(const Geometry& g, const void* packed, const m
         A.mu_rows = mu_rows; A.sigma_rows = sigma_rows; A.carry_in = carry_in; A.flags = flags;
         A.mu = w.mu[0]; A.sigma = w.sigma[0]; A.actions = w.actions; A.kept0 = kept_hist;
         A.s0_src = s0; A.s0_dst = w.s0x;
-        if ((rc = hip_check(launch_rh_init(A, stream), "init launch"))) return rc;
+        if ((rc = hip_check(mix ? launch_noise_init(A, mix, stream) : launch_rh_init(A, stream), "init launch"))) return rc;
     }
     const size_t keys_bytes = align256((size_t)BN * 4);
     int cur = 0;
@@ -1012,7 +1054,7 @@ static int cem_plan_rh_batch_kept(const Geometry& g, const void* packed, const m
         if (rc) return rc;
         if ((rc = select_impl(costs, g.E, p->N, p->K, MBRL_NAN_LAST, elites, rets, w.keys, keys_bytes, stream, B)))
             return rc;
-        if ((rc = select_impl(costs, g.E, p->N, Kc, MBRL_NAN_LAST, rw.best, nullptr, w.keys, keys_bytes, stream, B)))
+        if (Kc && (rc = select_impl(costs, g.E, p->N, Kc, MBRL_NAN_LAST, rw.best, nullptr, w.keys, keys_bytes, stream, B)))
             return rc;
         RhGatherArgs G{};
         G.seed = p->seed; G.iteration = it; G.N = p->N; G.H = p->H; G.a = g.a; G.K = p->K; G.Kc = Kc; G.B = B;
@@ -1020,7 +1062,8 @@ static int cem_plan_rh_batch_kept(const Geometry& g, const void* packed, const m
         G.mu = w.mu[cur]; G.sigma = w.sigma[cur]; G.kept_cur = it == 0 ? carry_in : kept_at(it); G.returns = rets;
         G.elites = elites; G.best = rw.best; G.aelite = rw.aelite; G.kept_next = kept_at(it + 1);
         G.kept_copy = last ? carry_out : nullptr; G.best_returns = last ? carry_returns_out : nullptr;
-        if ((rc = hip_check(launch_rh_gather(G, stream), "gather launch"))) return rc;
+        if ((rc = hip_check(mix ? launch_noise_gather(G, mix, stream) : launch_rh_gather(G, stream), "gather launch")))
+            return rc;
         rc = refit_staged_impl(rw.aelite, p->H, g.a, p->K, p->alpha, w.mu[cur], w.sigma[cur], w.mu[cur ^ 1],
                                w.sigma[cur ^ 1], stream, B);
         if (rc) return rc;
@@ -1030,7 +1073,7 @@ static int cem_plan_rh_batch_kept(const Geometry& g, const void* packed, const m
         D.mu = w.mu[cur ^ 1]; D.sigma = w.sigma[cur ^ 1]; D.kept = kept_at(it + 1);
         D.actions = last ? nullptr : w.actions;
         D.fin_mu = last ? mu : nullptr; D.fin_sigma = last ? sigma : nullptr; D.fin_actions = last ? actions_out : nullptr;
-        if ((rc = hip_check(launch_rh_draw(D, stream), "draw launch"))) return rc;
+        if ((rc = hip_check(mix ? launch_noise_draw(D, mix, stream) : launch_rh_draw(D, stream), "draw launch"))) return rc;
         cur ^= 1;
     }
     return batch_final_trajectories(g, packed, norm, s0, B, p->H, actions_out, states_out, w, stream);
@@ -1065,6 +1108,55 @@ int mbrl_cem_plan_rh_batch(const mbrl_mlp_shape* shape, const void* packed, cons
     return cem_plan_rh_batch_kept(g, packed, norm, cost, s0, B, rp, init_mu_rows, init_sigma_rows, carry_in,
                                   input_flags, mu, sigma, actions_out, states_out, carry_out, carry_returns_out,
                                   cost_hist, returns_hist, elite_hist, kept_hist, w, stream);
+}
+
+// What mbrl_cem_rh_mixed_workspace_bytes answers and both mixed entries demand: the batched layout, and for
+// B == 1 the larger of it and the single plan's (one query serves either entry).
+static size_t mixed_ws_bytes(const Geometry& g, const mbrl_cem_rh_params* rp, int B) {
+    const size_t batch = rh_batch_ws(g, rp, B, nullptr, true).bytes;
+    if (B > 1) return batch;
+    const size_t single = rh_ws(g, rp, nullptr, true).bytes;
+    return single > batch ? single : batch;
+}
+
+size_t mbrl_cem_rh_mixed_workspace_bytes(const mbrl_mlp_shape* shape, const mbrl_cem_rh_params* params, int32_t B) {
+    Geometry g;
+    if (shape_geometry(shape, &g) != MBRL_OK || rh_params_check(params) != MBRL_OK || B < 1) return 0;
+    if (params->cem.H > NOISE_MAX_H) return 0;
+    return mixed_ws_bytes(g, params, B);
+}
+
+int mbrl_cem_plan_rh_batch_mixed(const mbrl_mlp_shape* shape, const void* packed, const mbrl_norm* norm,
+                                 const mbrl_cost* cost, const float* s0, int32_t B, const mbrl_cem_rh_params* rp,
+                                 const float* init_mu_rows, const float* init_sigma_rows, const float* carry_in,
+                                 const int32_t* input_flags, const float* noise_mix, float* mu, float* sigma,
+                                 float* actions_out, float* states_out, float* carry_out, float* carry_returns_out,
+                                 float* cost_hist, float* returns_hist, int64_t* elite_hist, float* kept_hist,
+                                 void* workspace, size_t ws_bytes, mbrl_stream_t stream_) {
+    if (!noise_mix)
+        return mbrl_cem_plan_rh_batch(shape, packed, norm, cost, s0, B, rp, init_mu_rows, init_sigma_rows, carry_in,
+                                      input_flags, mu, sigma, actions_out, states_out, carry_out, carry_returns_out,
+                                      cost_hist, returns_hist, elite_hist, kept_hist, workspace, ws_bytes, stream_);
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    Geometry g;
+    int rc = shape_geometry(shape, &g);
+    if (rc) return rc;
+    if (B < 1) return fail(MBRL_EINVAL, "cem_plan_rh_batch_mixed: B=%d", B);
+    if ((rc = rh_params_check(rp))) return rc;
+    if (carry_in && rp->keep == 0) return fail(MBRL_EINVAL, "cem_plan_rh_batch_mixed: carry_in given with keep == 0");
+    if (!packed || !s0 || !actions_out || !states_out || !workspace)
+        return fail(MBRL_EINVAL, "cem_plan_rh_batch_mixed: packed/s0/actions_out/states_out/workspace NULL");
+    if ((rc = noise_check(rp->cem.H))) return rc;
+    if (rp->cem.N > 32768) return fail(MBRL_EUNSUPPORTED, "cem_plan_rh_batch_mixed: N=%d exceeds 32768", rp->cem.N);
+    if ((rc = batch_size_check(B, &rp->cem))) return rc;
+    if (B > 65535) return fail(MBRL_EUNSUPPORTED, "cem_plan_rh_batch_mixed: B=%d exceeds 65535", B);
+    if ((rc = refit_staged_check(g.a, rp->cem.K))) return rc;
+    const RhBatchWs w = rh_batch_ws(g, rp, B, workspace, true);
+    if (const size_t need = mixed_ws_bytes(g, rp, B); ws_bytes < need)
+        return fail(MBRL_EWORKSPACE, "cem_plan_rh_batch_mixed: workspace %zu < %zu", ws_bytes, need);
+    return cem_plan_rh_batch_kept(g, packed, norm, cost, s0, B, rp, init_mu_rows, init_sigma_rows, carry_in, input_flags,
+                                  mu, sigma, actions_out, states_out, carry_out, carry_returns_out, cost_hist,
+                                  returns_hist, elite_hist, kept_hist, w, stream, noise_mix);
 }
 
 }  // extern "C"

@@ -69,6 +69,8 @@ EXPORTED = (
     "mbrl_mppi_update", "mbrl_mppi_workspace_bytes", "mbrl_mppi_plan",
     "mbrl_cem_rh_workspace_bytes", "mbrl_cem_plan_rh",
     "mbrl_cem_rh_batch_workspace_bytes", "mbrl_cem_plan_rh_batch",
+    "mbrl_sample_actions_mixed", "mbrl_cem_rh_mixed_workspace_bytes", "mbrl_cem_plan_rh_mixed",
+    "mbrl_cem_plan_rh_batch_mixed",
 )
 
 
@@ -209,6 +211,15 @@ def load():
         "mbrl_cem_plan_rh_batch": (c_int32, [POINTER(MlpShape), P, POINTER(Norm), POINTER(Cost), P, c_int32,
                                              POINTER(CemRhParams), P, P, P, P, P, P, P, P, P, P, P, P, P, P, P,
                                              c_size_t, P]),
+        # coloured-noise proposals: the entries above with a noise_mix [H][H] pointer (NULL: forwarded)
+        "mbrl_sample_actions_mixed": (c_int32, [POINTER(Sampler), P, c_int32, c_int32, c_int32, c_int32, P, P]),
+        "mbrl_cem_rh_mixed_workspace_bytes": (c_size_t, [POINTER(MlpShape), POINTER(CemRhParams), c_int32]),
+        "mbrl_cem_plan_rh_mixed": (c_int32, [POINTER(MlpShape), P, POINTER(Norm), POINTER(Cost), P,
+                                             POINTER(CemRhParams), P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P,
+                                             c_size_t, P]),
+        "mbrl_cem_plan_rh_batch_mixed": (c_int32, [POINTER(MlpShape), P, POINTER(Norm), POINTER(Cost), P, c_int32,
+                                                   POINTER(CemRhParams), P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P,
+                                                   c_size_t, P]),
         "mbrl_comm_unique_id": (c_int32, [P]),
         "mbrl_comm_init": (c_int32, [P, c_int32, c_int32, POINTER(c_void_p)]),
         "mbrl_comm_destroy": (c_int32, [P]),

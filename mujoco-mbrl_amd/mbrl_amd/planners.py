@@ -16,6 +16,8 @@ CEMPlanner            -- the CEM hot path of BASELINE.json:
     one RCCL all-gather of the per-candidate returns per iteration; every rank then runs the same
     deterministic selection and refit (the refit regenerates elite actions from the counter RNG,
     so no moment collective is needed and the result is bit-identical for any rank count).
+    noise_beta / noise_mix give the proposals noise correlated along the horizon (colored_noise_mix; the
+    third iCEM ingredient), on the receding-horizon path.
 RecedingHorizonCEMPlanner -- CEMPlanner with warm start and elite carry-over on by default; its plan_batch
     (mbrl_cem_plan_rh_batch) keeps each problem's kept rows between control steps through memos.
 MPPIPlanner           -- CEM's loop with a softmax-weighted refit over every candidate in place of
@@ -30,6 +32,7 @@ _device_outputs / _stage_in / _stage_out (the one output buffer, on the device o
 staging), _cem_record_buffers, _mark, _finish and _generic_plan (the loop over opaque callables).
 """
 import contextlib
+import functools
 import threading
 import warnings
 
@@ -234,6 +237,7 @@ class RandomShootingPlanner(ModelPlanner):
 
     @staticmethod
     def plan(initial_state, model, cost, sample_action, horizon, initial_trajectory=None, **kwargs):
+        _noise_refuse(kwargs, "RandomShootingPlanner")
         kw = dict(kwargs)
         num_trajectories = kw.pop("num_trajectories", RandomShootingPlanner.defaults["num_trajectories"])
         return RandomShootingPlanner._plan(initial_state, model, cost, sample_action, horizon, initial_trajectory,
@@ -274,6 +278,7 @@ class RandomShootingPlanner(ModelPlanner):
         draw (row order, as B plan() calls would draw). Recognised closures roll all B*N candidates
         out in one launch (per-candidate start states), then take each row's np.argmin.
         Returns (states [B, H, s], actions [B, H, a])."""
+        _noise_refuse(kwargs, "RandomShootingPlanner.plan_batch")
         kw = dict(kwargs)
         N = int(kw.pop("num_trajectories", RandomShootingPlanner.defaults["num_trajectories"]))
         H, B = int(horizon), int(initial_states.shape[0])
@@ -340,10 +345,21 @@ class CEMPlanner(ModelPlanner):
     kept_hist [I + 1, Kc, H, a]; record=True also returns the rows a warm-started plan began from as
     init_mu / init_sigma). These kwargs raise NotImplementedError with distributed=True, in
     plan_batch and with callables the fused path does not recognise. B such plans at once, each with its own
-    warm start and carry: cem_plan_batch_rh and RecedingHorizonCEMPlanner.plan_batch."""
+    warm start and carry: cem_plan_batch_rh and RecedingHorizonCEMPlanner.plan_batch.
+
+    Coloured noise (mbrl_cem_plan_rh_mixed; the third iCEM ingredient, off by default): the proposal noise of a
+    candidate is correlated along the horizon instead of white.
+    noise_beta (0.0): the exponent of the noise's power-law spectrum, in [0, 4] (colored_noise_mix(horizon,
+        beta); 0 is white and passes no matrix at all: the existing plan, bit for bit).
+    noise_mix (None): an explicit [horizon, horizon] mixing matrix instead (any temporal correlation; rows of
+        unit norm keep sigma's meaning). Every entry finite, checked on the host. Naming both raises ValueError.
+    Either routes the plan to the receding-horizon path (the unfused update), with or without a warm start
+    or kept rows; horizon <= 64. The same refusals as the receding-horizon kwargs apply, and MPPIPlanner and
+    RandomShootingPlanner refuse them too."""
     defaults = dict(num_candidates=1000, num_elites=None, num_iterations=5, alpha=0.1, seed=None, init_std=None,
                     action_bounds=None, distributed=False, return_device=False, precision="f32",
-                    warm_start=False, shift=1, warm_std=None, keep_elites=0, carry=None)
+                    warm_start=False, shift=1, warm_std=None, keep_elites=0, carry=None, noise_beta=0.0,
+                    noise_mix=None)
 
     @staticmethod
     def plan(initial_state, model, cost, sample_action, horizon, initial_trajectory=None, **kwargs):
@@ -355,10 +371,11 @@ class CEMPlanner(ModelPlanner):
     def plan_batch(initial_states, model, cost, sample_action, horizon, **kwargs):
         """B plans at once, one per row of initial_states [B, s] (see cem_plan_batch)."""
         _rh_refuse(kwargs, "CEMPlanner.plan_batch")
+        _noise_refuse(kwargs, "CEMPlanner.plan_batch")
         return cem_plan_batch(initial_states, model, cost, sample_action, horizon, **kwargs)
 
     _SETTINGS = {}
-    _HOOKS = ("rollout_events", "plan_events", "carry", "prev_sigma")   # per-plan values: not settings
+    _HOOKS = ("rollout_events", "plan_events", "carry", "prev_sigma", "noise_mix")   # per-plan values: not settings
 
     @staticmethod
     def _settings(sample_action, horizon, kwargs):
@@ -404,11 +421,14 @@ class CEMPlanner(ModelPlanner):
         [, carry, carry_returns[, kept_hist]])."""
         if kwargs.get("distributed", False):
             _rh_refuse(kwargs, "CEMPlanner with distributed=True")   # (before anything needs a device)
+            _noise_refuse(kwargs, "CEMPlanner with distributed=True")
+        noise = _noise_inputs(kwargs, int(horizon)) if any(k in kwargs for k in _NOISE_KWARGS) else None
         dev = _device(kwargs)
         st = CEMPlanner._settings(sample_action, horizon, kwargs)
         # (the settings dict does not carry the receding-horizon kwargs: a plan that names none of them
         # takes the plain path with nothing added to its host turn)
         rh = _rh_inputs(st, initial_trajectory, kwargs) if any(k in kwargs for k in _RH_KWARGS) else None
+        rh = _rh_with_noise(rh, noise)
         with _on_device(dev):
             mdesc, cdesc, prob = fused.describe_problem(model, cost, dev, st["precision"])
             ws = None
@@ -417,6 +437,7 @@ class CEMPlanner(ModelPlanner):
                 ws = torch.distributed.get_world_size()
             if rh is not None and (mdesc is None or cdesc is None):
                 _rh_refuse(kwargs, "CEMPlanner with callables the fused path does not recognise")
+                _noise_refuse(kwargs, "CEMPlanner with callables the fused path does not recognise")
             if mdesc is not None and cdesc is not None:
                 if rh is not None:
                     res = _cem_fused_rh(prob, initial_state, st, rh)
@@ -447,6 +468,119 @@ def _rh_refuse(kwargs, where):
         if v is not None and v is not False and not (k == "keep_elites" and not isinstance(v, bool) and v == 0):
             raise NotImplementedError(f"{where}: {k}={v!r} is not implemented (receding-horizon CEM plans are "
                                       "single-GPU, fused-path plans; batched: cem_plan_batch_rh)")
+
+
+_NOISE_KWARGS = ("noise_beta", "noise_mix")
+NOISE_MAX_H = 64    # include/mbrl_cem.h: a mix with a longer horizon is MBRL_EUNSUPPORTED
+
+
+def _noise_refuse(kwargs, where):
+    """NotImplementedError naming the coloured-noise kwarg that is switched on: `where` has no coloured form."""
+    beta, mix = kwargs.get("noise_beta", 0.0), kwargs.get("noise_mix")
+    for k, v, on in (("noise_beta", beta, beta is not None and beta != 0), ("noise_mix", mix, mix is not None)):
+        if on:
+            shown = f"array{tuple(np.shape(v))}" if k == "noise_mix" else repr(v)
+            raise NotImplementedError(f"{where}: {k}={shown} is not implemented (coloured-noise proposals are "
+                                      "single-GPU, fused-path receding-horizon CEM plans: CEMPlanner.plan, "
+                                      "cem_plan_batch_rh)")
+
+
+def colored_noise_mix(H, beta):
+    """The [H, H] float32 matrix that turns H white normals into noise with a power-law spectrum
+    S(f) ~ f^(-beta) along the horizon: colorednoise.powerlaw_psd_gaussian's synthesis (Timmer & Koenig 1995)
+    written as a matrix, built in float64. Frequencies f_k = k / H, k = 1 .. H // 2, scales s_k = f_k^(-beta / 2)
+    and s_0 = s_1; column 0 is sqrt(2) s_0, columns 2k - 1 / 2k are 2 s_k cos / -2 s_k sin of 2 pi k t / H for
+    k < ceil(H / 2), and an even H's last column is sqrt(2) s_{H/2} (-1)^t. One scalar then gives every row unit
+    Euclidean norm, the DC term included (colorednoise leaves it out), so each step's noise is marginally
+    N(0, 1) and sigma keeps its meaning. beta = 0 is an orthogonal matrix (white noise); H = 1 is [[1]]."""
+    H, beta = int(H), float(beta)
+    if H < 1:
+        raise ValueError(f"colored_noise_mix: H={H} must be >= 1")
+    if not (np.isfinite(beta) and 0.0 <= beta <= 4.0):
+        raise ValueError(f"colored_noise_mix: beta must be finite and in [0, 4], got {beta}")
+    if H == 1:
+        return np.ones((1, 1), np.float32)
+    return _colored_noise_mix64(H, beta).astype(np.float32)
+
+
+def _colored_noise_mix64(H, beta):
+    """colored_noise_mix before the cast (float64; H >= 2)."""
+    t = np.arange(H, dtype=np.float64)
+    k = np.arange(1, H // 2 + 1, dtype=np.float64)
+    s = np.concatenate([[0.0], (k / H) ** (-beta / 2.0)])
+    s[0] = s[1]
+    C = np.zeros((H, H), np.float64)
+    C[:, 0] = np.sqrt(2.0) * s[0]
+    for kk in range(1, (H + 1) // 2):
+        C[:, 2 * kk - 1] = 2.0 * s[kk] * np.cos(2.0 * np.pi * kk * t / H)
+        C[:, 2 * kk] = -2.0 * s[kk] * np.sin(2.0 * np.pi * kk * t / H)
+    if H % 2 == 0:
+        C[:, H - 1] = np.sqrt(2.0) * s[H // 2] * np.where(np.arange(H) % 2 == 0, 1.0, -1.0)
+    norms = np.sqrt((C * C).sum(1))
+    assert np.allclose(norms, norms[0], rtol=1e-12, atol=0.0), "colored_noise_mix: rows of unequal norm"
+    return C / norms[0]
+
+
+def _noise_inputs(kwargs, H):
+    """The noise mix of a plan with these kwargs (host only): None for white noise (noise_beta == 0 and no
+    matrix), else (key, matrix) -- float32 [H, H], C-contiguous, every entry finite -- with `key` what the
+    device copy is cached under (the exponent, or the matrix's bytes)."""
+    beta, mix = kwargs.get("noise_beta", 0.0), kwargs.get("noise_mix")
+    beta = 0.0 if beta is None else float(beta)
+    if mix is not None and beta != 0.0:
+        raise ValueError("give noise_beta or noise_mix, not both")
+    if mix is None:
+        if not (np.isfinite(beta) and 0.0 <= beta <= 4.0):
+            raise ValueError(f"noise_beta must be finite and in [0, 4], got {beta}")
+        if beta == 0.0:
+            return None
+        _noise_horizon(H)
+        return _beta_noise(H, beta)
+    m = mix.detach().cpu().numpy() if isinstance(mix, torch.Tensor) else np.asarray(mix)
+    if m.shape != (H, H):
+        raise ValueError(f"noise_mix must be [horizon={H}, horizon={H}], got {m.shape}")
+    m = np.ascontiguousarray(m, dtype=np.float32)
+    if not np.isfinite(m).all():
+        raise ValueError("noise_mix must be finite")
+    _noise_horizon(H)
+    return ("mix", H, m.tobytes()), m
+
+
+@functools.lru_cache(maxsize=16)
+def _beta_noise(H, beta):
+    """_noise_inputs' answer for a power-law mix, built once per (H, beta): the matrix is read-only."""
+    m = colored_noise_mix(H, beta)
+    m.setflags(write=False)
+    return ("beta", H, beta), m
+
+
+def _noise_horizon(H):
+    if H > NOISE_MAX_H:
+        raise ValueError(f"coloured-noise proposals need horizon <= {NOISE_MAX_H}, got {H}")
+
+
+def _rh_with_noise(rh, noise):
+    """The receding-horizon inputs of a plan (or None) with its noise mix (or None): a mix alone still takes
+    the receding-horizon path, with no rows and nothing kept."""
+    if noise is None:
+        return rh
+    if rh is None:
+        rh = dict(mu_rows=None, sigma_rows=None, carry=None, Kc=0)
+    return dict(rh, mix=noise)
+
+
+_MIX_DEVICE = {}
+
+
+def _noise_mix_device(noise, dev):
+    """The device copy of a plan's noise mix (_noise_inputs), kept per (matrix, device)."""
+    key = noise[0] + (str(dev),)
+    hit = _MIX_DEVICE.get(key)
+    if hit is None:
+        if len(_MIX_DEVICE) > 16:
+            _MIX_DEVICE.clear()
+        hit = _MIX_DEVICE[key] = torch.from_numpy(noise[1].copy()).to(dev)   # (a cached matrix is read-only)
+    return hit
 
 
 def _rh_settings(kwargs, K):
@@ -533,6 +667,7 @@ def cem_plan_batch(initial_states, model, cost, sample_action, horizon, **kwargs
 
     Closures the fused path does not recognise fall back to one CEMPlanner.plan per row."""
     _rh_refuse(kwargs, "cem_plan_batch")
+    _noise_refuse(kwargs, "cem_plan_batch")
     dev = _device(kwargs)
     st = CEMPlanner._settings(sample_action, horizon, kwargs)
     B = int(initial_states.shape[0])
@@ -625,6 +760,7 @@ def cem_plan_batch_rh(initial_states, model, cost, sample_action, horizon, initi
     touches the device; closures the fused path does not recognise raise NotImplementedError."""
     if kwargs.get("distributed", False):
         raise NotImplementedError("cem_plan_batch_rh: distributed=True is not implemented")
+    noise = _noise_inputs(kwargs, int(horizon))
     for k, lists in (("carry", "carries"), ("prev_sigma", "prev_sigmas")):
         if kwargs.get(k) is not None:
             raise TypeError(f"cem_plan_batch_rh takes per-problem lists ({lists}=...), not {k}=")
@@ -647,9 +783,10 @@ def cem_plan_batch_rh(initial_states, model, cost, sample_action, horizon, initi
             if rh[k] is not None and rh[k].shape[-1] != a:
                 raise ValueError(f"{k} has {rh[k].shape[-1]} action dims, the model {a}")
         params = _lib.CemRhParams(_cem_params(st, int(st["seed"]) & 0xFFFFFFFFFFFFFFFF), Kc, 0)
-        need = lib.mbrl_cem_rh_batch_workspace_bytes(fused.ctypes_ref(prob.shape), fused.ctypes_ref(params), B)
+        sizer = lib.mbrl_cem_rh_batch_workspace_bytes if noise is None else lib.mbrl_cem_rh_mixed_workspace_bytes
+        need = sizer(fused.ctypes_ref(prob.shape), fused.ctypes_ref(params), B)
         if need == 0:
-            _lib.check(_lib.MBRL_EINVAL, "mbrl_cem_rh_batch_workspace_bytes")
+            _lib.check(_lib.MBRL_EINVAL, sizer.__name__)
         ws = _workspace(("cem_rh_batch", str(dev)), need, dev)
         s0 = initial_states.to(device=dev, dtype=torch.float32).reshape(B, s).contiguous()
         rows_d, sig_d, carry_d, flags_d = [None if rh[k] is None else torch.from_numpy(np.ascontiguousarray(rh[k])).to(dev)
@@ -664,11 +801,14 @@ def cem_plan_batch_rh(initial_states, model, cost, sample_action, horizon, initi
             if Kc:
                 out.update(kept_hist=e(I + 1, B, Kc, H, a))
         g = lambda k: _lib.ptr(out.get(k))  # noqa: E731
-        _lib.check(lib.mbrl_cem_plan_rh_batch(*prob.refs, _lib.ptr(s0), B, fused.ctypes_ref(params), _lib.ptr(rows_d),
-                                              _lib.ptr(sig_d), _lib.ptr(carry_d), _lib.ptr(flags_d), g("mu"),
-                                              g("sigma"), g("actions"), g("states"), g("carry"), g("carry_returns"),
-                                              g("costs"), g("returns"), g("elites"), g("kept_hist"), _lib.ptr(ws),
-                                              ws.numel(), _lib.stream_handle(dev)), "mbrl_cem_plan_rh_batch")
+        ins = (_lib.ptr(rows_d), _lib.ptr(sig_d), _lib.ptr(carry_d), _lib.ptr(flags_d))
+        if noise is not None:     # (one matrix serves all B problems)
+            call, ins = lib.mbrl_cem_plan_rh_batch_mixed, ins + (_lib.ptr(_noise_mix_device(noise, dev)),)
+        else:
+            call = lib.mbrl_cem_plan_rh_batch
+        _lib.check(call(*prob.refs, _lib.ptr(s0), B, fused.ctypes_ref(params), *ins, g("mu"), g("sigma"), g("actions"),
+                        g("states"), g("carry"), g("carry_returns"), g("costs"), g("returns"), g("elites"),
+                        g("kept_hist"), _lib.ptr(ws), ws.numel(), _lib.stream_handle(dev)), call.__name__)
         return {k: _to_host(v, st["keep"]) for k, v in out.items()}
 
 
@@ -903,7 +1043,8 @@ def _cem_fused_single(prob, initial_state, st):
 
 
 def _cem_fused_rh(prob, initial_state, st, rh):
-    """One C-ABI call: mbrl_cem_plan_rh (every iteration stream-ordered, no host sync). rh: _rh_inputs."""
+    """One C-ABI call: mbrl_cem_plan_rh, or mbrl_cem_plan_rh_mixed where the plan has a noise mix (every
+    iteration stream-ordered, no host sync). rh: _rh_inputs, with "mix" from _rh_with_noise."""
     lib = _lib.load()
     dev = prob.device
     md = prob.mdesc
@@ -912,11 +1053,14 @@ def _cem_fused_rh(prob, initial_state, st, rh):
     for k in ("mu_rows", "sigma_rows", "carry"):
         if rh[k] is not None and rh[k].shape[-1] != a:
             raise ValueError(f"{k} has {rh[k].shape[-1]} action dims, the model {a}")
-    pkey = ("rh", N, H, K, I, Kc, st["alpha"], st["lo"], st["hi"], st["init_std"], int(st["seed"]) & 0xFFFFFFFFFFFFFFFF)
-    _, pref, need = _plan_params(prob, pkey, lambda: _lib.CemRhParams(_cem_params(st, pkey[-1]), Kc, 0),
-                                 lib.mbrl_cem_rh_workspace_bytes)
+    noise = rh.get("mix")
+    pkey = ("rh" if noise is None else "rh_mixed", N, H, K, I, Kc, st["alpha"], st["lo"], st["hi"], st["init_std"],
+            int(st["seed"]) & 0xFFFFFFFFFFFFFFFF)
+    sizer = lib.mbrl_cem_rh_workspace_bytes if noise is None else lib.mbrl_cem_rh_mixed_workspace_bytes
+    _, pref, need = _plan_params(prob, pkey, lambda: _lib.CemRhParams(_cem_params(st, pkey[-1]), Kc, 0), sizer,
+                                 *(() if noise is None else (1,)))
     if need == 0:
-        _lib.check(_lib.MBRL_EINVAL, "mbrl_cem_rh_workspace_bytes")
+        _lib.check(_lib.MBRL_EINVAL, sizer.__name__)
     ws = _workspace(("cem_rh", str(dev)), need, dev)
     s0 = initial_state.to(device=dev, dtype=torch.float32).contiguous()
     rows_d, sig_d, carry_d = [None if rh[k] is None else torch.from_numpy(np.ascontiguousarray(rh[k])).to(dev)
@@ -931,11 +1075,14 @@ def _cem_fused_rh(prob, initial_state, st, rh):
         kept_hist = torch.empty((I + 1, Kc, H, a), dtype=torch.float32, device=dev) if rec else None
     pev = st["plan_events"]
     _mark(pev, 0)
-    _lib.check(lib.mbrl_cem_plan_rh(*prob.refs, _lib.ptr(s0), pref, _lib.ptr(rows_d), _lib.ptr(sig_d),
-                                    _lib.ptr(carry_d), *_output_ptrs(out), _lib.ptr(carry_out), _lib.ptr(carry_ret),
-                                    _lib.ptr(cost_hist), _lib.ptr(ret_hist), _lib.ptr(elite_hist),
-                                    _lib.ptr(kept_hist), _events(st, I), _lib.ptr(ws), ws.numel(),
-                                    _lib.stream_handle(dev)), "mbrl_cem_plan_rh")
+    ins = (_lib.ptr(rows_d), _lib.ptr(sig_d), _lib.ptr(carry_d))
+    if noise is not None:
+        call, ins = lib.mbrl_cem_plan_rh_mixed, ins + (_lib.ptr(_noise_mix_device(noise, dev)),)
+    else:
+        call = lib.mbrl_cem_plan_rh
+    _lib.check(call(*prob.refs, _lib.ptr(s0), pref, *ins, *_output_ptrs(out), _lib.ptr(carry_out), _lib.ptr(carry_ret),
+                    _lib.ptr(cost_hist), _lib.ptr(ret_hist), _lib.ptr(elite_hist), _lib.ptr(kept_hist), _events(st, I),
+                    _lib.ptr(ws), ws.numel(), _lib.stream_handle(dev)), call.__name__)
     _mark(pev, 1)
     if rec:
         out.update(costs=cost_hist, returns=ret_hist, elites=elite_hist)
@@ -1305,6 +1452,7 @@ class MPPIPlanner(ModelPlanner):
     @staticmethod
     def plan_detailed(initial_state, model, cost, sample_action, horizon, initial_trajectory=None, **kwargs):
         """plan() plus diagnostics: dict(states, actions, mu, sigma[, costs, weights, mu_hist, sigma_hist])."""
+        _noise_refuse(kwargs, "MPPIPlanner")
         st = MPPIPlanner._settings_build(sample_action, horizon, kwargs)
         dev = _device(kwargs)
         rows = None
