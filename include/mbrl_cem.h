@@ -528,7 +528,7 @@ int mbrl_cem_plan_rh_batch(const mbrl_mlp_shape* shape, const void* packed, cons
  * Euclidean norm keep e[t] marginally N(0, 1), so sigma keeps its meaning; the identity is the white draw.
  * Every entry must be finite: the CALLER'S check, as for the sigma rows (Python makes it on the host).
  * H > 64 with a mix is MBRL_EUNSUPPORTED before any launch (the kernels hold the matrix and one tile's normals
- * in LDS; csrc/cem_noise.hip). A NULL mix forwards to the entry without one: the same launches, the same bits.
+ * in LDS; csrc/cem_noise.hip). A NULL mix is the entry without one: the same launches, the same bits.
  *
  * mbrl_sample_actions_mixed: mbrl_sample_actions with the mix (RNG parity, step-by-step equivalents).
  *

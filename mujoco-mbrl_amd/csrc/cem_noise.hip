@@ -20,8 +20,6 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <initializer_list>
-
 #include "mbrl_host.h"
 #include "mbrl_rh_rows.h"
 #include "mbrl_rng.h"
@@ -129,10 +127,6 @@ __global__ void __launch_bounds__(256) noise_sample_kernel(uint64_t seed, int it
 struct InitOps {
     RhInitArgs A;
     int G;
-    __device__ float mu0(size_t i, int f) const {
-        return A.mu_rows && (f & 1) ? fminf(fmaxf(A.mu_rows[i], A.lo), A.hi) : A.init_mu;
-    }
-    __device__ float sg0(size_t i, int f) const { return A.sigma_rows && (f & 2) ? A.sigma_rows[i] : A.init_sigma; }
     __device__ void describe(size_t q, NoisePair& p) const {
         const size_t c = q / G;   // the candidate's Philox index: problem b's candidate n is b N + n
         p.g = (int)(q - c * G);
@@ -147,39 +141,18 @@ struct InitOps {
     __device__ void dist(const NoisePair& p, int t, int d, float& m, float& s) const {
         const int f = rh_flags(A.flags, p.b);
         const size_t i = ((size_t)p.b * A.H + t) * A.a + d;
-        m = mu0(i, f);
-        s = sg0(i, f);
+        m = rh_mu0(A, i, f);
+        s = rh_sg0(A, i, f);
     }
 };
 
 template <bool VEC>
 __global__ void __launch_bounds__(256) noise_init_kernel(const RhInitArgs A, const float* __restrict__ mix, int P) {
     const size_t gid = blockIdx.x * (size_t)blockDim.x + threadIdx.x, gsz = (size_t)gridDim.x * blockDim.x;
-#pragma unroll
-    for (int r = 0; r < 2; ++r)
-        for (size_t i = gid; A.zero.ptr[r] && i < A.zero.words[r]; i += gsz) A.zero.ptr[r][i] = 0u;
-    const int a = A.a, B = A.B;
-    if (A.s0_src) {   // problem b's state to each of its s0_rep rows (a single plan: the one copy)
-        const size_t s = (size_t)A.s, rep = (size_t)A.s0_rep;
-        for (size_t i = gid; i < (size_t)B * rep * s; i += gsz) {
-            const size_t row = i / s;
-            A.s0_dst[i] = A.s0_src[(row / rep) * s + (i - row * s)];
-        }
-    }
-    const InitOps ops{A, (a + 3) >> 2};
-    const size_t Ha = (size_t)A.H * a;
-    for (size_t i = gid; i < (size_t)B * Ha; i += gsz) {
-        const int f = rh_flags(A.flags, (int)(i / Ha));
-        A.mu[i] = ops.mu0(i, f);
-        A.sigma[i] = ops.sg0(i, f);
-    }
-    if (A.kept0) {
-        const size_t per = (size_t)A.Kc * Ha;
-        for (size_t i = gid; i < (size_t)B * per; i += gsz)
-            A.kept0[i] = A.carry_in && (rh_flags(A.flags, (int)(i / per)) & 4) ? A.carry_in[i] : 0.f;
-    }
+    rh_init_prologue(A, gid, gsz);
     if (!A.actions) return;
-    noise_tiles<VEC>(ops, mix, A.seed, 0u, A.H, a, A.lo, A.hi, (size_t)B * A.N * ops.G, P);
+    const InitOps ops{A, (A.a + 3) >> 2};
+    noise_tiles<VEC>(ops, mix, A.seed, 0u, A.H, A.a, A.lo, A.hi, (size_t)A.B * A.N * ops.G, P);
 }
 
 // ---- after the two selections: rh_gather_kernel with the regenerated rows coloured. Pairs [0, B K G): problem
@@ -222,11 +195,7 @@ struct GatherOps {
 template <bool VEC>
 __global__ void __launch_bounds__(256) noise_gather_kernel(const RhGatherArgs A, const float* __restrict__ mix, int P) {
     const size_t gid = blockIdx.x * (size_t)blockDim.x + threadIdx.x, gsz = (size_t)gridDim.x * blockDim.x;
-    if (A.best_returns)
-        for (size_t i = gid; i < (size_t)A.B * A.Kc; i += gsz) {
-            const int64_t n = A.best[i];   // (a candidate index; anything else reads nothing)
-            A.best_returns[i] = (uint64_t)n < (uint64_t)A.N ? A.returns[(i / A.Kc) * A.N + n] : __uint_as_float(0x7FC00000u);
-        }
+    rh_best_returns(A, gid, gsz);
     const GatherOps ops{A, (A.a + 3) >> 2};
     noise_tiles<VEC>(ops, mix, A.seed, (uint32_t)A.iteration, A.H, A.a, A.lo, A.hi,
                      (size_t)A.B * ((size_t)A.K + A.Kc) * ops.G, P);
@@ -256,13 +225,7 @@ struct DrawOps {
 template <bool VEC>
 __global__ void __launch_bounds__(256) noise_draw_kernel(const RhDrawArgs A, const float* __restrict__ mix, int P) {
     const size_t gid = blockIdx.x * (size_t)blockDim.x + threadIdx.x, gsz = (size_t)gridDim.x * blockDim.x;
-    if (A.fin_actions)
-        for (size_t i = gid; i < (size_t)A.B * A.H * A.a; i += gsz) {
-            const float m = A.mu[i];
-            if (A.fin_mu) A.fin_mu[i] = m;
-            if (A.fin_sigma) A.fin_sigma[i] = A.sigma[i];
-            A.fin_actions[i] = fminf(fmaxf(m, A.lo), A.hi);
-        }
+    rh_final_outputs(A, gid, gsz);
     if (!A.actions) return;
     const DrawOps ops{A, (A.a + 3) >> 2};
     noise_tiles<VEC>(ops, mix, A.seed, (uint32_t)A.iteration, A.H, A.a, A.lo, A.hi, (size_t)A.B * A.N * ops.G, P);
@@ -293,12 +256,6 @@ static NoiseLaunch noise_launch(size_t npairs, int H, size_t floor_threads) {
     L.grid = dim3((unsigned)blocks);
     L.lds = ((size_t)((H * H + 3) & ~3) + (size_t)4 * H * L.P) * sizeof(float);
     return L;
-}
-
-static bool aligned16(std::initializer_list<const void*> ps) {
-    for (const void* p : ps)
-        if (reinterpret_cast<uintptr_t>(p) & 15) return false;
-    return true;
 }
 
 template <class T>
@@ -338,22 +295,19 @@ hipError_t launch_noise_init(const RhInitArgs& A, const float* mix, hipStream_t 
     const size_t G = (size_t)(A.a + 3) / 4;
     const size_t others = (size_t)A.B * ((size_t)A.H * A.a * (A.kept0 ? 1 + A.Kc : 1) + (A.s0_src ? (size_t)A.s0_rep * A.s : 0));
     const NoiseLaunch L = noise_launch((size_t)A.B * A.N * G, A.H, others);
-    const bool vec = (A.a & 3) == 0 && aligned16({A.carry_in, A.actions});
-    return launch_noise_kernel(noise_init_kernel<true>, noise_init_kernel<false>, vec, L, stream, A, mix, L.P);
+    return launch_noise_kernel(noise_init_kernel<true>, noise_init_kernel<false>, rh_init_vec(A), L, stream, A, mix, L.P);
 }
 
 hipError_t launch_noise_gather(const RhGatherArgs& A, const float* mix, hipStream_t stream) {
     const size_t G = (size_t)(A.a + 3) / 4;
     const NoiseLaunch L = noise_launch((size_t)A.B * ((size_t)A.K + A.Kc) * G, A.H, (size_t)A.B * A.Kc);
-    const bool vec = (A.a & 3) == 0 && aligned16({A.kept_cur, A.aelite, A.kept_next, A.kept_copy});
-    return launch_noise_kernel(noise_gather_kernel<true>, noise_gather_kernel<false>, vec, L, stream, A, mix, L.P);
+    return launch_noise_kernel(noise_gather_kernel<true>, noise_gather_kernel<false>, rh_gather_vec(A), L, stream, A, mix, L.P);
 }
 
 hipError_t launch_noise_draw(const RhDrawArgs& A, const float* mix, hipStream_t stream) {
     const size_t G = (size_t)(A.a + 3) / 4;
     const NoiseLaunch L = noise_launch(A.actions ? (size_t)A.B * A.N * G : 0, A.H, (size_t)A.B * A.H * A.a);
-    const bool vec = (A.a & 3) == 0 && aligned16({A.kept, A.actions});
-    return launch_noise_kernel(noise_draw_kernel<true>, noise_draw_kernel<false>, vec, L, stream, A, mix, L.P);
+    return launch_noise_kernel(noise_draw_kernel<true>, noise_draw_kernel<false>, rh_draw_vec(A), L, stream, A, mix, L.P);
 }
 
 }  // namespace mbrl

@@ -15,8 +15,6 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <initializer_list>
-
 #include "mbrl_host.h"
 #include "mbrl_rh_rows.h"
 #include "mbrl_rng.h"
@@ -40,34 +38,10 @@ __device__ __forceinline__ void draw4(uint64_t seed, uint32_t n, uint32_t t, uin
 template <bool VEC>
 __global__ void __launch_bounds__(256) rh_init_kernel(const RhInitArgs A) {
     const size_t gid = blockIdx.x * (size_t)blockDim.x + threadIdx.x, gsz = (size_t)gridDim.x * blockDim.x;
-#pragma unroll
-    for (int r = 0; r < 2; ++r)
-        for (size_t i = gid; A.zero.ptr[r] && i < A.zero.words[r]; i += gsz) A.zero.ptr[r][i] = 0u;
-    const int a = A.a, B = A.B, N = A.N;
-    if (A.s0_src) {   // problem b's state to each of its s0_rep rows (a single plan: the one copy)
-        const size_t s = (size_t)A.s, rep = (size_t)A.s0_rep;
-        for (size_t i = gid; i < (size_t)B * rep * s; i += gsz) {
-            const size_t row = i / s;
-            A.s0_dst[i] = A.s0_src[(row / rep) * s + (i - row * s)];
-        }
-    }
-    const size_t Ha = (size_t)A.H * a;
-    // the initial distribution: what the draws below use, whether or not this thread also stores it
-    // (i: an index into [B][H][a], f: its problem's flags)
-    auto mu0 = [&](size_t i, int f) { return A.mu_rows && (f & 1) ? fminf(fmaxf(A.mu_rows[i], A.lo), A.hi) : A.init_mu; };
-    auto sg0 = [&](size_t i, int f) { return A.sigma_rows && (f & 2) ? A.sigma_rows[i] : A.init_sigma; };
-    for (size_t i = gid; i < (size_t)B * Ha; i += gsz) {
-        const int f = rh_flags(A.flags, (int)(i / Ha));
-        A.mu[i] = mu0(i, f);
-        A.sigma[i] = sg0(i, f);
-    }
-    if (A.kept0) {
-        const size_t per = (size_t)A.Kc * Ha;
-        for (size_t i = gid; i < (size_t)B * per; i += gsz)
-            A.kept0[i] = A.carry_in && (rh_flags(A.flags, (int)(i / per)) & 4) ? A.carry_in[i] : 0.f;
-    }
+    rh_init_prologue(A, gid, gsz);
     if (!A.actions) return;
-    const int G = (a + 3) >> 2;
+    const int a = A.a, B = A.B, N = A.N, G = (a + 3) >> 2;
+    const size_t Ha = (size_t)A.H * a;
     const size_t BN = (size_t)B * N, total = (size_t)A.H * BN * G;
     for (size_t i = gid; i < total; i += gsz) {
         const int g = (int)(i % G), t = (int)(i / G / BN);
@@ -83,7 +57,7 @@ __global__ void __launch_bounds__(256) rh_init_kernel(const RhInitArgs A) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const int d = 4 * g + j;
-                v[j] = d < a ? cem_action(mu0(row + d, f), sg0(row + d, f), z[j], A.lo, A.hi) : 0.f;
+                v[j] = d < a ? cem_action(rh_mu0(A, row + d, f), rh_sg0(A, row + d, f), z[j], A.lo, A.hi) : 0.f;
             }
         }
         store4<VEC>(A.actions + ((size_t)t * BN + c) * a, g, a, v);
@@ -94,11 +68,7 @@ template <bool VEC>
 __global__ void __launch_bounds__(256) rh_gather_kernel(const RhGatherArgs A) {
     const size_t gid = blockIdx.x * (size_t)blockDim.x + threadIdx.x, gsz = (size_t)gridDim.x * blockDim.x;
     const int a = A.a, H = A.H, K = A.K, Kc = A.Kc, N = A.N, B = A.B, G = (a + 3) >> 2;
-    if (A.best_returns)
-        for (size_t i = gid; i < (size_t)B * Kc; i += gsz) {
-            const int64_t n = A.best[i];   // (a candidate index; anything else reads nothing)
-            A.best_returns[i] = (uint64_t)n < (uint64_t)N ? A.returns[(i / Kc) * N + n] : __uint_as_float(0x7FC00000u);
-        }
+    rh_best_returns(A, gid, gsz);
     // threads [0, B H K G): problem b's elite e's step t in (b, t, e, g) order, aelite's; then [0, B Kc H G):
     // best row j's step t in (b, j, t, g) order, the kept rows'
     const size_t n_el = (size_t)B * H * K * G, total = n_el + (size_t)B * Kc * H * G;
@@ -138,13 +108,7 @@ template <bool VEC>
 __global__ void __launch_bounds__(256) rh_draw_kernel(const RhDrawArgs A) {
     const size_t gid = blockIdx.x * (size_t)blockDim.x + threadIdx.x, gsz = (size_t)gridDim.x * blockDim.x;
     const int a = A.a, H = A.H, N = A.N, B = A.B, G = (a + 3) >> 2;
-    if (A.fin_actions)
-        for (size_t i = gid; i < (size_t)B * H * a; i += gsz) {
-            const float m = A.mu[i];
-            if (A.fin_mu) A.fin_mu[i] = m;
-            if (A.fin_sigma) A.fin_sigma[i] = A.sigma[i];
-            A.fin_actions[i] = fminf(fmaxf(m, A.lo), A.hi);
-        }
+    rh_final_outputs(A, gid, gsz);
     if (!A.actions) return;
     const size_t BN = (size_t)B * N, total = (size_t)H * BN * G;
     for (size_t i = gid; i < total; i += gsz) {
@@ -167,26 +131,18 @@ static dim3 rh_grid(size_t threads) {
     return dim3((unsigned)(b < 1 ? 1 : (b < 8192 ? b : 8192)));
 }
 
-static bool aligned16(std::initializer_list<const void*> ps) {
-    for (const void* p : ps)
-        if (reinterpret_cast<uintptr_t>(p) & 15) return false;
-    return true;
-}
-
 hipError_t launch_rh_init(const RhInitArgs& A, hipStream_t stream) {
     const size_t G = (size_t)(A.a + 3) / 4;
     const size_t threads = (size_t)A.B * (A.actions ? (size_t)A.H * A.N * G : (size_t)A.H * A.a);
-    const bool vec = (A.a & 3) == 0 && aligned16({A.carry_in, A.actions});
-    if (vec) hipLaunchKernelGGL(rh_init_kernel<true>, rh_grid(threads), dim3(256), 0, stream, A);
+    if (rh_init_vec(A)) hipLaunchKernelGGL(rh_init_kernel<true>, rh_grid(threads), dim3(256), 0, stream, A);
     else hipLaunchKernelGGL(rh_init_kernel<false>, rh_grid(threads), dim3(256), 0, stream, A);
     return hipGetLastError();
 }
 
 hipError_t launch_rh_gather(const RhGatherArgs& A, hipStream_t stream) {
     const size_t G = (size_t)(A.a + 3) / 4;
-    const bool vec = (A.a & 3) == 0 && aligned16({A.kept_cur, A.aelite, A.kept_next, A.kept_copy});
     const dim3 grid = rh_grid((size_t)A.B * A.H * ((size_t)A.K + A.Kc) * G);
-    if (vec) hipLaunchKernelGGL(rh_gather_kernel<true>, grid, dim3(256), 0, stream, A);
+    if (rh_gather_vec(A)) hipLaunchKernelGGL(rh_gather_kernel<true>, grid, dim3(256), 0, stream, A);
     else hipLaunchKernelGGL(rh_gather_kernel<false>, grid, dim3(256), 0, stream, A);
     return hipGetLastError();
 }
@@ -194,8 +150,7 @@ hipError_t launch_rh_gather(const RhGatherArgs& A, hipStream_t stream) {
 hipError_t launch_rh_draw(const RhDrawArgs& A, hipStream_t stream) {
     const size_t G = (size_t)(A.a + 3) / 4;
     const size_t threads = (size_t)A.B * (A.actions ? (size_t)A.H * A.N * G : (size_t)A.H * A.a);
-    const bool vec = (A.a & 3) == 0 && aligned16({A.kept, A.actions});
-    if (vec) hipLaunchKernelGGL(rh_draw_kernel<true>, rh_grid(threads), dim3(256), 0, stream, A);
+    if (rh_draw_vec(A)) hipLaunchKernelGGL(rh_draw_kernel<true>, rh_grid(threads), dim3(256), 0, stream, A);
     else hipLaunchKernelGGL(rh_draw_kernel<false>, rh_grid(threads), dim3(256), 0, stream, A);
     return hipGetLastError();
 }

@@ -574,179 +574,6 @@ int mbrl_cem_plan(const mbrl_mlp_shape* shape, const void* packed, const mbrl_no
                         cost_hist, returns_hist, elite_hist, rollout_events, w, stream);
 }
 
-// ---- receding-horizon CEM (include/mbrl_cem.h mbrl_cem_plan_rh; kernels in cem_rh.hip): mbrl_cem_plan's
-// workspace first, then what kept rows need -- the two kept sets [Kc][H][a] (iteration i reads one and
-// writes the other), the best indices and the returns the carry's are read from.
-struct RhWs {
-    PlanWs plan;
-    float *kept[2], *rets;
-    int64_t* best;
-    size_t bytes;
-};
-
-// mixed (mbrl_cem_plan_rh_mixed): the returns also with keep == 0, where that plan selects unfused too.
-static RhWs rh_ws(const Geometry& g, const mbrl_cem_rh_params* rp, void* base, bool mixed = false) {
-    RhWs w{};
-    w.plan = plan_ws(g, &rp->cem, base);
-    WsCursor c(base);
-    c.off = w.plan.bytes;
-    const size_t kb = (size_t)rp->keep * rp->cem.H * g.a * 4;
-    w.kept[0] = c.take<float>(kb); w.kept[1] = c.take<float>(kb);
-    w.best = c.take<int64_t>((size_t)rp->keep * 8);
-    w.rets = c.take<float>(rp->keep || mixed ? (size_t)rp->cem.N * 4 : 0);
-    w.bytes = c.off;
-    return w;
-}
-
-static int rh_params_check(const mbrl_cem_rh_params* rp) {
-    if (!rp) return fail(MBRL_EINVAL, "cem_plan_rh: params is NULL");
-    if (int rc = cem_params_check(&rp->cem)) return rc;
-    if (rp->keep < 0 || rp->keep > rp->cem.K)
-        return fail(MBRL_EINVAL, "cem_plan_rh: keep=%d outside [0, K=%d]", rp->keep, rp->cem.K);
-    return MBRL_OK;
-}
-
-size_t mbrl_cem_rh_workspace_bytes(const mbrl_mlp_shape* shape, const mbrl_cem_rh_params* params) {
-    Geometry g;
-    if (shape_geometry(shape, &g) != MBRL_OK || rh_params_check(params) != MBRL_OK) return 0;
-    return rh_ws(g, params, nullptr).bytes;
-}
-
-// keep > 0: every iteration is the rollout of the proposals in w.plan.actions, then five small launches --
-// the K elites, the Kc best (the same returns selected twice), the gather of both sets' action rows, the
-// refit over the gathered elites, and the next proposals (kept rows scattered into slots [0, Kc), the rest
-// drawn) or, on the last iteration, the plan outputs. kept_i lives in kept_hist's row i where the caller
-// records, else in the workspace's two buffers; iteration 0 reads carry_in where it is.
-// mix (mbrl_cem_plan_rh_mixed; NULL: none): the same loop for any keep >= 0 with the first launch, the gather
-// and the draw coloured (cem_noise.hip); the Kc selection runs only when Kc > 0.
-static int cem_plan_rh_kept(const Geometry& g, const void* packed, const mbrl_norm* norm, const mbrl_cost* cost,
-                            const float* s0_in, const mbrl_cem_rh_params* rp, const float* mu_rows,
-                            const float* sigma_rows, const float* carry_in, float* mu, float* sigma,
-                            float* actions_out, float* states_out, float* carry_out, float* carry_returns_out,
-                            float* cost_hist, float* returns_hist, int64_t* elite_hist, float* kept_hist,
-                            mbrl_event_t* rollout_events, const RhWs& rw, hipStream_t stream,
-                            const float* mix = nullptr) {
-    const mbrl_cem_params* p = &rp->cem;
-    const PlanWs& w = rw.plan;
-    const int Kc = rp->keep;
-    const size_t kept_floats = (size_t)Kc * p->H * g.a;
-    auto kept_at = [&](int i) { return kept_hist ? kept_hist + (size_t)i * kept_floats : rw.kept[i & 1]; };
-    int rc;
-    const InitZero z = plan_zero(g, p->N, w.pair, w.traj);
-    {
-        RhInitArgs A{};
-        A.seed = p->seed; A.init_mu = p->init_mu; A.init_sigma = p->init_sigma; A.lo = p->lo; A.hi = p->hi;
-        A.H = p->H; A.a = g.a; A.N = p->N; A.Kc = Kc; A.s = g.s; A.B = 1; A.s0_rep = 1;
-        A.mu_rows = mu_rows; A.sigma_rows = sigma_rows; A.carry_in = carry_in;
-        A.mu = w.mu[0]; A.sigma = w.sigma[0]; A.actions = w.actions; A.kept0 = kept_hist;
-        A.s0_src = s0_in; A.s0_dst = w.s0; A.zero = z;
-        if ((rc = hip_check(mix ? launch_noise_init(A, mix, stream) : launch_rh_init(A, stream), "init launch"))) return rc;
-    }
-    unsigned pair_epoch = 0;
-    const float* s0 = w.s0;   // the workspace copy (s0_in may be mapped host memory)
-    int cur = 0;
-    for (int it = 0; it < p->iterations; ++it) {
-        const bool last = it + 1 == p->iterations;
-        float* costs = cost_hist ? cost_hist + (size_t)it * g.E * p->N : w.costs;
-        int64_t* elites = elite_hist ? elite_hist + (size_t)it * p->K : w.elites;
-        float* rets = returns_hist ? returns_hist + (size_t)it * p->N : rw.rets;
-        if ((rc = record_rollout_event(rollout_events, 2 * it, stream))) return rc;
-        rc = rollout_impl(g, packed, norm, cost, s0, 0, w.actions, nullptr, p->N, p->H, 0, costs, w.actions, nullptr,
-                          stream, pair_area_bytes(g, p->N) ? w.pair : nullptr, z.ptr[0] ? &pair_epoch : nullptr);
-        if (rc) return rc;
-        if ((rc = record_rollout_event(rollout_events, 2 * it + 1, stream))) return rc;
-        const size_t keys_bytes = align256((size_t)p->N * 4);
-        if ((rc = select_impl(costs, g.E, p->N, p->K, MBRL_NAN_LAST, elites, rets, w.keys, keys_bytes, stream))) return rc;
-        if (Kc && (rc = select_impl(costs, g.E, p->N, Kc, MBRL_NAN_LAST, rw.best, nullptr, w.keys, keys_bytes, stream)))
-            return rc;
-        RhGatherArgs G{};
-        G.seed = p->seed; G.iteration = it; G.N = p->N; G.H = p->H; G.a = g.a; G.K = p->K; G.Kc = Kc; G.B = 1;
-        G.from_kept = it > 0 || carry_in; G.lo = p->lo; G.hi = p->hi;
-        G.mu = w.mu[cur]; G.sigma = w.sigma[cur]; G.kept_cur = it == 0 ? carry_in : kept_at(it); G.returns = rets;
-        G.elites = elites; G.best = rw.best; G.aelite = w.aelite; G.kept_next = kept_at(it + 1);
-        G.kept_copy = last ? carry_out : nullptr; G.best_returns = last ? carry_returns_out : nullptr;
-        if ((rc = hip_check(mix ? launch_noise_gather(G, mix, stream) : launch_rh_gather(G, stream), "gather launch")))
-            return rc;
-        rc = refit_staged_impl(w.aelite, p->H, g.a, p->K, p->alpha, w.mu[cur], w.sigma[cur], w.mu[cur ^ 1],
-                               w.sigma[cur ^ 1], stream);
-        if (rc) return rc;
-        RhDrawArgs D{};
-        D.seed = p->seed; D.iteration = it + 1; D.H = p->H; D.a = g.a; D.N = p->N; D.Kc = Kc; D.B = 1;
-        D.lo = p->lo; D.hi = p->hi;
-        D.mu = w.mu[cur ^ 1]; D.sigma = w.sigma[cur ^ 1]; D.kept = kept_at(it + 1);
-        D.actions = last ? nullptr : w.actions;
-        D.fin_mu = last ? mu : nullptr; D.fin_sigma = last ? sigma : nullptr; D.fin_actions = last ? actions_out : nullptr;
-        if ((rc = hip_check(mix ? launch_noise_draw(D, mix, stream) : launch_rh_draw(D, stream), "draw launch"))) return rc;
-        cur ^= 1;
-    }
-    rc = final_trajectory(g, packed, norm, s0, actions_out, p->H, states_out, w.states, w.traj, stream,
-                          z.ptr[1] != nullptr);
-    if (rc) return rc;
-    return hip_check(hipGetLastError(), "plan launch");
-}
-
-int mbrl_cem_plan_rh(const mbrl_mlp_shape* shape, const void* packed, const mbrl_norm* norm, const mbrl_cost* cost,
-                     const float* s0_in, const mbrl_cem_rh_params* rp, const float* init_mu_rows,
-                     const float* init_sigma_rows, const float* carry_in, float* mu, float* sigma, float* actions_out,
-                     float* states_out, float* carry_out, float* carry_returns_out, float* cost_hist,
-                     float* returns_hist, int64_t* elite_hist, float* kept_hist, mbrl_event_t* rollout_events,
-                     void* workspace, size_t ws_bytes, mbrl_stream_t stream_) {
-    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-    Geometry g;
-    int rc = shape_geometry(shape, &g);
-    if (rc) return rc;
-    if ((rc = rh_params_check(rp))) return rc;
-    if (carry_in && rp->keep == 0) return fail(MBRL_EINVAL, "cem_plan_rh: carry_in given with keep == 0");
-    if (!packed || !actions_out || !states_out || !workspace)
-        return fail(MBRL_EINVAL, "cem_plan_rh: packed/actions_out/states_out/workspace NULL");
-    if (!s0_in) return fail(MBRL_EINVAL, "cem_plan_rh: s0 is NULL");
-    const RhWs w = rh_ws(g, rp, workspace);
-    if (ws_bytes < w.bytes) return fail(MBRL_EINVAL, "cem_plan_rh: workspace %zu < %zu", ws_bytes, w.bytes);
-    if (rp->cem.N > 32768) return fail(MBRL_EUNSUPPORTED, "cem_plan_rh: N=%d exceeds 32768", rp->cem.N);
-    if ((rc = pair_forced_check(g, rp->cem.N))) return rc;
-    if (rp->keep == 0)
-        return cem_plan_run(g, packed, norm, cost, s0_in, &rp->cem, init_mu_rows, init_sigma_rows, mu, sigma,
-                            actions_out, states_out, cost_hist, returns_hist, elite_hist, rollout_events, w.plan, stream);
-    if ((rc = refit_staged_check(g.a, rp->cem.K))) return rc;
-    return cem_plan_rh_kept(g, packed, norm, cost, s0_in, rp, init_mu_rows, init_sigma_rows, carry_in, mu, sigma,
-                            actions_out, states_out, carry_out, carry_returns_out, cost_hist, returns_hist, elite_hist,
-                            kept_hist, rollout_events, w, stream);
-}
-
-static size_t mixed_ws_bytes(const Geometry& g, const mbrl_cem_rh_params* rp, int B);
-
-int mbrl_cem_plan_rh_mixed(const mbrl_mlp_shape* shape, const void* packed, const mbrl_norm* norm,
-                           const mbrl_cost* cost, const float* s0_in, const mbrl_cem_rh_params* rp,
-                           const float* init_mu_rows, const float* init_sigma_rows, const float* carry_in,
-                           const float* noise_mix, float* mu, float* sigma, float* actions_out, float* states_out,
-                           float* carry_out, float* carry_returns_out, float* cost_hist, float* returns_hist,
-                           int64_t* elite_hist, float* kept_hist, mbrl_event_t* rollout_events, void* workspace,
-                           size_t ws_bytes, mbrl_stream_t stream_) {
-    if (!noise_mix)
-        return mbrl_cem_plan_rh(shape, packed, norm, cost, s0_in, rp, init_mu_rows, init_sigma_rows, carry_in, mu, sigma,
-                                actions_out, states_out, carry_out, carry_returns_out, cost_hist, returns_hist,
-                                elite_hist, kept_hist, rollout_events, workspace, ws_bytes, stream_);
-    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-    Geometry g;
-    int rc = shape_geometry(shape, &g);
-    if (rc) return rc;
-    if ((rc = rh_params_check(rp))) return rc;
-    if (carry_in && rp->keep == 0) return fail(MBRL_EINVAL, "cem_plan_rh_mixed: carry_in given with keep == 0");
-    if (!packed || !actions_out || !states_out || !workspace)
-        return fail(MBRL_EINVAL, "cem_plan_rh_mixed: packed/actions_out/states_out/workspace NULL");
-    if (!s0_in) return fail(MBRL_EINVAL, "cem_plan_rh_mixed: s0 is NULL");
-    if ((rc = noise_check(rp->cem.H))) return rc;
-    const RhWs w = rh_ws(g, rp, workspace, true);
-    if (const size_t need = mixed_ws_bytes(g, rp, 1); ws_bytes < need)
-        return fail(MBRL_EINVAL, "cem_plan_rh_mixed: workspace %zu < %zu", ws_bytes, need);
-    if (rp->cem.N > 32768) return fail(MBRL_EUNSUPPORTED, "cem_plan_rh_mixed: N=%d exceeds 32768", rp->cem.N);
-    if ((rc = pair_forced_check(g, rp->cem.N))) return rc;
-    if ((rc = refit_staged_check(g.a, rp->cem.K))) return rc;
-    return cem_plan_rh_kept(g, packed, norm, cost, s0_in, rp, init_mu_rows, init_sigma_rows, carry_in, mu, sigma,
-                            actions_out, states_out, carry_out, carry_returns_out, cost_hist, returns_hist, elite_hist,
-                            kept_hist, rollout_events, w, stream, noise_mix);
-}
-
 // Workspace layout for mbrl_mppi_plan (PlanWs without the selection's and the elites' scratch).
 struct MppiWs {
     float *costs, *mu[2], *sigma[2], *states, *actions[2], *s0;
@@ -983,9 +810,32 @@ int mbrl_cem_plan_batch(const mbrl_mlp_shape* shape, const void* packed, const m
                          nullptr, nullptr, nullptr, w, stream);
 }
 
-// ---- batched receding-horizon CEM (include/mbrl_cem.h mbrl_cem_plan_rh_batch): mbrl_cem_plan_batch's
-// workspace first, then what kept rows need for B problems -- the staged elites' actions [B][H][K][a], the
-// two kept sets [B][Kc][H][a], the best indices [B][Kc] and the returns [B][N].
+// ---- receding-horizon CEM, single and batched, white and mixed (include/mbrl_cem.h mbrl_cem_plan_rh,
+// mbrl_cem_plan_rh_batch and their _mixed forms; kernels in cem_rh.hip and cem_noise.hip). The workspaces:
+// mbrl_cem_plan's (mbrl_cem_plan_batch's) first, then what kept rows need -- the two kept sets [B][Kc][H][a]
+// (iteration i reads one and writes the other), the best indices [B][Kc], the returns [B][N] the carry's are
+// read from and, batched, the staged elites' actions [B][H][K][a] (the single plan stages in PlanWs.aelite).
+struct RhWs {
+    PlanWs plan;
+    float *kept[2], *rets;
+    int64_t* best;
+    size_t bytes;
+};
+
+// mixed: the returns also with keep == 0, where that plan selects unfused too.
+static RhWs rh_ws(const Geometry& g, const mbrl_cem_rh_params* rp, void* base, bool mixed = false) {
+    RhWs w{};
+    w.plan = plan_ws(g, &rp->cem, base);
+    WsCursor c(base);
+    c.off = w.plan.bytes;
+    const size_t kb = (size_t)rp->keep * rp->cem.H * g.a * 4;
+    w.kept[0] = c.take<float>(kb); w.kept[1] = c.take<float>(kb);
+    w.best = c.take<int64_t>((size_t)rp->keep * 8);
+    w.rets = c.take<float>(rp->keep || mixed ? (size_t)rp->cem.N * 4 : 0);
+    w.bytes = c.off;
+    return w;
+}
+
 struct RhBatchWs {
     BatchWs plan;
     float *aelite, *kept[2], *rets;
@@ -993,7 +843,7 @@ struct RhBatchWs {
     size_t bytes;
 };
 
-// mixed (mbrl_cem_plan_rh_batch_mixed): the staged elites and the returns also with keep == 0.
+// mixed: the staged elites and the returns also with keep == 0.
 static RhBatchWs rh_batch_ws(const Geometry& g, const mbrl_cem_rh_params* rp, int B, void* base, bool mixed = false) {
     RhBatchWs w{};
     const mbrl_cem_params* p = &rp->cem;
@@ -1009,107 +859,6 @@ static RhBatchWs rh_batch_ws(const Geometry& g, const mbrl_cem_rh_params* rp, in
     return w;
 }
 
-size_t mbrl_cem_rh_batch_workspace_bytes(const mbrl_mlp_shape* shape, const mbrl_cem_rh_params* params, int32_t B) {
-    Geometry g;
-    if (shape_geometry(shape, &g) != MBRL_OK || rh_params_check(params) != MBRL_OK || B < 1) return 0;
-    return rh_batch_ws(g, params, B, nullptr).bytes;
-}
-
-// keep > 0, B problems: cem_plan_rh_kept's launches with a problem dimension -- per iteration the one rollout
-// of the B N proposals, then the same five small launches, each over all B problems (segmented selections,
-// grid (H, B) refit); the first launch also expands s0 to the rollout's per-candidate start states.
-// Iteration 0 honours the problems' input flags; from iteration 1 on every problem has a kept set.
-// mix: as cem_plan_rh_kept's.
-static int cem_plan_rh_batch_kept(const Geometry& g, const void* packed, const mbrl_norm* norm, const mbrl_cost* cost,
-                                  const float* s0, int B, const mbrl_cem_rh_params* rp, const float* mu_rows,
-                                  const float* sigma_rows, const float* carry_in, const int32_t* flags, float* mu,
-                                  float* sigma, float* actions_out, float* states_out, float* carry_out,
-                                  float* carry_returns_out, float* cost_hist, float* returns_hist, int64_t* elite_hist,
-                                  float* kept_hist, const RhBatchWs& rw, hipStream_t stream,
-                                  const float* mix = nullptr) {
-    const mbrl_cem_params* p = &rp->cem;
-    const BatchWs& w = rw.plan;
-    const int Kc = rp->keep, BN = B * p->N;
-    const size_t kept_floats = (size_t)B * Kc * p->H * g.a;
-    auto kept_at = [&](int i) { return kept_hist ? kept_hist + (size_t)i * kept_floats : rw.kept[i & 1]; };
-    int rc;
-    {
-        RhInitArgs A{};
-        A.seed = p->seed; A.init_mu = p->init_mu; A.init_sigma = p->init_sigma; A.lo = p->lo; A.hi = p->hi;
-        A.H = p->H; A.a = g.a; A.N = p->N; A.Kc = Kc; A.s = g.s; A.B = B; A.s0_rep = p->N;
-        A.mu_rows = mu_rows; A.sigma_rows = sigma_rows; A.carry_in = carry_in; A.flags = flags;
-        A.mu = w.mu[0]; A.sigma = w.sigma[0]; A.actions = w.actions; A.kept0 = kept_hist;
-        A.s0_src = s0; A.s0_dst = w.s0x;
-        if ((rc = hip_check(mix ? launch_noise_init(A, mix, stream) : launch_rh_init(A, stream), "init launch"))) return rc;
-    }
-    const size_t keys_bytes = align256((size_t)BN * 4);
-    int cur = 0;
-    for (int it = 0; it < p->iterations; ++it) {
-        const bool last = it + 1 == p->iterations;
-        float* costs = cost_hist ? cost_hist + (size_t)it * g.E * BN : w.costs;
-        int64_t* elites = elite_hist ? elite_hist + (size_t)it * B * p->K : w.elites;
-        float* rets = returns_hist ? returns_hist + (size_t)it * BN : rw.rets;
-        rc = rollout_impl(g, packed, norm, cost, w.s0x, 1, w.actions, nullptr, BN, p->H, 0, costs, nullptr, nullptr,
-                          stream);
-        if (rc) return rc;
-        if ((rc = select_impl(costs, g.E, p->N, p->K, MBRL_NAN_LAST, elites, rets, w.keys, keys_bytes, stream, B)))
-            return rc;
-        if (Kc && (rc = select_impl(costs, g.E, p->N, Kc, MBRL_NAN_LAST, rw.best, nullptr, w.keys, keys_bytes, stream, B)))
-            return rc;
-        RhGatherArgs G{};
-        G.seed = p->seed; G.iteration = it; G.N = p->N; G.H = p->H; G.a = g.a; G.K = p->K; G.Kc = Kc; G.B = B;
-        G.from_kept = it > 0 || carry_in; G.flags = it == 0 ? flags : nullptr; G.lo = p->lo; G.hi = p->hi;
-        G.mu = w.mu[cur]; G.sigma = w.sigma[cur]; G.kept_cur = it == 0 ? carry_in : kept_at(it); G.returns = rets;
-        G.elites = elites; G.best = rw.best; G.aelite = rw.aelite; G.kept_next = kept_at(it + 1);
-        G.kept_copy = last ? carry_out : nullptr; G.best_returns = last ? carry_returns_out : nullptr;
-        if ((rc = hip_check(mix ? launch_noise_gather(G, mix, stream) : launch_rh_gather(G, stream), "gather launch")))
-            return rc;
-        rc = refit_staged_impl(rw.aelite, p->H, g.a, p->K, p->alpha, w.mu[cur], w.sigma[cur], w.mu[cur ^ 1],
-                               w.sigma[cur ^ 1], stream, B);
-        if (rc) return rc;
-        RhDrawArgs D{};
-        D.seed = p->seed; D.iteration = it + 1; D.H = p->H; D.a = g.a; D.N = p->N; D.Kc = Kc; D.B = B;
-        D.lo = p->lo; D.hi = p->hi;
-        D.mu = w.mu[cur ^ 1]; D.sigma = w.sigma[cur ^ 1]; D.kept = kept_at(it + 1);
-        D.actions = last ? nullptr : w.actions;
-        D.fin_mu = last ? mu : nullptr; D.fin_sigma = last ? sigma : nullptr; D.fin_actions = last ? actions_out : nullptr;
-        if ((rc = hip_check(mix ? launch_noise_draw(D, mix, stream) : launch_rh_draw(D, stream), "draw launch"))) return rc;
-        cur ^= 1;
-    }
-    return batch_final_trajectories(g, packed, norm, s0, B, p->H, actions_out, states_out, w, stream);
-}
-
-int mbrl_cem_plan_rh_batch(const mbrl_mlp_shape* shape, const void* packed, const mbrl_norm* norm,
-                           const mbrl_cost* cost, const float* s0, int32_t B, const mbrl_cem_rh_params* rp,
-                           const float* init_mu_rows, const float* init_sigma_rows, const float* carry_in,
-                           const int32_t* input_flags, float* mu, float* sigma, float* actions_out, float* states_out,
-                           float* carry_out, float* carry_returns_out, float* cost_hist, float* returns_hist,
-                           int64_t* elite_hist, float* kept_hist, void* workspace, size_t ws_bytes,
-                           mbrl_stream_t stream_) {
-    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-    Geometry g;
-    int rc = shape_geometry(shape, &g);
-    if (rc) return rc;
-    if (B < 1) return fail(MBRL_EINVAL, "cem_plan_rh_batch: B=%d", B);
-    if ((rc = rh_params_check(rp))) return rc;
-    if (carry_in && rp->keep == 0) return fail(MBRL_EINVAL, "cem_plan_rh_batch: carry_in given with keep == 0");
-    if (!packed || !s0 || !actions_out || !states_out || !workspace)
-        return fail(MBRL_EINVAL, "cem_plan_rh_batch: packed/s0/actions_out/states_out/workspace NULL");
-    if (rp->cem.N > 32768) return fail(MBRL_EUNSUPPORTED, "cem_plan_rh_batch: N=%d exceeds 32768", rp->cem.N);
-    if ((rc = batch_size_check(B, &rp->cem))) return rc;
-    // (the selections run one workgroup per problem, the staged refit a (H, B) grid)
-    if (rp->keep > 0 && B > 65535) return fail(MBRL_EUNSUPPORTED, "cem_plan_rh_batch: B=%d exceeds 65535", B);
-    if (rp->keep > 0 && (rc = refit_staged_check(g.a, rp->cem.K))) return rc;
-    const RhBatchWs w = rh_batch_ws(g, rp, B, workspace);
-    if (ws_bytes < w.bytes) return fail(MBRL_EWORKSPACE, "cem_plan_rh_batch: workspace %zu < %zu", ws_bytes, w.bytes);
-    if (rp->keep == 0)
-        return cem_batch_run(g, packed, norm, cost, s0, B, &rp->cem, init_mu_rows, init_sigma_rows, input_flags, mu,
-                             sigma, actions_out, states_out, cost_hist, returns_hist, elite_hist, w.plan, stream);
-    return cem_plan_rh_batch_kept(g, packed, norm, cost, s0, B, rp, init_mu_rows, init_sigma_rows, carry_in,
-                                  input_flags, mu, sigma, actions_out, states_out, carry_out, carry_returns_out,
-                                  cost_hist, returns_hist, elite_hist, kept_hist, w, stream);
-}
-
 // What mbrl_cem_rh_mixed_workspace_bytes answers and both mixed entries demand: the batched layout, and for
 // B == 1 the larger of it and the single plan's (one query serves either entry).
 static size_t mixed_ws_bytes(const Geometry& g, const mbrl_cem_rh_params* rp, int B) {
@@ -1119,11 +868,250 @@ static size_t mixed_ws_bytes(const Geometry& g, const mbrl_cem_rh_params* rp, in
     return single > batch ? single : batch;
 }
 
+static int rh_params_check(const mbrl_cem_rh_params* rp) {
+    if (!rp) return fail(MBRL_EINVAL, "cem_plan_rh: params is NULL");
+    if (int rc = cem_params_check(&rp->cem)) return rc;
+    if (rp->keep < 0 || rp->keep > rp->cem.K)
+        return fail(MBRL_EINVAL, "cem_plan_rh: keep=%d outside [0, K=%d]", rp->keep, rp->cem.K);
+    return MBRL_OK;
+}
+
+size_t mbrl_cem_rh_workspace_bytes(const mbrl_mlp_shape* shape, const mbrl_cem_rh_params* params) {
+    Geometry g;
+    if (shape_geometry(shape, &g) != MBRL_OK || rh_params_check(params) != MBRL_OK) return 0;
+    return rh_ws(g, params, nullptr).bytes;
+}
+
+size_t mbrl_cem_rh_batch_workspace_bytes(const mbrl_mlp_shape* shape, const mbrl_cem_rh_params* params, int32_t B) {
+    Geometry g;
+    if (shape_geometry(shape, &g) != MBRL_OK || rh_params_check(params) != MBRL_OK || B < 1) return 0;
+    return rh_batch_ws(g, params, B, nullptr).bytes;
+}
+
 size_t mbrl_cem_rh_mixed_workspace_bytes(const mbrl_mlp_shape* shape, const mbrl_cem_rh_params* params, int32_t B) {
     Geometry g;
     if (shape_geometry(shape, &g) != MBRL_OK || rh_params_check(params) != MBRL_OK || B < 1) return 0;
     if (params->cem.H > NOISE_MAX_H) return 0;
     return mixed_ws_bytes(g, params, B);
+}
+
+// One receding-horizon entry's arguments. The single entries: B = 1, no flags; the batched ones: no events;
+// the white ones (and a mixed one called without a mix): mix NULL.
+struct RhCall {
+    const char* name;   // the entry, for the messages
+    bool batched;       // mbrl_cem_plan_rh_batch's layouts, and s0 checked with the other pointers
+    const mbrl_mlp_shape* shape;
+    const void* packed;
+    const mbrl_norm* norm;
+    const mbrl_cost* cost;
+    const float* s0;
+    int B;
+    const mbrl_cem_rh_params* rp;
+    const float *mu_rows, *sigma_rows, *carry_in;
+    const int32_t* flags;
+    const float* mix;
+    float *mu, *sigma, *actions_out, *states_out, *carry_out, *carry_returns_out, *cost_hist, *returns_hist;
+    int64_t* elite_hist;
+    float* kept_hist;
+    mbrl_event_t* events;
+    void* workspace;
+    size_t ws_bytes;
+    mbrl_stream_t stream;
+};
+
+// Every refusal of the four entries, before any launch, in this order: the shape, B, the parameters, a carry
+// without kept rows, NULL arguments, the mix's horizon, N, B N, then -- where the plan runs the kept-rows loop
+// (keep > 0 or a mix) -- B (the selections run one workgroup per problem, the staged refit a (H, B) grid) and
+// the staged refit's K x a, the workspace (the single entries answer MBRL_EINVAL, the batched ones
+// MBRL_EWORKSPACE) and, for the single plan, a forced pair kernel that does not apply. On MBRL_OK the entry's
+// workspace is carved: *single or *batch.
+static int rh_entry_check(const RhCall& c, Geometry* g, RhWs* single, RhBatchWs* batch) {
+    int rc = shape_geometry(c.shape, g);
+    if (rc) return rc;
+    if (c.B < 1) return fail(MBRL_EINVAL, "%s: B=%d", c.name, c.B);
+    if ((rc = rh_params_check(c.rp))) return rc;
+    const mbrl_cem_params* p = &c.rp->cem;
+    const bool kept_loop = c.rp->keep > 0 || c.mix;
+    if (c.carry_in && c.rp->keep == 0) return fail(MBRL_EINVAL, "%s: carry_in given with keep == 0", c.name);
+    if (!c.packed || (c.batched && !c.s0) || !c.actions_out || !c.states_out || !c.workspace)
+        return fail(MBRL_EINVAL, "%s: packed/%sactions_out/states_out/workspace NULL", c.name, c.batched ? "s0/" : "");
+    if (!c.s0) return fail(MBRL_EINVAL, "%s: s0 is NULL", c.name);
+    if (c.mix && (rc = noise_check(p->H))) return rc;
+    if (p->N > 32768) return fail(MBRL_EUNSUPPORTED, "%s: N=%d exceeds 32768", c.name, p->N);
+    if ((rc = batch_size_check(c.B, p))) return rc;
+    if (kept_loop && c.B > 65535) return fail(MBRL_EUNSUPPORTED, "%s: B=%d exceeds 65535", c.name, c.B);
+    if (kept_loop && (rc = refit_staged_check(g->a, p->K))) return rc;
+    // the entry's workspace carved (*single or *batch) and its size: a mixed plan demands what its query answers
+    size_t need = c.batched ? (*batch = rh_batch_ws(*g, c.rp, c.B, c.workspace, c.mix != nullptr)).bytes
+                            : (*single = rh_ws(*g, c.rp, c.workspace, c.mix != nullptr)).bytes;
+    if (c.mix) need = mixed_ws_bytes(*g, c.rp, c.B);
+    if (c.ws_bytes < need)
+        return fail(c.batched ? MBRL_EWORKSPACE : MBRL_EINVAL, "%s: workspace %zu < %zu", c.name, c.ws_bytes, need);
+    return c.batched ? MBRL_OK : pair_forced_check(*g, p->N);
+}
+
+// What the kept-rows loop of the single plan and of a batch differ in: where the buffers live and how the
+// rollout and the trajectory are fed.
+struct RhLoop {
+    float *costs, *actions, *mu[2], *sigma[2], *aelite, *kept[2], *rets, *states;
+    int64_t *elites, *best;
+    uint32_t* keys;
+    TrajScratch traj;
+    float* s0_ws;           // the rollout's start states: s0_rep copies of each problem's
+    int s0_rep, s0_per_cand;
+    const float* s0_traj;   // [B][s] for the final trajectories
+    void* pair;             // the pair area (the single plan, where its size offers pairs), or NULL
+    InitZero zero;          // the hand-off words the first launch zeroes (the single plan's)
+};
+
+// The single plan: its own s0 copy (s0_in may be mapped host memory), the pair area and the prezeroed words.
+static RhLoop rh_loop_single(const Geometry& g, int N, const RhWs& rw) {
+    const PlanWs& w = rw.plan;
+    return {w.costs, w.actions, {w.mu[0], w.mu[1]}, {w.sigma[0], w.sigma[1]}, w.aelite, {rw.kept[0], rw.kept[1]},
+            rw.rets, w.states, w.elites, rw.best, w.keys, w.traj, w.s0, 1, 0, w.s0,
+            pair_area_bytes(g, N) ? w.pair : nullptr, plan_zero(g, N, w.pair, w.traj)};
+}
+
+// A batch: per-candidate start states, no pairs, nothing prezeroed, the trajectories from the caller's s0.
+static RhLoop rh_loop_batch(const RhBatchWs& rw, int N, const float* s0) {
+    const BatchWs& w = rw.plan;
+    return {w.costs, w.actions, {w.mu[0], w.mu[1]}, {w.sigma[0], w.sigma[1]}, rw.aelite, {rw.kept[0], rw.kept[1]},
+            rw.rets, w.states, w.elites, rw.best, w.keys, w.traj, w.s0x, N, 1, s0, nullptr, InitZero{}};
+}
+
+static RhInitArgs rh_init_args(const Geometry& g, const RhCall& c, const RhLoop& L) {
+    const mbrl_cem_params* p = &c.rp->cem;
+    RhInitArgs A{};
+    A.seed = p->seed; A.init_mu = p->init_mu; A.init_sigma = p->init_sigma; A.lo = p->lo; A.hi = p->hi;
+    A.H = p->H; A.a = g.a; A.N = p->N; A.Kc = c.rp->keep; A.s = g.s; A.B = c.B; A.s0_rep = L.s0_rep;
+    A.mu_rows = c.mu_rows; A.sigma_rows = c.sigma_rows; A.carry_in = c.carry_in; A.flags = c.flags;
+    A.mu = L.mu[0]; A.sigma = L.sigma[0]; A.actions = L.actions; A.kept0 = c.kept_hist;
+    A.s0_src = c.s0; A.s0_dst = L.s0_ws; A.zero = L.zero;
+    return A;
+}
+
+// kept_cur / kept_next: kept_it and kept_{it+1}; iteration 0 reads carry_in where it is and honours the
+// problems' input flags, from iteration 1 on every problem has a kept set.
+static RhGatherArgs rh_gather_args(const Geometry& g, const RhCall& c, const RhLoop& L, int it, int cur,
+                                   const float* rets, const int64_t* elites, const float* kept_cur, float* kept_next) {
+    const mbrl_cem_params* p = &c.rp->cem;
+    const bool last = it + 1 == p->iterations;
+    RhGatherArgs G{};
+    G.seed = p->seed; G.iteration = it; G.N = p->N; G.H = p->H; G.a = g.a; G.K = p->K; G.Kc = c.rp->keep; G.B = c.B;
+    G.from_kept = it > 0 || c.carry_in; G.flags = it == 0 ? c.flags : nullptr; G.lo = p->lo; G.hi = p->hi;
+    G.mu = L.mu[cur]; G.sigma = L.sigma[cur]; G.kept_cur = it == 0 ? c.carry_in : kept_cur; G.returns = rets;
+    G.elites = elites; G.best = L.best; G.aelite = L.aelite; G.kept_next = kept_next;
+    G.kept_copy = last ? c.carry_out : nullptr; G.best_returns = last ? c.carry_returns_out : nullptr;
+    return G;
+}
+
+// After iteration `it`'s refit into mu / sigma [cur ^ 1]: the next proposals, or the plan outputs.
+static RhDrawArgs rh_draw_args(const Geometry& g, const RhCall& c, const RhLoop& L, int it, int cur, const float* kept) {
+    const mbrl_cem_params* p = &c.rp->cem;
+    const bool last = it + 1 == p->iterations;
+    RhDrawArgs D{};
+    D.seed = p->seed; D.iteration = it + 1; D.H = p->H; D.a = g.a; D.N = p->N; D.Kc = c.rp->keep; D.B = c.B;
+    D.lo = p->lo; D.hi = p->hi;
+    D.mu = L.mu[cur ^ 1]; D.sigma = L.sigma[cur ^ 1]; D.kept = kept;
+    D.actions = last ? nullptr : L.actions;
+    D.fin_mu = last ? c.mu : nullptr; D.fin_sigma = last ? c.sigma : nullptr; D.fin_actions = last ? c.actions_out : nullptr;
+    return D;
+}
+
+// keep > 0, B problems (the single plan: B = 1): every iteration is the one rollout of the B N proposals in
+// L.actions, then five small launches, each over all B problems -- the K elites, the Kc best (the same returns
+// selected twice, segmented by problem), the gather of both sets' action rows, the refit over the gathered
+// elites (grid (H, B)), and the next proposals (kept rows scattered into slots [0, Kc), the rest drawn) or, on
+// the last iteration, the plan outputs. kept_i lives in kept_hist's row i where the caller records, else in
+// the workspace's two buffers. Then each problem's final mean rolled out, one trajectory launch each.
+// mix (NULL: none): the same loop for any keep >= 0 with the first launch, the gather and the draw coloured
+// (cem_noise.hip); the Kc selection runs only when Kc > 0.
+static int cem_plan_rh_kept(const Geometry& g, const RhCall& c, const RhLoop& L, hipStream_t stream) {
+    const mbrl_cem_params* p = &c.rp->cem;
+    const float* mix = c.mix;
+    const int B = c.B, Kc = c.rp->keep, BN = B * p->N;
+    const size_t kept_floats = (size_t)B * Kc * p->H * g.a;
+    auto kept_at = [&](int i) { return c.kept_hist ? c.kept_hist + (size_t)i * kept_floats : L.kept[i & 1]; };
+    int rc;
+    const RhInitArgs A = rh_init_args(g, c, L);
+    if ((rc = hip_check(mix ? launch_noise_init(A, mix, stream) : launch_rh_init(A, stream), "init launch"))) return rc;
+    unsigned pair_epoch = 0;
+    const size_t keys_bytes = align256((size_t)BN * 4);
+    int cur = 0;
+    for (int it = 0; it < p->iterations; ++it) {
+        float* costs = c.cost_hist ? c.cost_hist + (size_t)it * g.E * BN : L.costs;
+        int64_t* elites = c.elite_hist ? c.elite_hist + (size_t)it * B * p->K : L.elites;
+        float* rets = c.returns_hist ? c.returns_hist + (size_t)it * BN : L.rets;
+        if ((rc = record_rollout_event(c.events, 2 * it, stream))) return rc;
+        rc = rollout_impl(g, c.packed, c.norm, c.cost, L.s0_ws, L.s0_per_cand, L.actions, nullptr, BN, p->H, 0, costs,
+                          nullptr, nullptr, stream, L.pair, L.zero.ptr[0] ? &pair_epoch : nullptr);
+        if (rc) return rc;
+        if ((rc = record_rollout_event(c.events, 2 * it + 1, stream))) return rc;
+        if ((rc = select_impl(costs, g.E, p->N, p->K, MBRL_NAN_LAST, elites, rets, L.keys, keys_bytes, stream, B)))
+            return rc;
+        if (Kc && (rc = select_impl(costs, g.E, p->N, Kc, MBRL_NAN_LAST, L.best, nullptr, L.keys, keys_bytes, stream, B)))
+            return rc;
+        const RhGatherArgs G = rh_gather_args(g, c, L, it, cur, rets, elites, kept_at(it), kept_at(it + 1));
+        if ((rc = hip_check(mix ? launch_noise_gather(G, mix, stream) : launch_rh_gather(G, stream), "gather launch")))
+            return rc;
+        rc = refit_staged_impl(L.aelite, p->H, g.a, p->K, p->alpha, L.mu[cur], L.sigma[cur], L.mu[cur ^ 1],
+                               L.sigma[cur ^ 1], stream, B);
+        if (rc) return rc;
+        const RhDrawArgs D = rh_draw_args(g, c, L, it, cur, kept_at(it + 1));
+        if ((rc = hip_check(mix ? launch_noise_draw(D, mix, stream) : launch_rh_draw(D, stream), "draw launch"))) return rc;
+        cur ^= 1;
+    }
+    // each final mean's rollout -> predicted states [E][H][s] (E == 1: straight into states_out), member mean
+    const size_t Hs = (size_t)p->H * g.s;
+    for (int b = 0; b < B; ++b) {
+        rc = final_trajectory(g, c.packed, c.norm, L.s0_traj + (size_t)b * g.s, c.actions_out + (size_t)b * p->H * g.a,
+                              p->H, c.states_out + b * Hs, L.states, L.traj, stream, L.zero.ptr[1] != nullptr);
+        if (rc) return rc;
+    }
+    return hip_check(hipGetLastError(), c.batched ? "batched plan launch" : "plan launch");
+}
+
+// The four entries: the checks, then the fused-update loops where no rows are kept and no mix is given
+// (cem_plan_run / cem_batch_run with the initial distribution's rows), else the kept-rows loop.
+static int rh_plan(const RhCall& c) {
+    hipStream_t stream = reinterpret_cast<hipStream_t>(c.stream);
+    Geometry g;
+    RhWs w;
+    RhBatchWs bw;
+    if (int rc = rh_entry_check(c, &g, &w, &bw)) return rc;
+    const mbrl_cem_params* p = &c.rp->cem;
+    const bool kept_loop = c.rp->keep > 0 || c.mix;
+    if (kept_loop)
+        return cem_plan_rh_kept(g, c, c.batched ? rh_loop_batch(bw, p->N, c.s0) : rh_loop_single(g, p->N, w), stream);
+    if (c.batched)
+        return cem_batch_run(g, c.packed, c.norm, c.cost, c.s0, c.B, p, c.mu_rows, c.sigma_rows, c.flags, c.mu, c.sigma,
+                             c.actions_out, c.states_out, c.cost_hist, c.returns_hist, c.elite_hist, bw.plan, stream);
+    return cem_plan_run(g, c.packed, c.norm, c.cost, c.s0, p, c.mu_rows, c.sigma_rows, c.mu, c.sigma, c.actions_out,
+                        c.states_out, c.cost_hist, c.returns_hist, c.elite_hist, c.events, w.plan, stream);
+}
+
+int mbrl_cem_plan_rh_mixed(const mbrl_mlp_shape* shape, const void* packed, const mbrl_norm* norm,
+                           const mbrl_cost* cost, const float* s0_in, const mbrl_cem_rh_params* rp,
+                           const float* init_mu_rows, const float* init_sigma_rows, const float* carry_in,
+                           const float* noise_mix, float* mu, float* sigma, float* actions_out, float* states_out,
+                           float* carry_out, float* carry_returns_out, float* cost_hist, float* returns_hist,
+                           int64_t* elite_hist, float* kept_hist, mbrl_event_t* rollout_events, void* workspace,
+                           size_t ws_bytes, mbrl_stream_t stream) {
+    return rh_plan({noise_mix ? "cem_plan_rh_mixed" : "cem_plan_rh", false, shape, packed, norm, cost, s0_in, 1, rp,
+                    init_mu_rows, init_sigma_rows, carry_in, nullptr, noise_mix, mu, sigma, actions_out, states_out,
+                    carry_out, carry_returns_out, cost_hist, returns_hist, elite_hist, kept_hist, rollout_events,
+                    workspace, ws_bytes, stream});
+}
+
+int mbrl_cem_plan_rh(const mbrl_mlp_shape* shape, const void* packed, const mbrl_norm* norm, const mbrl_cost* cost,
+                     const float* s0_in, const mbrl_cem_rh_params* rp, const float* init_mu_rows,
+                     const float* init_sigma_rows, const float* carry_in, float* mu, float* sigma, float* actions_out,
+                     float* states_out, float* carry_out, float* carry_returns_out, float* cost_hist,
+                     float* returns_hist, int64_t* elite_hist, float* kept_hist, mbrl_event_t* rollout_events,
+                     void* workspace, size_t ws_bytes, mbrl_stream_t stream) {
+    return mbrl_cem_plan_rh_mixed(shape, packed, norm, cost, s0_in, rp, init_mu_rows, init_sigma_rows, carry_in, nullptr,
+                                  mu, sigma, actions_out, states_out, carry_out, carry_returns_out, cost_hist,
+                                  returns_hist, elite_hist, kept_hist, rollout_events, workspace, ws_bytes, stream);
 }
 
 int mbrl_cem_plan_rh_batch_mixed(const mbrl_mlp_shape* shape, const void* packed, const mbrl_norm* norm,
@@ -1132,32 +1120,24 @@ int mbrl_cem_plan_rh_batch_mixed(const mbrl_mlp_shape* shape, const void* packed
                                  const int32_t* input_flags, const float* noise_mix, float* mu, float* sigma,
                                  float* actions_out, float* states_out, float* carry_out, float* carry_returns_out,
                                  float* cost_hist, float* returns_hist, int64_t* elite_hist, float* kept_hist,
-                                 void* workspace, size_t ws_bytes, mbrl_stream_t stream_) {
-    if (!noise_mix)
-        return mbrl_cem_plan_rh_batch(shape, packed, norm, cost, s0, B, rp, init_mu_rows, init_sigma_rows, carry_in,
-                                      input_flags, mu, sigma, actions_out, states_out, carry_out, carry_returns_out,
-                                      cost_hist, returns_hist, elite_hist, kept_hist, workspace, ws_bytes, stream_);
-    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-    Geometry g;
-    int rc = shape_geometry(shape, &g);
-    if (rc) return rc;
-    if (B < 1) return fail(MBRL_EINVAL, "cem_plan_rh_batch_mixed: B=%d", B);
-    if ((rc = rh_params_check(rp))) return rc;
-    if (carry_in && rp->keep == 0) return fail(MBRL_EINVAL, "cem_plan_rh_batch_mixed: carry_in given with keep == 0");
-    if (!packed || !s0 || !actions_out || !states_out || !workspace)
-        return fail(MBRL_EINVAL, "cem_plan_rh_batch_mixed: packed/s0/actions_out/states_out/workspace NULL");
-    if ((rc = noise_check(rp->cem.H))) return rc;
-    if (rp->cem.N > 32768) return fail(MBRL_EUNSUPPORTED, "cem_plan_rh_batch_mixed: N=%d exceeds 32768", rp->cem.N);
-    if ((rc = batch_size_check(B, &rp->cem))) return rc;
-    if (B > 65535) return fail(MBRL_EUNSUPPORTED, "cem_plan_rh_batch_mixed: B=%d exceeds 65535", B);
-    if ((rc = refit_staged_check(g.a, rp->cem.K))) return rc;
-    const RhBatchWs w = rh_batch_ws(g, rp, B, workspace, true);
-    if (const size_t need = mixed_ws_bytes(g, rp, B); ws_bytes < need)
-        return fail(MBRL_EWORKSPACE, "cem_plan_rh_batch_mixed: workspace %zu < %zu", ws_bytes, need);
-    return cem_plan_rh_batch_kept(g, packed, norm, cost, s0, B, rp, init_mu_rows, init_sigma_rows, carry_in, input_flags,
-                                  mu, sigma, actions_out, states_out, carry_out, carry_returns_out, cost_hist,
-                                  returns_hist, elite_hist, kept_hist, w, stream, noise_mix);
+                                 void* workspace, size_t ws_bytes, mbrl_stream_t stream) {
+    return rh_plan({noise_mix ? "cem_plan_rh_batch_mixed" : "cem_plan_rh_batch", true, shape, packed, norm, cost, s0, B,
+                    rp, init_mu_rows, init_sigma_rows, carry_in, input_flags, noise_mix, mu, sigma, actions_out,
+                    states_out, carry_out, carry_returns_out, cost_hist, returns_hist, elite_hist, kept_hist, nullptr,
+                    workspace, ws_bytes, stream});
+}
+
+int mbrl_cem_plan_rh_batch(const mbrl_mlp_shape* shape, const void* packed, const mbrl_norm* norm,
+                           const mbrl_cost* cost, const float* s0, int32_t B, const mbrl_cem_rh_params* rp,
+                           const float* init_mu_rows, const float* init_sigma_rows, const float* carry_in,
+                           const int32_t* input_flags, float* mu, float* sigma, float* actions_out, float* states_out,
+                           float* carry_out, float* carry_returns_out, float* cost_hist, float* returns_hist,
+                           int64_t* elite_hist, float* kept_hist, void* workspace, size_t ws_bytes,
+                           mbrl_stream_t stream) {
+    return mbrl_cem_plan_rh_batch_mixed(shape, packed, norm, cost, s0, B, rp, init_mu_rows, init_sigma_rows, carry_in,
+                                        input_flags, nullptr, mu, sigma, actions_out, states_out, carry_out,
+                                        carry_returns_out, cost_hist, returns_hist, elite_hist, kept_hist, workspace,
+                                        ws_bytes, stream);
 }
 
 }  // extern "C"
-

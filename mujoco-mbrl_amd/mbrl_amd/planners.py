@@ -743,6 +743,25 @@ def _rh_batch_inputs(st, B, initial_trajectories, carries, prev_sigmas, kwargs, 
     return out
 
 
+def _rh_call_inputs(lib, rh, a, dev, noise, batched):
+    """What the single and the batched receding-horizon call share: the rows' action-dimension check, the
+    upload of the mean rows, sigma rows, carry and (batched) flags -- an absent one stays None -- and the choice
+    of sizer and entry by the noise mix (one matrix serves all B problems). Returns (the uploaded tensors, the
+    entry's input pointers, sizer, entry)."""
+    keys = ("mu_rows", "sigma_rows", "carry") + (("flags",) if batched else ())
+    for k in keys[:3]:
+        if rh[k] is not None and rh[k].shape[-1] != a:
+            raise ValueError(f"{k} has {rh[k].shape[-1]} action dims, the model {a}")
+    tensors = [None if rh[k] is None else torch.from_numpy(np.ascontiguousarray(rh[k])).to(dev) for k in keys]
+    ins = tuple(_lib.ptr(t) for t in tensors)
+    entry = "mbrl_cem_plan_rh_batch" if batched else "mbrl_cem_plan_rh"
+    if noise is None:
+        sizer = lib.mbrl_cem_rh_batch_workspace_bytes if batched else lib.mbrl_cem_rh_workspace_bytes
+        return tensors, ins, sizer, getattr(lib, entry)
+    ins += (_lib.ptr(_noise_mix_device(noise, dev)),)
+    return tensors, ins, lib.mbrl_cem_rh_mixed_workspace_bytes, getattr(lib, entry + "_mixed")
+
+
 def cem_plan_batch_rh(initial_states, model, cost, sample_action, horizon, initial_trajectories=None, carries=None,
                       prev_sigmas=None, **kwargs):
     """B independent receding-horizon CEM plans in shared launches (mbrl_cem_plan_rh_batch): cem_plan_batch
@@ -779,18 +798,13 @@ def cem_plan_batch_rh(initial_states, model, cost, sample_action, horizon, initi
         lib = _lib.load()
         N, K, H, I, Kc = st["N"], st["K"], st["H"], st["I"], rh["Kc"]
         a, s, E = mdesc["a"], mdesc["s"], mdesc["E"]
-        for k in ("mu_rows", "sigma_rows", "carry"):
-            if rh[k] is not None and rh[k].shape[-1] != a:
-                raise ValueError(f"{k} has {rh[k].shape[-1]} action dims, the model {a}")
+        _held, ins, sizer, call = _rh_call_inputs(lib, rh, a, dev, noise, True)   # (the uploads, held to the call)
         params = _lib.CemRhParams(_cem_params(st, int(st["seed"]) & 0xFFFFFFFFFFFFFFFF), Kc, 0)
-        sizer = lib.mbrl_cem_rh_batch_workspace_bytes if noise is None else lib.mbrl_cem_rh_mixed_workspace_bytes
         need = sizer(fused.ctypes_ref(prob.shape), fused.ctypes_ref(params), B)
         if need == 0:
             _lib.check(_lib.MBRL_EINVAL, sizer.__name__)
         ws = _workspace(("cem_rh_batch", str(dev)), need, dev)
         s0 = initial_states.to(device=dev, dtype=torch.float32).reshape(B, s).contiguous()
-        rows_d, sig_d, carry_d, flags_d = [None if rh[k] is None else torch.from_numpy(np.ascontiguousarray(rh[k])).to(dev)
-                                           for k in ("mu_rows", "sigma_rows", "carry", "flags")]
         e = lambda *sh, dt=torch.float32: torch.empty(sh, dtype=dt, device=dev)  # noqa: E731
         out = dict(states=e(B, H, s), actions=e(B, H, a), mu=e(B, H, a), sigma=e(B, H, a))
         rec = st["record"]
@@ -801,11 +815,6 @@ def cem_plan_batch_rh(initial_states, model, cost, sample_action, horizon, initi
             if Kc:
                 out.update(kept_hist=e(I + 1, B, Kc, H, a))
         g = lambda k: _lib.ptr(out.get(k))  # noqa: E731
-        ins = (_lib.ptr(rows_d), _lib.ptr(sig_d), _lib.ptr(carry_d), _lib.ptr(flags_d))
-        if noise is not None:     # (one matrix serves all B problems)
-            call, ins = lib.mbrl_cem_plan_rh_batch_mixed, ins + (_lib.ptr(_noise_mix_device(noise, dev)),)
-        else:
-            call = lib.mbrl_cem_plan_rh_batch
         _lib.check(call(*prob.refs, _lib.ptr(s0), B, fused.ctypes_ref(params), *ins, g("mu"), g("sigma"), g("actions"),
                         g("states"), g("carry"), g("carry_returns"), g("costs"), g("returns"), g("elites"),
                         g("kept_hist"), _lib.ptr(ws), ws.numel(), _lib.stream_handle(dev)), call.__name__)
@@ -1050,21 +1059,16 @@ def _cem_fused_rh(prob, initial_state, st, rh):
     md = prob.mdesc
     N, K, H, I, Kc = st["N"], st["K"], st["H"], st["I"], rh["Kc"]
     a, s, E = md["a"], md["s"], md["E"]
-    for k in ("mu_rows", "sigma_rows", "carry"):
-        if rh[k] is not None and rh[k].shape[-1] != a:
-            raise ValueError(f"{k} has {rh[k].shape[-1]} action dims, the model {a}")
     noise = rh.get("mix")
+    (rows_d, sig_d, _carry_d), ins, sizer, call = _rh_call_inputs(lib, rh, a, dev, noise, False)   # (held to the call)
     pkey = ("rh" if noise is None else "rh_mixed", N, H, K, I, Kc, st["alpha"], st["lo"], st["hi"], st["init_std"],
             int(st["seed"]) & 0xFFFFFFFFFFFFFFFF)
-    sizer = lib.mbrl_cem_rh_workspace_bytes if noise is None else lib.mbrl_cem_rh_mixed_workspace_bytes
     _, pref, need = _plan_params(prob, pkey, lambda: _lib.CemRhParams(_cem_params(st, pkey[-1]), Kc, 0), sizer,
                                  *(() if noise is None else (1,)))
     if need == 0:
         _lib.check(_lib.MBRL_EINVAL, sizer.__name__)
     ws = _workspace(("cem_rh", str(dev)), need, dev)
     s0 = initial_state.to(device=dev, dtype=torch.float32).contiguous()
-    rows_d, sig_d, carry_d = [None if rh[k] is None else torch.from_numpy(np.ascontiguousarray(rh[k])).to(dev)
-                              for k in ("mu_rows", "sigma_rows", "carry")]
     out = _device_outputs(dev, H, s, a)
     rec = st["record"]
     cost_hist, ret_hist, elite_hist = _cem_record_buffers(dev, rec, I, E, N, K)
@@ -1075,11 +1079,6 @@ def _cem_fused_rh(prob, initial_state, st, rh):
         kept_hist = torch.empty((I + 1, Kc, H, a), dtype=torch.float32, device=dev) if rec else None
     pev = st["plan_events"]
     _mark(pev, 0)
-    ins = (_lib.ptr(rows_d), _lib.ptr(sig_d), _lib.ptr(carry_d))
-    if noise is not None:
-        call, ins = lib.mbrl_cem_plan_rh_mixed, ins + (_lib.ptr(_noise_mix_device(noise, dev)),)
-    else:
-        call = lib.mbrl_cem_plan_rh
     _lib.check(call(*prob.refs, _lib.ptr(s0), pref, *ins, *_output_ptrs(out), _lib.ptr(carry_out), _lib.ptr(carry_ret),
                     _lib.ptr(cost_hist), _lib.ptr(ret_hist), _lib.ptr(elite_hist), _lib.ptr(kept_hist), _events(st, I),
                     _lib.ptr(ws), ws.numel(), _lib.stream_handle(dev)), call.__name__)

@@ -1,15 +1,13 @@
 """Batched receding-horizon CEM (include/mbrl_cem.h mbrl_cem_plan_rh_batch) restated in NumPy: ONE problem of
-a batch is cem_rh_reference.plan with candidate indices b N + arange(N) for the proposal RNG, built from the
-oracle's pieces (oracle.cem, oracle.philox.cem_actions) and that module's helpers. TEST INFRASTRUCTURE ONLY:
-the checker for the problem dimension of csrc/cem_rh.hip, the staged refit and the batched plan loop.
+a batch is cem_rh_reference.plan with its own initial state and candidate indices b N + arange(N) for the
+proposal RNG. TEST INFRASTRUCTURE ONLY: the checker for the problem dimension of csrc/cem_rh.hip, the staged
+refit and the batched plan loop.
 
 A batch is B such plans that share the model, the cost and the CEM settings and differ in their initial
 state, their optional inputs (an absent input = that problem's flag bit clear) and their candidate offset."""
 import numpy as np
 
 import cem_rh_reference as rh
-from oracle import cem as ocem
-from oracle.philox import cem_actions
 
 F32 = np.float32
 FLAG_MU, FLAG_SIGMA, FLAG_CARRY = 1, 2, 4
@@ -17,51 +15,15 @@ SMALL = rh.SMALL
 GAP_MIN = rh.GAP_MIN
 
 
-def plan_problem(problem, s0, b, N, H, K, I, *, keep=0, init_mu_rows=None, init_sigma_rows=None, carry_in=None,
-                 seed=None, final=True):
+def plan_problem(problem, s0, b, N, H, K, I, **kw):
     """Problem b of a batch: cem_rh_reference.plan on initial state s0 with Philox candidate indices
-    b N + arange(N). Same outputs as that function (b == 0 and s0 == problem["s0"]: the same plan)."""
-    d = ocem.CEM_DEFAULTS
-    alpha, lo, hi = d["alpha"], d["lo"], d["hi"]
-    a = problem["cfg"]["a"]
-    Kc = int(keep)
-    seed = problem["rng_seed"] if seed is None else seed
-    idx = b * N + np.arange(N)
-    assert 0 <= Kc <= K and (carry_in is None or Kc > 0)
-    mu = np.zeros((H, a), F32) if init_mu_rows is None else \
-        np.clip(np.asarray(init_mu_rows, F32), F32(lo), F32(hi)).astype(F32)
-    sigma = np.full((H, a), F32((hi - lo) / 4.0), F32) if init_sigma_rows is None else \
-        np.asarray(init_sigma_rows, F32).copy()
-    kept = None if carry_in is None else np.asarray(carry_in, F32).reshape(Kc, H, a)
-    out = dict(costs=[], returns=[], elites=[], best=[], actions=[], mu=[], sigma=[], mu0=mu, sigma0=sigma,
-               kept=[np.zeros((Kc, H, a), F32) if kept is None else kept.copy()])
-    s0 = np.asarray(s0, F32)
-    for it in range(I):
-        A = cem_actions(mu, sigma, lo, hi, seed, it, idx)
-        if Kc and kept is not None:
-            A[:, :Kc, :] = rh.clip_keep_nan(kept, lo, hi).transpose(1, 0, 2)
-        costs = ocem.rollout(problem["model"], problem["norm"], problem["cost"], s0, A)
-        ret = ocem.ensemble_returns(costs)
-        elites = ocem.select_elites(ret, K)
-        best = ocem.select_elites(ret, Kc) if Kc else np.zeros(0, np.int64)
-        mu, sigma = ocem.refit(mu, sigma, np.ascontiguousarray(A[:, elites, :].transpose(1, 0, 2)), alpha)
-        kept = np.ascontiguousarray(A[:, best, :].transpose(1, 0, 2))
-        for k, v in dict(costs=costs, returns=ret, elites=elites, best=best, actions=A, mu=mu, sigma=sigma).items():
-            out[k].append(v)
-        out["kept"].append(kept.copy())
-    out.update(mu_out=mu, sigma_out=sigma, carry=kept, carry_returns=out["returns"][-1][out["best"][-1]],
-               final_actions=np.clip(mu, F32(lo), F32(hi)).astype(F32))
-    if final:
-        _, states = ocem.rollout(problem["model"], problem["norm"], problem["cost"], s0,
-                                 out["final_actions"][:, None, :], store_states=True)
-        out["final_states"] = np.mean(states[:, :, 0, :], axis=0, dtype=F32) if len(problem["model"]) > 1 \
-            else states[0, :, 0, :]
-    return out
+    b N + arange(N) (its keywords; b == 0 and s0 == problem["s0"]: the single plan)."""
+    return rh.plan(problem, N, H, K, I, s0=s0, b=b, **kw)
 
 
-def plan_batch(problem, s0s, N, H, K, I, keep, kws, seed=None, final=True):
-    """The B plans of a batch: kws[b] holds problem b's optional inputs (plan_problem's keywords)."""
-    return [plan_problem(problem, s0s[b], b, N, H, K, I, keep=keep, seed=seed, final=final, **kws[b])
+def plan_batch(problem, s0s, N, H, K, I, keep, kws, seed=None, final=True, mix=None):
+    """The B plans of a batch: kws[b] holds problem b's optional inputs (cem_rh_reference.plan's keywords)."""
+    return [plan_problem(problem, s0s[b], b, N, H, K, I, keep=keep, seed=seed, final=final, mix=mix, **kws[b])
             for b in range(len(kws))]
 
 
@@ -113,28 +75,7 @@ def case_id(case):
     return f"W{W}-L{L}-a{a}-N{N}-E{E}-Kc{Kc}-B{len(inputs)}-" + "+".join(x or "0" for x in inputs)
 
 
-def make_case(case):
-    """(problem, s0s [B, s], kws) of one fixture batch: the synthetic cartpole problem with the case's shape
-    (problem 0 starts from its s0, the others from perturbed copies) and each problem's optional inputs drawn
-    from the case seed (some mean and carry entries outside the bounds)."""
-    W, L, a, N, E, Kc, inputs, seed = case
-    H = SMALL["H"]
-    p = ocem.synth_problem(2, seed=7300 + seed, W=W, L=L, a=a, E=E, N=N, H=H)
-    rng = np.random.default_rng(seed)
-    B = len(inputs)
-    s0s = np.stack([p["s0"]] + [(p["s0"] + rng.normal(0.0, 0.2, p["s0"].shape)).astype(F32) for _ in range(B - 1)])
-    kws = []
-    for given in inputs:
-        kw = {}
-        if "m" in given:
-            kw["init_mu_rows"] = rng.uniform(-1.3, 1.3, (H, a)).astype(F32)
-        if "s" in given:
-            kw["init_sigma_rows"] = rng.uniform(0.1, 0.6, (H, a)).astype(F32)
-        if "c" in given:
-            assert Kc > 0
-            kw["carry_in"] = rng.uniform(-1.2, 1.2, (Kc, H, a)).astype(F32)
-        kws.append(kw)
-    return p, s0s.astype(F32), kws
+make_case = rh.make_batch   # (problem, s0s [B, s], kws) of one fixture batch
 
 
 def case_plans(case):

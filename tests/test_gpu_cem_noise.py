@@ -1,6 +1,6 @@
 """GPU: coloured-noise proposals (csrc/cem_noise.hip: mbrl_sample_actions_mixed, mbrl_cem_plan_rh_mixed,
 mbrl_cem_plan_rh_batch_mixed and their loops in plan.hip) and the planners' noise_beta / noise_mix kwargs,
-against the NumPy restatement (tests/cem_noise_reference.py).
+against the NumPy restatement (tests/cem_rh_reference.py plan / mixed_actions; fixtures: tests/cem_noise_reference.py).
 
 Bars: the mixed draw bit for bit; the plans at tests/test_gpu_cem_rh.py's bars -- costs within 1e-5 relative,
 elite and best index sets identical (tests/test_cem_noise_host.py asserts the fixtures' return gaps), mu,
