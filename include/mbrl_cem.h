@@ -32,7 +32,8 @@ extern "C" {
  * mbrl_mppi_params): they were added within v13, purely additively -- no existing entry point, struct
  * or option changed, so the version did not move. The receding-horizon CEM plan (mbrl_cem_rh_params,
  * mbrl_cem_rh_workspace_bytes, mbrl_cem_plan_rh) joined them the same way, and its batched form
- * (mbrl_cem_rh_batch_workspace_bytes, mbrl_cem_plan_rh_batch) after it. */
+ * (mbrl_cem_rh_batch_workspace_bytes, mbrl_cem_plan_rh_batch) after it, then batched MPPI
+ * (mbrl_mppi_update_batch, mbrl_mppi_batch_workspace_bytes, mbrl_mppi_plan_batch). */
 #define MBRL_ABI_VERSION 13
 
 typedef struct ihipStream_t* mbrl_stream_t; /* == hipStream_t */
@@ -437,6 +438,48 @@ int mbrl_mppi_plan(const mbrl_mlp_shape* shape, const void* packed, const mbrl_n
                    float* sigma, float* actions_out, float* states_out, float* cost_hist, float* weight_hist,
                    float* mu_hist, float* sigma_hist, mbrl_event_t* rollout_events, void* workspace,
                    size_t ws_bytes, mbrl_stream_t stream);
+
+/* ---- batched MPPI (added within ABI v13, additively: no existing entry, struct or option changes).
+ * mbrl_mppi_update_batch: mbrl_mppi_update for B problems as ONE launch (grid (H S, B)), no workspace.
+ * Problem b's costs are columns [b N, (b + 1) N) of costs [E][B N], its proposals columns b N + n of actions
+ * [H][B N][a]; the sampler's mu / sigma and mu_out / sigma_out are [B][H][a]. Each problem forms its own
+ * returns, beta, weights and eta over its own N, in mbrl_mppi_update's summation order counted from its
+ * candidate 0: every output of problem b equals mbrl_mppi_update on contiguous copies of its slices, bit for
+ * bit (a problem without a finite return keeps its distribution while its neighbours update).
+ * Optional (NULL = off): weights_out [B][N]; returns_out [B][N]; stats_out [B][2]; next_actions [H][B N][a]
+ * (not `actions`): iteration sampler->iteration + 1's proposals of every problem, column b N + n drawn from
+ * mu_out[b] / sigma_out[b] with Philox index b N + n, bit-identical to mbrl_sample_actions with n_offset = b N.
+ * Before any launch: mbrl_mppi_update's checks; B < 1: MBRL_EINVAL; B > 65535 or B N beyond
+ * mbrl_cem_plan_batch's bound: MBRL_EUNSUPPORTED. */
+int mbrl_mppi_update_batch(const float* costs, int32_t E, int32_t N, int32_t B, const float* actions,
+                           const mbrl_sampler* sampler, int32_t H, int32_t a, float temperature, float alpha,
+                           int32_t update_sigma, float* mu_out, float* sigma_out, float* weights_out,
+                           float* returns_out, float* stats_out, float* next_actions, mbrl_stream_t stream);
+
+/* mbrl_mppi_plan_batch: B independent mbrl_mppi_plan plans (one initial state each, s0 [B][s] device) in
+ * shared launches; params->N is per problem. One first launch (the distributions, the start states expanded
+ * to one per candidate, iteration 0's proposals where the update draws them), then per iteration ONE rollout
+ * over the B N candidates and ONE mbrl_mppi_update_batch launch, then each problem's final trajectory, one
+ * launch each as in mbrl_cem_plan_batch.
+ * Warm start: init_mu_rows [B][H][a] device or NULL; input_flags [B] int32 device or NULL. Bit 0 of
+ * input_flags[b] set: problem b's initial mean is its rows clipped to [lo, hi]; clear: params->init_mu (its
+ * first control step). NULL flags: every problem takes its rows; a set bit with NULL rows is ignored (as
+ * mbrl_cem_plan_rh_batch, so one batch mixes first-step and mid-episode problems).
+ * mu, sigma (optional), actions_out = clip(mu, lo, hi): [B][H][a]; states_out [B][H][s] (member mean); device.
+ * Optional records (NULL = off): cost_hist [I][E][B N]; weight_hist [I][B][N]; mu_hist / sigma_hist
+ * [I + 1][B][H][a], row 0 the initial distributions.
+ * Problem 0 of any batch, and all of a B = 1 batch, is mbrl_mppi_plan bit for bit (outputs and records);
+ * problem b is the same plan with Philox candidate index b N + n.
+ * mbrl_mppi_batch_workspace_bytes returns 0 for a bad shape, bad params or B < 1; its answer never shrinks as B
+ * grows and is never below mbrl_mppi_workspace_bytes (for B = 1 it also serves mbrl_mppi_plan). Before any launch: NULL packed / s0 / actions_out / states_out / workspace, B < 1
+ * or bad params: MBRL_EINVAL; N > 32768, B > 65535 or B N beyond mbrl_cem_plan_batch's bound:
+ * MBRL_EUNSUPPORTED; a workspace that is too small: MBRL_EWORKSPACE. */
+size_t mbrl_mppi_batch_workspace_bytes(const mbrl_mlp_shape* shape, const mbrl_mppi_params* params, int32_t B);
+int mbrl_mppi_plan_batch(const mbrl_mlp_shape* shape, const void* packed, const mbrl_norm* norm, const mbrl_cost* cost,
+                         const float* s0, int32_t B, const mbrl_mppi_params* params, const float* init_mu_rows,
+                         const int32_t* input_flags, float* mu, float* sigma, float* actions_out, float* states_out,
+                         float* cost_hist, float* weight_hist, float* mu_hist, float* sigma_hist, void* workspace,
+                         size_t ws_bytes, mbrl_stream_t stream);
 
 /* ---- receding-horizon CEM plan (warm start and elite carry-over, the two iCEM ingredients of Pinneri
  * et al. 2020; not in the reference; added within ABI v13, additively, as the MPPI calls were).

@@ -475,6 +475,12 @@ struct MppiArgs {
 };
 size_t mppi_update_lds_bytes(int N, int a);
 hipError_t launch_mppi_update(const MppiArgs& A, int S, hipStream_t stream);
+// The same update for B problems in one launch, grid (H * S, B): A describes one problem (N, H, a, the
+// scalars) and the batch's buffers -- costs [E][B N], actions / next_actions [H][B N][a], mu / sigma, the
+// outputs and fin_* [B][H][a], weights_out / returns_out [B][N], stats_out [B][2]. Problem b draws its next
+// proposals with Philox index b N + n (draw_off / draw_n are not read). Per problem, the single launch's bits.
+constexpr int MPPI_MAX_B = 65535;
+hipError_t launch_mppi_update_batch(const MppiArgs& A, int S, int B, hipStream_t stream);
 // The fill mbrl_mppi_update and mbrl_mppi_plan (plan.hip) share: one update of `sp`'s distribution over
 // all N candidates; the caller adds the fin_* / *_out diagnostics and the next proposals' draw.
 MppiArgs make_mppi_args(const float* costs, int E, int N, int H, int a, const float* actions, const mbrl_sampler& sp,
@@ -482,6 +488,9 @@ MppiArgs make_mppi_args(const float* costs, int E, int N, int H, int a, const fl
 // Argument checks of both (MBRL_* code, message set).
 int mppi_temperature_check(float temperature);
 int mppi_range_check(int N, int a);
+// B of a batched update or plan: MBRL_EINVAL below 1, MBRL_EUNSUPPORTED above MPPI_MAX_B or where B N
+// exceeds mbrl_cem_plan_batch's bound.
+int mppi_batch_check(int B, int N);
 
 // Fused gradient-descent planner (gd.hip): one persistent workgroup runs every Adam iteration of
 // planners.py:103-137 (goal-state cost, one ensemble member).

@@ -23,6 +23,8 @@
 //      with update_draw's arithmetic and indexing (bit-identical to mbrl_sample_actions).
 // If no return is finite the distribution is left unchanged, bit for bit.
 // All arithmetic fp32, correctly rounded, no contraction.
+// The same kernel serves B problems in one launch (mbrl_mppi_update_batch, mbrl_mppi_plan_batch): grid
+// (H * S, B), each workgroup on one problem's slices of the batch's buffers (mppi_update_kernel<true>).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -67,13 +69,33 @@ __device__ __forceinline__ float mppi_unkey(uint32_t k) {
     return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k);
 }
 
-__global__ void __launch_bounds__(MPPI_THREADS) mppi_update_kernel(const MppiArgs A) {
+// BATCH: grid (H * S, B), workgroup (t * S + j, b) on problem b of B = gridDim.y. Problem b's costs are columns
+// [b N, (b + 1) N) of costs [E][B N], its proposals columns b N + n of actions [H][B N][a] (and of next_actions,
+// drawn with Philox index b N + n), its distribution mu / sigma [B][H][a]; weights / returns [B][N], stats
+// [B][2]. Every offset below is uniform over the workgroup; the arithmetic is the single kernel's, over the
+// problem's own N (chunks counted from its candidate 0). BATCH = false compiles to the single-problem kernel.
+template <bool BATCH>
+__global__ void __launch_bounds__(MPPI_THREADS) mppi_update_kernel(MppiArgs A) {
 #pragma clang fp contract(off)
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int S = gridDim.x / A.H;                      // draw slices per row
     const int t = blockIdx.x / S, j = blockIdx.x - (blockIdx.x / S) * S;
-    const bool lead = blockIdx.x == 0;                  // writes the weights, returns and stats
+    const bool lead = blockIdx.x == 0;                  // writes the (problem's) weights, returns and stats
     const int N = A.N, a = A.a, a4 = (a + 3) & ~3, E = A.E;
+    const size_t cs = BATCH ? (size_t)gridDim.y * N : (size_t)N;   // member stride of costs, candidates per row
+    if (BATCH) {
+        const size_t bN = (size_t)blockIdx.y * N, bHa = (size_t)blockIdx.y * A.H * a;
+        A.costs += bN; A.actions += bN * a; A.mu += bHa; A.sigma += bHa; A.mu_out += bHa; A.sigma_out += bHa;
+        if (A.fin_actions) {
+            A.fin_actions += bHa;
+            if (A.fin_mu) A.fin_mu += bHa;
+            if (A.fin_sigma) A.fin_sigma += bHa;
+        }
+        if (A.weights_out) A.weights_out += bN;
+        if (A.returns_out) A.returns_out += bN;
+        if (A.stats_out) A.stats_out += 2 * blockIdx.y;
+        if (A.next_actions) A.next_actions += bN * a;
+    }
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int nch = (N + ELITE_CHUNK - 1) / ELITE_CHUNK;
     const int n2 = (nch + ELITE_CHUNK - 1) / ELITE_CHUNK;
@@ -95,7 +117,7 @@ __global__ void __launch_bounds__(MPPI_THREADS) mppi_update_kernel(const MppiArg
     for (int n = tid; n < N; n += MPPI_THREADS) {
         float r = A.costs[n];
         if (E > 1) {
-            for (int e = 1; e < E; ++e) r = __fadd_rn(r, A.costs[(size_t)e * N + n]);
+            for (int e = 1; e < E; ++e) r = __fadd_rn(r, A.costs[e * cs + n]);
             r = __fdiv_rn(r, (float)E);
         }
         if (lead && A.returns_out) A.returns_out[n] = r;
@@ -178,7 +200,7 @@ __global__ void __launch_bounds__(MPPI_THREADS) mppi_update_kernel(const MppiArg
     } else {
         const int TCH = mppi_tile_chunks(a);
         const int ca = ELITE_CHUNK * a;
-        const float* row = A.actions + (size_t)t * N * a;
+        const float* row = A.actions + (size_t)t * cs * a;
         float* tile = area;
         const int npass = A.update_sigma ? 2 : 1;
         for (int pass = 0; pass < npass; ++pass) {
@@ -274,8 +296,9 @@ __global__ void __launch_bounds__(MPPI_THREADS) mppi_update_kernel(const MppiArg
     __syncthreads();   // next complete
     // ---- row t of the next iteration's proposals for candidate slice j (update_draw, cem.hip)
     const int G = (a + 3) >> 2;
-    const int Dn = A.draw_n;
-    const uint32_t cbase = (uint32_t)A.draw_off;
+    const int Dn = BATCH ? N : A.draw_n;
+    const size_t Dr = BATCH ? cs : (size_t)Dn;          // candidates per row of next_actions
+    const uint32_t cbase = BATCH ? blockIdx.y * (uint32_t)N : (uint32_t)A.draw_off;
     const int NS = (Dn + S - 1) / S, n0 = j * NS, n1 = min(Dn, n0 + NS);
     for (int idx = tid; idx < (n1 - n0) * G; idx += MPPI_THREADS) {
         const int n = n0 + idx / G, g = idx - (idx / G) * G;
@@ -285,7 +308,7 @@ __global__ void __launch_bounds__(MPPI_THREADS) mppi_update_kernel(const MppiArg
         for (int q = 0; q < 4; ++q) {
             const int d = 4 * g + q;
             if (d < a)
-                A.next_actions[((size_t)t * Dn + n) * a + d] = cem_action(next[d], next[a4 + d], z[q], A.lo, A.hi);
+                A.next_actions[((size_t)t * Dr + n) * a + d] = cem_action(next[d], next[a4 + d], z[q], A.lo, A.hi);
         }
     }
 }
@@ -294,9 +317,20 @@ hipError_t launch_mppi_update(const MppiArgs& A, int S, hipStream_t stream) {
     const size_t lds = mppi_update_lds_bytes(A.N, A.a);
     if (A.N < 1 || A.N > MPPI_MAX_N || A.a < 1 || A.a > MPPI_MAX_A || A.H < 1 || S < 1 || lds > (size_t)MPPI_LDS_MAX)
         return hipErrorInvalidValue;
-    hipError_t err = ensure_dynamic_lds(reinterpret_cast<const void*>(&mppi_update_kernel), MPPI_LDS_MAX);
+    hipError_t err = ensure_dynamic_lds(reinterpret_cast<const void*>(&mppi_update_kernel<false>), MPPI_LDS_MAX);
     if (err != hipSuccess) return err;
-    hipLaunchKernelGGL(mppi_update_kernel, dim3(A.H * S), dim3(MPPI_THREADS), lds, stream, A);
+    hipLaunchKernelGGL(mppi_update_kernel<false>, dim3(A.H * S), dim3(MPPI_THREADS), lds, stream, A);
+    return hipGetLastError();
+}
+
+hipError_t launch_mppi_update_batch(const MppiArgs& A, int S, int B, hipStream_t stream) {
+    const size_t lds = mppi_update_lds_bytes(A.N, A.a);   // per problem: one workgroup sees one problem
+    if (A.N < 1 || A.N > MPPI_MAX_N || A.a < 1 || A.a > MPPI_MAX_A || A.H < 1 || S < 1 || B < 1 || B > MPPI_MAX_B ||
+        lds > (size_t)MPPI_LDS_MAX)
+        return hipErrorInvalidValue;
+    hipError_t err = ensure_dynamic_lds(reinterpret_cast<const void*>(&mppi_update_kernel<true>), MPPI_LDS_MAX);
+    if (err != hipSuccess) return err;
+    hipLaunchKernelGGL(mppi_update_kernel<true>, dim3(A.H * S, B), dim3(MPPI_THREADS), lds, stream, A);
     return hipGetLastError();
 }
 
@@ -322,6 +356,13 @@ int mppi_range_check(int N, int a) {
     if (N > MPPI_MAX_N || a > MPPI_MAX_A)
         return fail(MBRL_EUNSUPPORTED, "mppi: N=%d a=%d exceeds the update kernel (N <= %d, a <= %d)", N, a, MPPI_MAX_N,
                     MPPI_MAX_A);
+    return MBRL_OK;
+}
+
+int mppi_batch_check(int B, int N) {
+    if (B < 1) return fail(MBRL_EINVAL, "mppi: B=%d must be >= 1", B);
+    if (B > MPPI_MAX_B) return fail(MBRL_EUNSUPPORTED, "mppi: B=%d exceeds %d", B, MPPI_MAX_B);
+    if ((int64_t)B * N > INT32_MAX / 2) return fail(MBRL_EUNSUPPORTED, "mppi: B*N too large");
     return MBRL_OK;
 }
 
@@ -351,3 +392,22 @@ extern "C" int mbrl_mppi_update(const float* costs, int32_t E, int32_t N, const 
     return hip_check(launch_mppi_update(U, S, reinterpret_cast<hipStream_t>(stream)), "mppi update launch");
 }
 
+extern "C" int mbrl_mppi_update_batch(const float* costs, int32_t E, int32_t N, int32_t B, const float* actions,
+                                      const mbrl_sampler* sampler, int32_t H, int32_t a, float temperature, float alpha,
+                                      int32_t update_sigma, float* mu_out, float* sigma_out, float* weights_out,
+                                      float* returns_out, float* stats_out, float* next_actions, mbrl_stream_t stream) {
+    if (!costs || !actions || !sampler || !sampler->mu || !sampler->sigma || !mu_out || !sigma_out)
+        return fail(MBRL_EINVAL, "mppi_update_batch: NULL argument");
+    if (N < 1 || E < 1 || H < 1 || a < 1) return fail(MBRL_EINVAL, "mppi_update_batch: need N (%d), E, H, a >= 1", N);
+    if (int rc = mppi_temperature_check(temperature)) return rc;
+    if (next_actions == actions)
+        return fail(MBRL_EINVAL,
+                    "mppi_update_batch: next_actions must not be the actions buffer (other workgroups still read it)");
+    if (int rc = mppi_range_check(N, a)) return rc;
+    if (int rc = mppi_batch_check(B, N)) return rc;
+    MppiArgs U = make_mppi_args(costs, E, N, H, a, actions, *sampler, temperature, alpha, update_sigma, mu_out, sigma_out);
+    U.weights_out = weights_out; U.returns_out = returns_out; U.stats_out = stats_out;
+    U.next_actions = next_actions;
+    const int S = next_actions ? draw_slices(H, B, N, a) : 1;
+    return hip_check(launch_mppi_update_batch(U, S, B, reinterpret_cast<hipStream_t>(stream)), "mppi batched update launch");
+}

@@ -1,7 +1,7 @@
 // The plans: host dispatch of the rollout and trajectory kernels (rollout_impl, traj_impl), the plan
 // workspaces, the helpers the plan loops share (mbrl_plan.h) and the single-GPU plan entries
 // (include/mbrl_cem.h): rollout cost, trajectory, CEM plan, receding-horizon CEM plan, MPPI plan, batched
-// CEM plan, batched receding-horizon CEM plan, and the two receding-horizon plans with a noise mix.
+// CEM plan, batched MPPI plan, batched receding-horizon CEM plan, and the two receding-horizon plans with a noise mix.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -718,12 +718,12 @@ static int batch_size_check(int B, const mbrl_cem_params* p) {
 
 // Each problem's final mean rolled out: its states (the cooperative trajectory kernel), one launch each.
 static int batch_final_trajectories(const Geometry& g, const void* packed, const mbrl_norm* norm, const float* s0, int B,
-                                    int H, const float* actions_out, float* states_out, const BatchWs& w,
-                                    hipStream_t stream) {
+                                    int H, const float* actions_out, float* states_out, float* member_scratch,
+                                    const TrajScratch& ts, hipStream_t stream) {
     const size_t Hs = (size_t)H * g.s;
     for (int b = 0; b < B; ++b) {
         int rc = final_trajectory(g, packed, norm, s0 + (size_t)b * g.s, actions_out + (size_t)b * H * g.a, H,
-                                  states_out + b * Hs, w.states, w.traj, stream, 0);
+                                  states_out + b * Hs, member_scratch, ts, stream, 0);
         if (rc) return rc;
     }
     return hip_check(hipGetLastError(), "batched plan launch");
@@ -789,7 +789,7 @@ static int cem_batch_run(const Geometry& g, const void* packed, const mbrl_norm*
         if (rc) return rc;
         cur ^= 1;
     }
-    return batch_final_trajectories(g, packed, norm, s0, B, p->H, actions_out, states_out, w, stream);
+    return batch_final_trajectories(g, packed, norm, s0, B, p->H, actions_out, states_out, w.states, w.traj, stream);
 }
 
 int mbrl_cem_plan_batch(const mbrl_mlp_shape* shape, const void* packed, const mbrl_norm* norm, const mbrl_cost* cost,
@@ -808,6 +808,111 @@ int mbrl_cem_plan_batch(const mbrl_mlp_shape* shape, const void* packed, const m
     if (ws_bytes < w.bytes) return fail(MBRL_EWORKSPACE, "workspace %zu < %zu", ws_bytes, w.bytes);
     return cem_batch_run(g, packed, norm, cost, s0, B, p, nullptr, nullptr, nullptr, mu, sigma, actions_out, states_out,
                          nullptr, nullptr, nullptr, w, stream);
+}
+
+// ---- batched MPPI: B independent mbrl_mppi_plan plans in shared launches (BatchWs without the selection's
+// scratch; actions[2] as MppiWs: where the update draws the next proposals they go to the other buffer).
+struct MppiBatchWs {
+    float *costs, *actions[2], *mu[2], *sigma[2], *s0x, *states;
+    TrajScratch traj;
+    size_t bytes;
+};
+
+static MppiBatchWs mppi_batch_ws(const Geometry& g, const mbrl_mppi_params* p, int B, void* base) {
+    MppiBatchWs w{};
+    WsCursor c(base);
+    const size_t BN = (size_t)B * p->N, BHa = (size_t)B * p->H * g.a;
+    w.traj = take_traj_scratch(c, g);   // memset block first, status right behind
+    w.costs = c.take<float>((size_t)g.E * BN * 4);
+    w.actions[0] = c.take<float>((size_t)p->H * BN * g.a * 4);
+    w.actions[1] = update_samples(p->N, g.a) ? c.take<float>((size_t)p->H * BN * g.a * 4) : w.actions[0];
+    w.mu[0] = c.take<float>(BHa * 4); w.mu[1] = c.take<float>(BHa * 4);
+    w.sigma[0] = c.take<float>(BHa * 4); w.sigma[1] = c.take<float>(BHa * 4);
+    w.s0x = c.take<float>(BN * g.s * 4);
+    w.states = c.take<float>((size_t)g.E * p->H * g.s * 4);
+    w.bytes = c.off;
+    return w;
+}
+
+// What mbrl_mppi_batch_workspace_bytes answers and the plan demands: the larger of the batched layout and
+// mbrl_mppi_plan's (which may hold a pair area the batch has no use for), so that the answer never shrinks
+// as B grows and at B == 1 one query serves either entry.
+static size_t mppi_batch_ws_bytes(const Geometry& g, const mbrl_mppi_params* p, int B) {
+    const size_t batch = mppi_batch_ws(g, p, B, nullptr).bytes;
+    const size_t single = mppi_ws(g, p, nullptr).bytes;
+    return single > batch ? single : batch;
+}
+
+size_t mbrl_mppi_batch_workspace_bytes(const mbrl_mlp_shape* shape, const mbrl_mppi_params* params, int32_t B) {
+    Geometry g;
+    if (shape_geometry(shape, &g) != MBRL_OK || mppi_params_check(params) != MBRL_OK || B < 1) return 0;
+    return mppi_batch_ws_bytes(g, params, B);
+}
+
+// The first launch (rh_init_kernel: each problem's initial mean from its rows or init_mu, sigma, the start
+// states expanded to one per candidate and, where the update draws, iteration 0's proposals), then per
+// iteration one rollout over the B N candidates and one update over the B problems (grid (H S, B)), then
+// each problem's final mean rolled out, one trajectory launch each.
+int mbrl_mppi_plan_batch(const mbrl_mlp_shape* shape, const void* packed, const mbrl_norm* norm, const mbrl_cost* cost,
+                         const float* s0, int32_t B, const mbrl_mppi_params* p, const float* init_mu_rows,
+                         const int32_t* input_flags, float* mu, float* sigma, float* actions_out, float* states_out,
+                         float* cost_hist, float* weight_hist, float* mu_hist, float* sigma_hist, void* workspace,
+                         size_t ws_bytes, mbrl_stream_t stream_) {
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    Geometry g;
+    int rc = shape_geometry(shape, &g);
+    if (rc) return rc;
+    if ((rc = mppi_params_check(p))) return rc;
+    if (B < 1) return fail(MBRL_EINVAL, "mppi_plan_batch: B=%d", B);
+    if (!packed || !s0 || !actions_out || !states_out || !workspace)
+        return fail(MBRL_EINVAL, "mppi_plan_batch: packed/s0/actions_out/states_out/workspace NULL");
+    if ((rc = mppi_range_check(p->N, g.a))) return rc;
+    if ((rc = mppi_batch_check(B, p->N))) return rc;
+    const MppiBatchWs w = mppi_batch_ws(g, p, B, workspace);
+    if (const size_t need = mppi_batch_ws_bytes(g, p, B); ws_bytes < need)
+        return fail(MBRL_EWORKSPACE, "mppi_plan_batch: workspace %zu < %zu", ws_bytes, need);
+    const int N = p->N, BN = B * N;
+    const size_t BHa = (size_t)B * p->H * g.a;
+    // the update draws the next proposals itself where mbrl_mppi_plan's would (update_samples, per problem)
+    const bool fuse_draw = update_samples(N, g.a);
+    const int S = fuse_draw ? draw_slices(p->H, B, N, g.a) : 1;
+    {
+        RhInitArgs A{};
+        A.seed = p->seed; A.init_mu = p->init_mu; A.init_sigma = p->init_sigma; A.lo = p->lo; A.hi = p->hi;
+        A.H = p->H; A.a = g.a; A.N = N; A.s = g.s; A.B = B; A.s0_rep = N; A.mu_rows = init_mu_rows; A.flags = input_flags;
+        A.mu = w.mu[0]; A.sigma = w.sigma[0]; A.actions = fuse_draw ? w.actions[0] : nullptr;
+        A.s0_src = s0; A.s0_dst = w.s0x;
+        if ((rc = hip_check(launch_rh_init(A, stream), "init launch"))) return rc;
+    }
+    auto record = [&](int row, int cur) {   // every problem's distribution after `row` updates into the history
+        hipError_t e = hipSuccess;
+        if (mu_hist) e = hipMemcpyAsync(mu_hist + row * BHa, w.mu[cur], BHa * 4, hipMemcpyDeviceToDevice, stream);
+        if (e == hipSuccess && sigma_hist)
+            e = hipMemcpyAsync(sigma_hist + row * BHa, w.sigma[cur], BHa * 4, hipMemcpyDeviceToDevice, stream);
+        return hip_check(e, "history copy");
+    };
+    if ((rc = record(0, 0))) return rc;
+    int cur = 0;
+    for (int it = 0; it < p->iterations; ++it) {
+        const mbrl_sampler sp = make_sampler(p, it, w.mu[cur], w.sigma[cur]);
+        float* costs = cost_hist ? cost_hist + (size_t)it * g.E * BN : w.costs;
+        float* acts = w.actions[fuse_draw ? (it & 1) : 0];   // this iteration's proposals
+        // problem b's candidate n is global candidate b*N + n (its Philox counter)
+        if (!fuse_draw && (rc = sample_impl(&sp, p->H, g.a, BN, 0, acts, stream, N))) return rc;
+        rc = rollout_impl(g, packed, norm, cost, w.s0x, 1, acts, nullptr, BN, p->H, 0, costs, nullptr, nullptr, stream);
+        if (rc) return rc;
+        const bool last = it + 1 == p->iterations;   // the last update also writes mu / sigma / clip(mu)
+        MppiArgs U = make_mppi_args(costs, g.E, N, p->H, g.a, acts, sp, p->temperature, p->alpha, p->update_sigma,
+                                    w.mu[cur ^ 1], w.sigma[cur ^ 1]);
+        U.fin_mu = last ? mu : nullptr; U.fin_sigma = last ? sigma : nullptr; U.fin_actions = last ? actions_out : nullptr;
+        U.weights_out = weight_hist ? weight_hist + (size_t)it * BN : nullptr;
+        U.next_actions = (fuse_draw && !last) ? w.actions[(it + 1) & 1] : nullptr;
+        rc = hip_check(launch_mppi_update_batch(U, U.next_actions ? S : 1, B, stream), "mppi batched update launch");
+        if (rc) return rc;
+        cur ^= 1;
+        if ((rc = record(it + 1, cur))) return rc;
+    }
+    return batch_final_trajectories(g, packed, norm, s0, B, p->H, actions_out, states_out, w.states, w.traj, stream);
 }
 
 // ---- receding-horizon CEM, single and batched, white and mixed (include/mbrl_cem.h mbrl_cem_plan_rh,

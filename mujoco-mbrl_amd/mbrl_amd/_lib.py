@@ -71,6 +71,7 @@ EXPORTED = (
     "mbrl_cem_rh_batch_workspace_bytes", "mbrl_cem_plan_rh_batch",
     "mbrl_sample_actions_mixed", "mbrl_cem_rh_mixed_workspace_bytes", "mbrl_cem_plan_rh_mixed",
     "mbrl_cem_plan_rh_batch_mixed",
+    "mbrl_mppi_update_batch", "mbrl_mppi_batch_workspace_bytes", "mbrl_mppi_plan_batch",
 )
 
 
@@ -204,6 +205,11 @@ def load():
         "mbrl_mppi_workspace_bytes": (c_size_t, [POINTER(MlpShape), POINTER(MppiParams)]),
         "mbrl_mppi_plan": (c_int32, [POINTER(MlpShape), P, POINTER(Norm), POINTER(Cost), P, POINTER(MppiParams), P,
                                      P, P, P, P, P, P, P, P, P, P, c_size_t, P]),
+        "mbrl_mppi_update_batch": (c_int32, [P, c_int32, c_int32, c_int32, P, POINTER(Sampler), c_int32, c_int32,
+                                             c_float, c_float, c_int32, P, P, P, P, P, P, P]),
+        "mbrl_mppi_batch_workspace_bytes": (c_size_t, [POINTER(MlpShape), POINTER(MppiParams), c_int32]),
+        "mbrl_mppi_plan_batch": (c_int32, [POINTER(MlpShape), P, POINTER(Norm), POINTER(Cost), P, c_int32,
+                                           POINTER(MppiParams), P, P, P, P, P, P, P, P, P, P, P, c_size_t, P]),
         "mbrl_cem_rh_workspace_bytes": (c_size_t, [POINTER(MlpShape), POINTER(CemRhParams)]),
         "mbrl_cem_plan_rh": (c_int32, [POINTER(MlpShape), P, POINTER(Norm), POINTER(Cost), P, POINTER(CemRhParams),
                                        P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, c_size_t, P]),

@@ -646,6 +646,24 @@ def mppi_update(costs, actions, sampler, H, a, temperature, alpha, update_sigma,
                                     _lib.stream_handle(costs.device)), "mbrl_mppi_update")
 
 
+def mppi_update_batch(costs, actions, sampler, B, H, a, temperature, alpha, update_sigma, mu_out, sigma_out,
+                      weights_out=None, returns_out=None, stats_out=None, next_actions=None):
+    """mbrl_mppi_update_batch: mppi_update for B problems in one launch. costs: [E, B*N], problem b's columns
+    [b*N, (b+1)*N); actions (and the optional next_actions, another buffer): [H, B*N, a]; the sampler's mu /
+    sigma and mu_out / sigma_out: [B, H, a]; weights_out / returns_out: [B, N]; stats_out: [B, 2]. Problem b's
+    next proposals are drawn with Philox candidate index b*N + n."""
+    lib = _lib.load()
+    E, BN = costs.shape
+    B = int(B)
+    if B < 1 or BN % B:
+        raise ValueError(f"costs have {BN} columns for B={B} problems")
+    _lib.check(lib.mbrl_mppi_update_batch(_lib.ptr(costs), E, BN // B, B, _lib.ptr(actions), ctypes_ref(sampler), H, a,
+                                          float(temperature), float(alpha), int(bool(update_sigma)), _lib.ptr(mu_out),
+                                          _lib.ptr(sigma_out), _lib.ptr(weights_out), _lib.ptr(returns_out),
+                                          _lib.ptr(stats_out), _lib.ptr(next_actions),
+                                          _lib.stream_handle(costs.device)), "mbrl_mppi_update_batch")
+
+
 def make_sampler(seed, iteration, mu, sigma, lo, hi):
     return _lib.Sampler(int(seed) & 0xFFFFFFFFFFFFFFFF, int(iteration), 0, _lib.ptr(mu), _lib.ptr(sigma),
                         float(lo), float(hi))

@@ -22,6 +22,8 @@ RecedingHorizonCEMPlanner -- CEMPlanner with warm start and elite carry-over on 
     (mbrl_cem_plan_rh_batch) keeps each problem's kept rows between control steps through memos.
 MPPIPlanner           -- CEM's loop with a softmax-weighted refit over every candidate in place of
     the elite cut (mbrl_mppi_plan), warm-started from the previous plan.
+BatchedMPPIPlanner    -- MPPIPlanner with a plan_batch (mppi_plan_batch, mbrl_mppi_plan_batch): B warm-started
+    plans in shared launches, the class a served policy uses.
 GradientDescentPlanner -- the reference's Adam loop on one action sequence (planners.py:28-137).
 
 All four take the fused path when fused.describe_* (gd.describe) recognise the model / cost closures;
@@ -1413,8 +1415,8 @@ class MPPIPlanner(ModelPlanner):
 
     plan returns (predicted states of the clipped final mean, the clipped final mean); plan_detailed
     adds mu, sigma and, with record=True, costs [I, E, N], weights [I, N], mu_hist / sigma_hist
-    [I + 1, H, a] (row 0 the initial distribution). distributed=True and plan_batch are not implemented
-    for MPPI (NotImplementedError)."""
+    [I + 1, H, a] (row 0 the initial distribution). distributed=True and this class's plan_batch are not
+    implemented (NotImplementedError); the batched form is mppi_plan_batch / BatchedMPPIPlanner."""
     defaults = dict(num_candidates=1000, num_iterations=1, temperature=1.0, alpha=0.0, update_sigma=False,
                     init_std=None, action_bounds=None, seed=None, shift=1, return_device=False, precision="f32",
                     distributed=False)
@@ -1524,3 +1526,80 @@ def _mppi_generic(model, cost, s0, st, a, dev, rows):
     sigma0 = torch.full((H, a), st["init_std"], dtype=torch.float32, device=dev)     # (row 0 of sigma_hist)
     return _generic_plan(model, cost, s0, st, a, dev, mu, update,
                          dict(costs=[], weights=[], mu_hist=[mu.clone()], sigma_hist=[sigma0]))
+
+
+def mppi_plan_batch(initial_states, model, cost, sample_action, horizon, initial_trajectories=None, **kwargs):
+    """B independent MPPI plans in shared launches (mbrl_mppi_plan_batch): one per row of initial_states
+    [B, s], each with its own warm start, so one GPU planner serves B environments that are each somewhere in
+    their own episode. kwargs as MPPIPlanner.plan; num_candidates is per problem. initial_trajectories is a list
+    of B entries, each None (that problem starts from a zero mean: its first control step) or (states, actions)
+    of its previous plan, shifted per row with mppi_warm_start_rows. Problem b draws its proposals as
+    candidates [b*N, (b+1)*N) of one Philox stream; problem 0 is MPPIPlanner.plan_detailed bit for bit.
+
+    Returns a dict: states [B, H, s], actions, mu, sigma [B, H, a]; record=True adds costs [I, E, B*N],
+    weights [I, B, N] and mu_hist / sigma_hist [I + 1, B, H, a]. Host tensors unless return_device.
+    distributed, noise_beta and noise_mix are refused as MPPIPlanner refuses them, and a list that is not B
+    long raises ValueError, before anything touches the device. Closures the fused path does not recognise
+    fall back to one MPPIPlanner plan per row."""
+    _noise_refuse(kwargs, "mppi_plan_batch")
+    st = MPPIPlanner._settings_build(sample_action, horizon, kwargs)
+    B = int(initial_states.shape[0])
+    if B < 1:
+        raise ValueError("mppi_plan_batch needs at least one initial state")
+    inits = _per_row(initial_trajectories, B, "initial_trajectories")
+    rows = [None if x is None else mppi_warm_start_rows(x[1], st["H"], st["shift"], st["lo"], st["hi"]) for x in inits]
+    dev = _device(kwargs)
+    keep, rec = st["keep"], st["record"]
+    with torch.cuda.device(dev):
+        mdesc, cdesc, prob = fused.describe_problem(model, cost, dev, st["precision"])
+        if mdesc is None or cdesc is None:
+            kw = dict(kwargs, seed=st["seed"], return_device=True)
+            outs = [MPPIPlanner.plan_detailed(initial_states[b], model, cost, sample_action, horizon, inits[b], **kw)
+                    for b in range(B)]
+            out = {k: torch.stack([o[k] for o in outs]) for k in ("states", "actions", "mu", "sigma")}
+            if rec:
+                out.update(costs=torch.cat([o["costs"] for o in outs], 2),
+                           **{k: torch.stack([o[k] for o in outs], 1) for k in ("weights", "mu_hist", "sigma_hist")})
+            return {k: _to_host(v, keep) for k, v in out.items()}
+        lib = _lib.load()
+        N, H, I = st["N"], st["H"], st["I"]
+        a, s, E = mdesc["a"], mdesc["s"], mdesc["E"]
+        for b, r in enumerate(rows):
+            if r is not None and r.shape[1] != a:
+                raise ValueError(f"row {b}: initial_trajectory actions have {r.shape[1]} dims, the model {a}")
+        rows_d = flags_d = None
+        if any(r is not None for r in rows):
+            stacked = np.stack([np.zeros((H, a), np.float32) if r is None else r for r in rows])
+            rows_d = torch.from_numpy(np.ascontiguousarray(stacked)).to(dev)
+            flags_d = torch.tensor([0 if r is None else RH_FLAG_MU for r in rows], dtype=torch.int32).to(dev)
+        params = _lib.MppiParams(N, H, I, int(st["update_sigma"]), st["temperature"], st["alpha"], st["lo"], st["hi"],
+                                 0.0, st["init_std"], int(st["seed"]) & 0xFFFFFFFFFFFFFFFF)
+        need = lib.mbrl_mppi_batch_workspace_bytes(fused.ctypes_ref(prob.shape), fused.ctypes_ref(params), B)
+        if need == 0:
+            _lib.check(_lib.MBRL_EINVAL, "mbrl_mppi_batch_workspace_bytes")
+        ws = _workspace(("mppi_batch", str(dev)), need, dev)
+        s0 = initial_states.to(device=dev, dtype=torch.float32).reshape(B, s).contiguous()
+        e = lambda *sh: torch.empty(sh, dtype=torch.float32, device=dev)  # noqa: E731
+        out = dict(states=e(B, H, s), actions=e(B, H, a), mu=e(B, H, a), sigma=e(B, H, a))
+        if rec:
+            out.update(costs=e(I, E, B * N), weights=e(I, B, N), mu_hist=e(I + 1, B, H, a), sigma_hist=e(I + 1, B, H, a))
+        g = lambda k: _lib.ptr(out.get(k))  # noqa: E731
+        _lib.check(lib.mbrl_mppi_plan_batch(*prob.refs, _lib.ptr(s0), B, fused.ctypes_ref(params), _lib.ptr(rows_d),
+                                            _lib.ptr(flags_d), g("mu"), g("sigma"), g("actions"), g("states"),
+                                            g("costs"), g("weights"), g("mu_hist"), g("sigma_hist"), _lib.ptr(ws),
+                                            ws.numel(), _lib.stream_handle(dev)), "mbrl_mppi_plan_batch")
+        return {k: _to_host(v, keep) for k, v in out.items()}
+
+
+class BatchedMPPIPlanner(MPPIPlanner):
+    """MPPIPlanner with a batched form, so the planner service (parallel.get_rollouts_parallel) answers a whole
+    round of requests with one mppi_plan_batch call and warm-starts every rollout it serves from that rollout's
+    own previous plan. plan() is MPPIPlanner.plan."""
+    # the planner service passes each rollout's previous plan (initial_trajectories)
+    warm_starts = True
+
+    @staticmethod
+    def plan_batch(initial_states, model, cost, sample_action, horizon, initial_trajectories=None, **kwargs):
+        """B plans at once; returns (states [B, H, s], actions [B, H, a])."""
+        res = mppi_plan_batch(initial_states, model, cost, sample_action, horizon, initial_trajectories, **kwargs)
+        return res["states"], res["actions"]
