@@ -33,7 +33,9 @@ extern "C" {
  * or option changed, so the version did not move. The receding-horizon CEM plan (mbrl_cem_rh_params,
  * mbrl_cem_rh_workspace_bytes, mbrl_cem_plan_rh) joined them the same way, and its batched form
  * (mbrl_cem_rh_batch_workspace_bytes, mbrl_cem_plan_rh_batch) after it, then batched MPPI
- * (mbrl_mppi_update_batch, mbrl_mppi_batch_workspace_bytes, mbrl_mppi_plan_batch). */
+ * (mbrl_mppi_update_batch, mbrl_mppi_batch_workspace_bytes, mbrl_mppi_plan_batch), then MPPI over the K best
+ * (mbrl_mppi_elite_params, mbrl_mppi_update_elite, mbrl_mppi_update_elite_batch,
+ * mbrl_mppi_elite_workspace_bytes, mbrl_mppi_plan_elite, mbrl_mppi_plan_elite_batch). */
 #define MBRL_ABI_VERSION 13
 
 typedef struct ihipStream_t* mbrl_stream_t; /* == hipStream_t */
@@ -480,6 +482,86 @@ int mbrl_mppi_plan_batch(const mbrl_mlp_shape* shape, const void* packed, const 
                          const int32_t* input_flags, float* mu, float* sigma, float* actions_out, float* states_out,
                          float* cost_hist, float* weight_hist, float* mu_hist, float* sigma_hist, void* workspace,
                          size_t ws_bytes, mbrl_stream_t stream);
+
+/* ---- MPPI over the K best (the TD-MPC-style update: elite-restricted weights and a sigma clamp; not in the
+ * reference; added within ABI v13, additively: no existing entry, struct or option changes, no new option id).
+ * One iteration's update with K in [1, N] and 0 <= sigma_min <= sigma_max (+inf allowed):
+ *   r_n   = member-mean return, exactly as mbrl_select_elites / mbrl_mppi_update form it;
+ *   elite = the K smallest (r_n, n) pairs under MBRL_NAN_LAST -- what mbrl_select_elites returns: a stable
+ *           order, so a tie at the boundary goes to the lower index;
+ *   n is valid iff it is an elite AND r_n is finite (with fewer than K finite returns the selection holds NaN
+ *           or inf rows; those stay invalid. -inf sorts first: it can fill the elite set with invalid rows);
+ *   beta, x_n, w_n = expf(-x_n) as mbrl_mppi_update for valid n; w_n = 0 for every other n;
+ *   eta, m, v are summed over ALL N candidates in mbrl_mppi_update's canonical 32-chunk order, the zero weights
+ *           taking part as zeros: the order still depends on N alone;
+ *   mu' as mbrl_mppi_update; with update_sigma
+ *           sigma' = min(max(sqrt(alpha sigma^2 + (1 - alpha) v), sigma_min), sigma_max)
+ *           (sigma_min = 0, sigma_max = +inf change no bit); without it sigma is copied unclamped (classic MPPI);
+ *   no valid candidate: mu and sigma are copied bit for bit.
+ * So K = N with the neutral clamp is mbrl_mppi_update byte for byte (every output), and K = 1 with alpha = 0
+ * gives mu'[t][d] == the best candidate's proposal row. A large temperature with K < N is CEM's elite mean.
+ *
+ * mbrl_mppi_update_elite: TWO launches -- the selection (mbrl_select_elites' kernel), then the update kernel,
+ * which builds an N-bit membership map from the list and zeroes every non-member's weight (csrc/mppi.hip).
+ * Arguments as mbrl_mppi_update, plus K, the clamp, and
+ *   elite_idx_out [K] int64 or NULL: the elite set in ascending candidate index (as mbrl_select_elites);
+ *   weights_out [N]: 0 for non-elites; returns_out [N]: the true returns of all N; stats_out [2] = (beta, eta);
+ *   workspace >= mbrl_select_workspace_bytes(N); with elite_idx_out == NULL the list lives behind it:
+ *   8 K bytes rounded up to 256 more.
+ * Before any launch: mbrl_mppi_update's checks; NULL workspace, K outside [1, N], sigma_min < 0,
+ * sigma_max < sigma_min or a NaN clamp: MBRL_EINVAL; a workspace that is too small: MBRL_EWORKSPACE. */
+int mbrl_mppi_update_elite(const float* costs, int32_t E, int32_t N, int32_t K, const float* actions,
+                           const mbrl_sampler* sampler, int32_t H, int32_t a, float temperature, float alpha,
+                           int32_t update_sigma, float sigma_min, float sigma_max, float* mu_out, float* sigma_out,
+                           int64_t* elite_idx_out, float* weights_out, float* returns_out, float* stats_out,
+                           float* next_actions, int32_t draw_offset, int32_t draw_count, void* workspace,
+                           size_t ws_bytes, mbrl_stream_t stream);
+
+/* mbrl_mppi_update_elite_batch: the same for B problems, laid out as mbrl_mppi_update_batch's; elite_idx_out
+ * [B][K] (indices local to the problem) or NULL. Two launches whatever B is: the segmented selection, then the
+ * update over grid (H S, B). Problem b equals mbrl_mppi_update_elite on contiguous copies of its slices, bit for
+ * bit. workspace >= mbrl_select_workspace_bytes(B N), plus 8 B K bytes rounded up to 256 without elite_idx_out.
+ * Checks: the two siblings'; a workspace that is too small: MBRL_EWORKSPACE. */
+int mbrl_mppi_update_elite_batch(const float* costs, int32_t E, int32_t N, int32_t K, int32_t B, const float* actions,
+                                 const mbrl_sampler* sampler, int32_t H, int32_t a, float temperature, float alpha,
+                                 int32_t update_sigma, float sigma_min, float sigma_max, float* mu_out,
+                                 float* sigma_out, int64_t* elite_idx_out, float* weights_out, float* returns_out,
+                                 float* stats_out, float* next_actions, void* workspace, size_t ws_bytes,
+                                 mbrl_stream_t stream);
+
+/* The plans: mbrl_mppi_plan / mbrl_mppi_plan_batch with each iteration as rollout -> selection -> restricted
+ * update (the next proposals' draw stays fused in the update launch wherever the classic plan fuses it; no
+ * launch inside the loop is per problem), and two more inputs:
+ *   init_sigma_rows [H][a] ([B][H][a]) device or NULL: row t of the initial std instead of params->mppi.init_sigma
+ *     -- the previous plan's sigma carried to the next control step, which the clamp makes safe. Every entry
+ *     finite and > 0: the CALLER'S check, as for mbrl_cem_plan_rh (Python makes it on the host). In the batch,
+ *     bit 1 of input_flags[b] governs them as in mbrl_cem_plan_rh_batch (bit 0: init_mu_rows);
+ *   elite_hist [I][K] ([I][B][K], local indices) int64 or NULL: each iteration's elite set.
+ * Everything else -- outputs, records, mapped host memory for the single plan, the Philox counter space -- is the
+ * sibling's. Problem 0 of a batch and a B = 1 batch are mbrl_mppi_plan_elite bit for bit.
+ * mbrl_mppi_elite_workspace_bytes(shape, params, B) sizes both plans (B = 1: the single plan and a batch of one):
+ * 0 for a bad shape, bad params (K and the clamp included) or B < 1; it never shrinks as B grows and is never
+ * below mbrl_mppi_batch_workspace_bytes(shape, &params->mppi, B).
+ * Before any launch: the siblings' checks and codes (a small workspace: MBRL_EINVAL from the single plan,
+ * MBRL_EWORKSPACE from the batch), K outside [1, N], sigma_min < 0, sigma_max < sigma_min, a NaN clamp: MBRL_EINVAL. */
+typedef struct {
+    mbrl_mppi_params mppi;
+    int32_t K;             /* elites, 1 .. N */
+    int32_t _pad;
+    float sigma_min, sigma_max; /* clamp on sigma' (update_sigma only): 0 <= sigma_min <= sigma_max, +inf allowed */
+} mbrl_mppi_elite_params;
+size_t mbrl_mppi_elite_workspace_bytes(const mbrl_mlp_shape* shape, const mbrl_mppi_elite_params* params, int32_t B);
+int mbrl_mppi_plan_elite(const mbrl_mlp_shape* shape, const void* packed, const mbrl_norm* norm, const mbrl_cost* cost,
+                         const float* s0, const mbrl_mppi_elite_params* params, const float* init_mu_rows,
+                         const float* init_sigma_rows, float* mu, float* sigma, float* actions_out, float* states_out,
+                         float* cost_hist, float* weight_hist, float* mu_hist, float* sigma_hist, int64_t* elite_hist,
+                         mbrl_event_t* rollout_events, void* workspace, size_t ws_bytes, mbrl_stream_t stream);
+int mbrl_mppi_plan_elite_batch(const mbrl_mlp_shape* shape, const void* packed, const mbrl_norm* norm,
+                               const mbrl_cost* cost, const float* s0, int32_t B, const mbrl_mppi_elite_params* params,
+                               const float* init_mu_rows, const float* init_sigma_rows, const int32_t* input_flags,
+                               float* mu, float* sigma, float* actions_out, float* states_out, float* cost_hist,
+                               float* weight_hist, float* mu_hist, float* sigma_hist, int64_t* elite_hist,
+                               void* workspace, size_t ws_bytes, mbrl_stream_t stream);
 
 /* ---- receding-horizon CEM plan (warm start and elite carry-over, the two iCEM ingredients of Pinneri
  * et al. 2020; not in the reference; added within ABI v13, additively, as the MPPI calls were).

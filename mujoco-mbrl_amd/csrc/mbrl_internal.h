@@ -485,6 +485,19 @@ hipError_t launch_mppi_update_batch(const MppiArgs& A, int S, int B, hipStream_t
 // all N candidates; the caller adds the fin_* / *_out diagnostics and the next proposals' draw.
 MppiArgs make_mppi_args(const float* costs, int E, int N, int H, int a, const float* actions, const mbrl_sampler& sp,
                         float temperature, float alpha, int update_sigma, float* mu_out, float* sigma_out);
+// The elite-restricted update (mbrl_mppi_update_elite): the same kernel with the selection's list. A candidate
+// outside `elites` ([K] ascending local indices; batched [B][K]) is invalid (weight 0, not in beta); with
+// update_sigma the new sigma is clamped to [sigma_min, sigma_max]. B == 0: the single kernel; B >= 1: the
+// batched one, the buffers laid out as launch_mppi_update_batch's.
+struct MppiEliteArgs : MppiArgs {
+    const int64_t* elites;
+    int K;
+    float sigma_min, sigma_max;
+};
+hipError_t launch_mppi_update_elite(const MppiEliteArgs& A, int S, int B, hipStream_t stream);
+MppiEliteArgs make_mppi_elite_args(const MppiArgs& U, const int64_t* elites, int K, float sigma_min, float sigma_max);
+// K in [1, N], 0 <= sigma_min <= sigma_max, no NaN: MBRL_EINVAL otherwise.
+int mppi_elite_check(int N, int K, float sigma_min, float sigma_max);
 // Argument checks of both (MBRL_* code, message set).
 int mppi_temperature_check(float temperature);
 int mppi_range_check(int N, int a);

@@ -25,8 +25,18 @@
 // All arithmetic fp32, correctly rounded, no contraction.
 // The same kernel serves B problems in one launch (mbrl_mppi_update_batch, mbrl_mppi_plan_batch): grid
 // (H * S, B), each workgroup on one problem's slices of the batch's buffers (mppi_update_kernel<true>).
+//
+// Elite-restricted form (mbrl_mppi_update_elite, DESIGN.md "MPPI over the K best"): the same kernel over
+// MppiEliteArgs. The stable top-K of the returns comes from the selection launch before it (select_impl, one
+// segment per problem); every workgroup turns the list into an N-bit membership map in LDS (in the tile
+// weights' area, which phase 1 does not use), a candidate outside it counts as invalid -- it stays out of
+// beta and its weight is 0, so it takes part in every sum as a zero and the summation order is unchanged --
+// and sigma' is clamped to [sigma_min, sigma_max] where update_sigma writes it. MppiArgs instantiations
+// compile to the code they had: every addition is under `if constexpr (ELITE)`.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <type_traits>
 
 #include "mbrl_host.h"
 #include "mbrl_rng.h"
@@ -74,9 +84,11 @@ __device__ __forceinline__ float mppi_unkey(uint32_t k) {
 // drawn with Philox index b N + n), its distribution mu / sigma [B][H][a]; weights / returns [B][N], stats
 // [B][2]. Every offset below is uniform over the workgroup; the arithmetic is the single kernel's, over the
 // problem's own N (chunks counted from its candidate 0). BATCH = false compiles to the single-problem kernel.
-template <bool BATCH>
-__global__ void __launch_bounds__(MPPI_THREADS) mppi_update_kernel(MppiArgs A) {
+// ARGS: MppiArgs, or MppiEliteArgs for the elite-restricted update (elites [K], batched [B][K], local indices).
+template <bool BATCH, class ARGS>
+__global__ void __launch_bounds__(MPPI_THREADS) mppi_update_kernel(ARGS A) {
 #pragma clang fp contract(off)
+    constexpr bool ELITE = std::is_same<ARGS, MppiEliteArgs>::value;
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int S = gridDim.x / A.H;                      // draw slices per row
     const int t = blockIdx.x / S, j = blockIdx.x - (blockIdx.x / S) * S;
@@ -95,6 +107,7 @@ __global__ void __launch_bounds__(MPPI_THREADS) mppi_update_kernel(MppiArgs A) {
         if (A.returns_out) A.returns_out += bN;
         if (A.stats_out) A.stats_out += 2 * blockIdx.y;
         if (A.next_actions) A.next_actions += bN * a;
+        if constexpr (ELITE) A.elites += (size_t)blockIdx.y * A.K;
     }
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int nch = (N + ELITE_CHUNK - 1) / ELITE_CHUNK;
@@ -107,6 +120,18 @@ __global__ void __launch_bounds__(MPPI_THREADS) mppi_update_kernel(MppiArgs A) {
     float* next = mean + a4;                             // [2][a4] mu', sigma' of row t
     float* musg = next + 2 * a4;                         // [2][a4] mu, sigma of row t
     float* area = musg + 2 * a4;
+    // ---- the elites' membership map, bit n & 31 of word n >> 5 (nch <= 1024 words, in wt until the tiles);
+    // an index outside [0, N) sets nothing
+    uint32_t* emap = reinterpret_cast<uint32_t*>(wt);
+    if constexpr (ELITE) {
+        if (tid < nch) emap[tid] = 0u;
+        __syncthreads();
+        for (int k = tid; k < A.K; k += MPPI_THREADS) {
+            const int64_t n = A.elites[k];
+            if ((uint64_t)n < (uint64_t)N) atomicOr(&emap[n >> 5], 1u << (n & 31));
+        }
+        __syncthreads();
+    }
 
     for (int d = tid; d < a; d += MPPI_THREADS) {
         musg[d] = A.mu[t * a + d];
@@ -122,7 +147,7 @@ __global__ void __launch_bounds__(MPPI_THREADS) mppi_update_kernel(MppiArgs A) {
         }
         if (lead && A.returns_out) A.returns_out[n] = r;
         area[n + (n >> 5)] = r;
-        kmin = min(kmin, mppi_key(r));
+        if (!ELITE || ((emap[n >> 5] >> (n & 31)) & 1u)) kmin = min(kmin, mppi_key(r));
     }
     kmin = wave_min_u32(kmin);
     if (lane == 0) wmin[wave] = kmin;
@@ -134,12 +159,13 @@ __global__ void __launch_bounds__(MPPI_THREADS) mppi_update_kernel(MppiArgs A) {
     const float beta = mppi_unkey(km);
     // ---- weights: thread c holds chunk c's
     const int c = tid;
+    const uint32_t member = ELITE ? (c < nch ? emap[c] : 0u) : 0xFFFFFFFFu;   // chunk c's elites
     float w[ELITE_CHUNK];
 #pragma unroll
     for (int q = 0; q < ELITE_CHUNK; ++q) {
         const int n = ELITE_CHUNK * c + q;
         float wq = 0.0f;
-        if (n < N && any) {
+        if (n < N && any && ((member >> q) & 1u)) {
             const float r = area[(ELITE_CHUNK + 1) * c + q];
             if ((__float_as_uint(r) & 0x7F800000u) != 0x7F800000u)
                 wq = expf(-__fdiv_rn(__fadd_rn(r, -beta), A.temperature));
@@ -179,7 +205,13 @@ __global__ void __launch_bounds__(MPPI_THREADS) mppi_update_kernel(MppiArgs A) {
         float mn = mu0, sn = s0;
         if (any) {
             mn = __fadd_rn(__fmul_rn(A.alpha, mu0), __fmul_rn(A.oma, m));
-            if (A.update_sigma) sn = exact_sqrt(__fadd_rn(__fmul_rn(A.alpha, __fmul_rn(s0, s0)), __fmul_rn(A.oma, v)));
+            if (A.update_sigma) {
+                sn = exact_sqrt(__fadd_rn(__fmul_rn(A.alpha, __fmul_rn(s0, s0)), __fmul_rn(A.oma, v)));
+                if constexpr (ELITE) {   // the clamp (comparisons: [0, +inf] changes no bit, -0.0 included)
+                    if (sn < A.sigma_min) sn = A.sigma_min;
+                    if (sn > A.sigma_max) sn = A.sigma_max;
+                }
+            }
         }
         next[d] = mn;
         next[a4 + d] = sn;
@@ -317,9 +349,9 @@ hipError_t launch_mppi_update(const MppiArgs& A, int S, hipStream_t stream) {
     const size_t lds = mppi_update_lds_bytes(A.N, A.a);
     if (A.N < 1 || A.N > MPPI_MAX_N || A.a < 1 || A.a > MPPI_MAX_A || A.H < 1 || S < 1 || lds > (size_t)MPPI_LDS_MAX)
         return hipErrorInvalidValue;
-    hipError_t err = ensure_dynamic_lds(reinterpret_cast<const void*>(&mppi_update_kernel<false>), MPPI_LDS_MAX);
+    hipError_t err = ensure_dynamic_lds(reinterpret_cast<const void*>(&mppi_update_kernel<false, MppiArgs>), MPPI_LDS_MAX);
     if (err != hipSuccess) return err;
-    hipLaunchKernelGGL(mppi_update_kernel<false>, dim3(A.H * S), dim3(MPPI_THREADS), lds, stream, A);
+    hipLaunchKernelGGL((mppi_update_kernel<false, MppiArgs>), dim3(A.H * S), dim3(MPPI_THREADS), lds, stream, A);
     return hipGetLastError();
 }
 
@@ -328,10 +360,45 @@ hipError_t launch_mppi_update_batch(const MppiArgs& A, int S, int B, hipStream_t
     if (A.N < 1 || A.N > MPPI_MAX_N || A.a < 1 || A.a > MPPI_MAX_A || A.H < 1 || S < 1 || B < 1 || B > MPPI_MAX_B ||
         lds > (size_t)MPPI_LDS_MAX)
         return hipErrorInvalidValue;
-    hipError_t err = ensure_dynamic_lds(reinterpret_cast<const void*>(&mppi_update_kernel<true>), MPPI_LDS_MAX);
+    hipError_t err = ensure_dynamic_lds(reinterpret_cast<const void*>(&mppi_update_kernel<true, MppiArgs>), MPPI_LDS_MAX);
     if (err != hipSuccess) return err;
-    hipLaunchKernelGGL(mppi_update_kernel<true>, dim3(A.H * S, B), dim3(MPPI_THREADS), lds, stream, A);
+    hipLaunchKernelGGL((mppi_update_kernel<true, MppiArgs>), dim3(A.H * S, B), dim3(MPPI_THREADS), lds, stream, A);
     return hipGetLastError();
+}
+
+// The elite-restricted update: B == 0 the single kernel (grid H * S), B >= 1 the batched one (grid (H * S, B)).
+// The map needs no LDS of its own (it lives in the tile weights' [32][33] words: nch <= 1024).
+hipError_t launch_mppi_update_elite(const MppiEliteArgs& A, int S, int B, hipStream_t stream) {
+    const size_t lds = mppi_update_lds_bytes(A.N, A.a);
+    if (A.N < 1 || A.N > MPPI_MAX_N || A.a < 1 || A.a > MPPI_MAX_A || A.H < 1 || S < 1 || B < 0 || B > MPPI_MAX_B ||
+        lds > (size_t)MPPI_LDS_MAX || !A.elites || A.K < 1 || A.K > A.N)
+        return hipErrorInvalidValue;
+    if (B == 0) {
+        hipError_t err = ensure_dynamic_lds(reinterpret_cast<const void*>(&mppi_update_kernel<false, MppiEliteArgs>),
+                                            MPPI_LDS_MAX);
+        if (err != hipSuccess) return err;
+        hipLaunchKernelGGL((mppi_update_kernel<false, MppiEliteArgs>), dim3(A.H * S), dim3(MPPI_THREADS), lds, stream, A);
+    } else {
+        hipError_t err = ensure_dynamic_lds(reinterpret_cast<const void*>(&mppi_update_kernel<true, MppiEliteArgs>),
+                                            MPPI_LDS_MAX);
+        if (err != hipSuccess) return err;
+        hipLaunchKernelGGL((mppi_update_kernel<true, MppiEliteArgs>), dim3(A.H * S, B), dim3(MPPI_THREADS), lds, stream, A);
+    }
+    return hipGetLastError();
+}
+
+MppiEliteArgs make_mppi_elite_args(const MppiArgs& U, const int64_t* elites, int K, float sigma_min, float sigma_max) {
+    MppiEliteArgs X{};
+    static_cast<MppiArgs&>(X) = U;
+    X.elites = elites; X.K = K; X.sigma_min = sigma_min; X.sigma_max = sigma_max;
+    return X;
+}
+
+int mppi_elite_check(int N, int K, float sigma_min, float sigma_max) {
+    if (K < 1 || K > N) return fail(MBRL_EINVAL, "mppi: need 1 <= K (%d) <= N (%d)", K, N);
+    if (!(sigma_min >= 0.0f) || !(sigma_max >= sigma_min))   // (a NaN fails either comparison)
+        return fail(MBRL_EINVAL, "mppi: need 0 <= sigma_min (%g) <= sigma_max (%g)", (double)sigma_min, (double)sigma_max);
+    return MBRL_OK;
 }
 
 MppiArgs make_mppi_args(const float* costs, int E, int N, int H, int a, const float* actions, const mbrl_sampler& sp,
@@ -410,4 +477,65 @@ extern "C" int mbrl_mppi_update_batch(const float* costs, int32_t E, int32_t N, 
     U.next_actions = next_actions;
     const int S = next_actions ? draw_slices(H, B, N, a) : 1;
     return hip_check(launch_mppi_update_batch(U, S, B, reinterpret_cast<hipStream_t>(stream)), "mppi batched update launch");
+}
+
+// ---- elite-restricted MPPI (include/mbrl_cem.h "MPPI over the K best"): the selection launch, then the update.
+// The workspace: the selection's keys first, then the elite list where the caller takes none.
+static int mppi_update_elite_run(const float* costs, int E, int N, int K, int B, const float* actions,
+                                 const mbrl_sampler* sampler, int H, int a, float temperature, float alpha,
+                                 int update_sigma, float sigma_min, float sigma_max, float* mu_out, float* sigma_out,
+                                 int64_t* elite_idx_out, float* weights_out, float* returns_out, float* stats_out,
+                                 float* next_actions, int draw_offset, int draw_count, void* workspace, size_t ws_bytes,
+                                 hipStream_t stream, const char* who) {
+    const int nb = B ? B : 1;
+    if (!costs || !actions || !sampler || !sampler->mu || !sampler->sigma || !mu_out || !sigma_out || !workspace)
+        return fail(MBRL_EINVAL, "%s: NULL argument", who);
+    if (N < 1 || E < 1 || H < 1 || a < 1) return fail(MBRL_EINVAL, "%s: need N (%d), E, H, a >= 1", who, N);
+    if (int rc = mppi_temperature_check(temperature)) return rc;
+    if (int rc = mppi_elite_check(N, K, sigma_min, sigma_max)) return rc;
+    if (!B && next_actions && (draw_count < 1 || draw_offset < 0 || (int64_t)draw_offset + draw_count > N))
+        return fail(MBRL_EINVAL, "%s: draw range [%d, %d + %d) outside [0, %d)", who, draw_offset, draw_offset,
+                    draw_count, N);
+    if (next_actions == actions)
+        return fail(MBRL_EINVAL, "%s: next_actions must not be the actions buffer (other workgroups still read it)", who);
+    if (int rc = mppi_range_check(N, a)) return rc;
+    if (B)
+        if (int rc = mppi_batch_check(B, N)) return rc;
+    const size_t keys = align256((size_t)N * nb * 4);
+    const size_t need = keys + (elite_idx_out ? 0 : align256((size_t)nb * K * 8));
+    if (ws_bytes < need) return fail(MBRL_EWORKSPACE, "%s: workspace %zu < %zu", who, ws_bytes, need);
+    int64_t* elites = elite_idx_out ? elite_idx_out : reinterpret_cast<int64_t*>(static_cast<char*>(workspace) + keys);
+    if (int rc = select_impl(costs, E, N, K, MBRL_NAN_LAST, elites, nullptr, workspace, keys, stream, nb)) return rc;
+    MppiArgs U = make_mppi_args(costs, E, N, H, a, actions, *sampler, temperature, alpha, update_sigma, mu_out, sigma_out);
+    U.weights_out = weights_out; U.returns_out = returns_out; U.stats_out = stats_out;
+    U.next_actions = next_actions;
+    if (!B && next_actions) { U.draw_off = draw_offset; U.draw_n = draw_count; }
+    const int S = next_actions ? (B ? draw_slices(H, B, N, a) : draw_slices(H, 1, draw_count, a)) : 1;
+    return hip_check(launch_mppi_update_elite(make_mppi_elite_args(U, elites, K, sigma_min, sigma_max), S, B, stream),
+                     "mppi elite update launch");
+}
+
+extern "C" int mbrl_mppi_update_elite(const float* costs, int32_t E, int32_t N, int32_t K, const float* actions,
+                                      const mbrl_sampler* sampler, int32_t H, int32_t a, float temperature, float alpha,
+                                      int32_t update_sigma, float sigma_min, float sigma_max, float* mu_out,
+                                      float* sigma_out, int64_t* elite_idx_out, float* weights_out, float* returns_out,
+                                      float* stats_out, float* next_actions, int32_t draw_offset, int32_t draw_count,
+                                      void* workspace, size_t ws_bytes, mbrl_stream_t stream) {
+    return mppi_update_elite_run(costs, E, N, K, 0, actions, sampler, H, a, temperature, alpha, update_sigma, sigma_min,
+                                 sigma_max, mu_out, sigma_out, elite_idx_out, weights_out, returns_out, stats_out,
+                                 next_actions, draw_offset, draw_count, workspace, ws_bytes,
+                                 reinterpret_cast<hipStream_t>(stream), "mppi_update_elite");
+}
+
+extern "C" int mbrl_mppi_update_elite_batch(const float* costs, int32_t E, int32_t N, int32_t K, int32_t B,
+                                            const float* actions, const mbrl_sampler* sampler, int32_t H, int32_t a,
+                                            float temperature, float alpha, int32_t update_sigma, float sigma_min,
+                                            float sigma_max, float* mu_out, float* sigma_out, int64_t* elite_idx_out,
+                                            float* weights_out, float* returns_out, float* stats_out, float* next_actions,
+                                            void* workspace, size_t ws_bytes, mbrl_stream_t stream) {
+    if (B < 1) return fail(MBRL_EINVAL, "mppi_update_elite_batch: B=%d must be >= 1", B);
+    return mppi_update_elite_run(costs, E, N, K, B, actions, sampler, H, a, temperature, alpha, update_sigma, sigma_min,
+                                 sigma_max, mu_out, sigma_out, elite_idx_out, weights_out, returns_out, stats_out,
+                                 next_actions, 0, 0, workspace, ws_bytes, reinterpret_cast<hipStream_t>(stream),
+                                 "mppi_update_elite_batch");
 }

@@ -579,12 +579,14 @@ struct MppiWs {
     float *costs, *mu[2], *sigma[2], *states, *actions[2], *s0;
     void* pair;
     TrajScratch traj;
+    int64_t* elites;   // the elite-restricted plan's list [K] and the selection's keys (K == 0: neither)
+    uint32_t* keys;
     size_t bytes;
 };
 
 // actions[2]: where the update draws the next proposals (update_samples) they go to the other buffer --
 // the row's other workgroups are still streaming the proposals the rollout consumed.
-static MppiWs mppi_ws(const Geometry& g, const mbrl_mppi_params* p, void* base) {
+static MppiWs mppi_ws(const Geometry& g, const mbrl_mppi_params* p, void* base, int K = 0) {
     MppiWs w{};
     WsCursor c(base);
     const size_t Ha = (size_t)p->H * g.a;
@@ -597,6 +599,10 @@ static MppiWs mppi_ws(const Geometry& g, const mbrl_mppi_params* p, void* base) 
     w.traj = take_traj_scratch(c, g);
     w.s0 = c.take<float>((size_t)g.s * 4);
     w.pair = c.take<char>(pair_area_bytes(g, p->N));
+    if (K > 0) {   // (behind mbrl_mppi_plan's layout, which does not move)
+        w.elites = c.take<int64_t>((size_t)K * 8);
+        w.keys = c.take<uint32_t>((size_t)p->N * 4);
+    }
     w.bytes = c.off;
     return w;
 }
@@ -614,30 +620,39 @@ size_t mbrl_mppi_workspace_bytes(const mbrl_mlp_shape* shape, const mbrl_mppi_pa
     return mppi_ws(g, params, nullptr).bytes;
 }
 
-int mbrl_mppi_plan(const mbrl_mlp_shape* shape, const void* packed, const mbrl_norm* norm, const mbrl_cost* cost,
-                   const float* s0_in, const mbrl_mppi_params* p, const float* init_mu_rows, float* mu, float* sigma,
-                   float* actions_out, float* states_out, float* cost_hist, float* weight_hist, float* mu_hist,
-                   float* sigma_hist, mbrl_event_t* rollout_events, void* workspace, size_t ws_bytes,
-                   mbrl_stream_t stream_) {
-    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-    Geometry g;
-    int rc = shape_geometry(shape, &g);
-    if (rc) return rc;
-    if ((rc = mppi_params_check(p))) return rc;
-    if (!packed || !actions_out || !states_out || !workspace)
-        return fail(MBRL_EINVAL, "mppi_plan: packed/actions_out/states_out/workspace NULL");
-    if (!s0_in) return fail(MBRL_EINVAL, "mppi_plan: s0 is NULL");
-    MppiWs w = mppi_ws(g, p, workspace);
-    if (ws_bytes < w.bytes) return fail(MBRL_EINVAL, "mppi_plan: workspace %zu < %zu", ws_bytes, w.bytes);
-    if ((rc = mppi_range_check(p->N, g.a))) return rc;
-    if ((rc = pair_forced_check(g, p->N))) return rc;
+// The elite-restricted plans' extra settings: bad params first, then K and the clamp (MBRL_EINVAL).
+static int mppi_elite_params_check(const mbrl_mppi_elite_params* ep) {
+    if (!ep) return fail(MBRL_EINVAL, "mppi: params is NULL");
+    if (int rc = mppi_params_check(&ep->mppi)) return rc;
+    return mppi_elite_check(ep->mppi.N, ep->K, ep->sigma_min, ep->sigma_max);
+}
+
+// mbrl_mppi_plan and mbrl_mppi_plan_elite, the arguments checked and the workspace carved. ep == NULL: the classic
+// plan (every finite candidate weighted), one update launch per iteration. With ep: a selection launch before each
+// update (the K best into elite_hist's row or the workspace), the update restricted to them and sigma clamped;
+// sigma_rows (rh_init_kernel as the first launch, as mbrl_cem_plan_rh's) only with ep.
+static int mppi_plan_run(const Geometry& g, const void* packed, const mbrl_norm* norm, const mbrl_cost* cost,
+                         const float* s0_in, const mbrl_mppi_params* p, const mbrl_mppi_elite_params* ep,
+                         const float* init_mu_rows, const float* sigma_rows, float* mu, float* sigma, float* actions_out,
+                         float* states_out, float* cost_hist, float* weight_hist, float* mu_hist, float* sigma_hist,
+                         int64_t* elite_hist, mbrl_event_t* rollout_events, const MppiWs& w, hipStream_t stream) {
+    int rc;
     // the update draws the next proposals itself where cem_update_kernel would (update_samples)
     const bool fuse_draw = update_samples(p->N, g.a);
     const int S = fuse_draw ? draw_slices(p->H, 1, p->N, g.a) : 1;
     const InitZero z = plan_zero(g, p->N, w.pair, w.traj);
-    launch_cem_init(dim3(p->H * S, 1), stream, p->seed, p->init_mu, p->init_sigma, p->lo, p->hi, p->H, g.a, p->N, w.mu[0],
-                    w.sigma[0], fuse_draw ? w.actions[0] : nullptr, s0_in, g.s, w.s0, 0, z, init_mu_rows);
-    if ((rc = hip_check(hipGetLastError(), "init launch"))) return rc;
+    if (sigma_rows) {   // (cem_init_kernel has no sigma rows: rh_init_kernel, the same values)
+        RhInitArgs A{};
+        A.seed = p->seed; A.init_mu = p->init_mu; A.init_sigma = p->init_sigma; A.lo = p->lo; A.hi = p->hi;
+        A.H = p->H; A.a = g.a; A.N = p->N; A.s = g.s; A.B = 1; A.s0_rep = 1; A.mu_rows = init_mu_rows;
+        A.sigma_rows = sigma_rows; A.mu = w.mu[0]; A.sigma = w.sigma[0]; A.actions = fuse_draw ? w.actions[0] : nullptr;
+        A.s0_src = s0_in; A.s0_dst = w.s0; A.zero = z;
+        if ((rc = hip_check(launch_rh_init(A, stream), "init launch"))) return rc;
+    } else {
+        launch_cem_init(dim3(p->H * S, 1), stream, p->seed, p->init_mu, p->init_sigma, p->lo, p->hi, p->H, g.a, p->N,
+                        w.mu[0], w.sigma[0], fuse_draw ? w.actions[0] : nullptr, s0_in, g.s, w.s0, 0, z, init_mu_rows);
+        if ((rc = hip_check(hipGetLastError(), "init launch"))) return rc;
+    }
     const size_t Ha = (size_t)p->H * g.a;
     auto record = [&](int row, int cur) {   // the distribution after `row` updates into the history
         hipError_t e = hipSuccess;
@@ -666,7 +681,16 @@ int mbrl_mppi_plan(const mbrl_mlp_shape* shape, const void* packed, const mbrl_n
         U.fin_mu = last ? mu : nullptr; U.fin_sigma = last ? sigma : nullptr; U.fin_actions = last ? actions_out : nullptr;
         U.weights_out = weight_hist ? weight_hist + (size_t)it * p->N : nullptr;
         U.next_actions = (fuse_draw && !last) ? w.actions[(it + 1) & 1] : nullptr;
-        rc = hip_check(launch_mppi_update(U, U.next_actions ? S : 1, stream), "mppi update launch");
+        if (ep) {
+            int64_t* elites = elite_hist ? elite_hist + (size_t)it * ep->K : w.elites;
+            rc = select_impl(costs, g.E, p->N, ep->K, MBRL_NAN_LAST, elites, nullptr, w.keys, align256((size_t)p->N * 4),
+                             stream);
+            if (rc) return rc;
+            rc = hip_check(launch_mppi_update_elite(make_mppi_elite_args(U, elites, ep->K, ep->sigma_min, ep->sigma_max),
+                                                    U.next_actions ? S : 1, 0, stream), "mppi elite update launch");
+        } else {
+            rc = hip_check(launch_mppi_update(U, U.next_actions ? S : 1, stream), "mppi update launch");
+        }
         if (rc) return rc;
         cur ^= 1;
         if ((rc = record(it + 1, cur))) return rc;
@@ -676,6 +700,49 @@ int mbrl_mppi_plan(const mbrl_mlp_shape* shape, const void* packed, const mbrl_n
                           z.ptr[1] != nullptr);
     if (rc) return rc;
     return hip_check(hipGetLastError(), "plan launch");
+}
+
+int mbrl_mppi_plan(const mbrl_mlp_shape* shape, const void* packed, const mbrl_norm* norm, const mbrl_cost* cost,
+                   const float* s0_in, const mbrl_mppi_params* p, const float* init_mu_rows, float* mu, float* sigma,
+                   float* actions_out, float* states_out, float* cost_hist, float* weight_hist, float* mu_hist,
+                   float* sigma_hist, mbrl_event_t* rollout_events, void* workspace, size_t ws_bytes,
+                   mbrl_stream_t stream_) {
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    Geometry g;
+    int rc = shape_geometry(shape, &g);
+    if (rc) return rc;
+    if ((rc = mppi_params_check(p))) return rc;
+    if (!packed || !actions_out || !states_out || !workspace)
+        return fail(MBRL_EINVAL, "mppi_plan: packed/actions_out/states_out/workspace NULL");
+    if (!s0_in) return fail(MBRL_EINVAL, "mppi_plan: s0 is NULL");
+    MppiWs w = mppi_ws(g, p, workspace);
+    if (ws_bytes < w.bytes) return fail(MBRL_EINVAL, "mppi_plan: workspace %zu < %zu", ws_bytes, w.bytes);
+    if ((rc = mppi_range_check(p->N, g.a))) return rc;
+    if ((rc = pair_forced_check(g, p->N))) return rc;
+    return mppi_plan_run(g, packed, norm, cost, s0_in, p, nullptr, init_mu_rows, nullptr, mu, sigma, actions_out,
+                         states_out, cost_hist, weight_hist, mu_hist, sigma_hist, nullptr, rollout_events, w, stream);
+}
+
+int mbrl_mppi_plan_elite(const mbrl_mlp_shape* shape, const void* packed, const mbrl_norm* norm, const mbrl_cost* cost,
+                         const float* s0_in, const mbrl_mppi_elite_params* ep, const float* init_mu_rows,
+                         const float* init_sigma_rows, float* mu, float* sigma, float* actions_out, float* states_out,
+                         float* cost_hist, float* weight_hist, float* mu_hist, float* sigma_hist, int64_t* elite_hist,
+                         mbrl_event_t* rollout_events, void* workspace, size_t ws_bytes, mbrl_stream_t stream_) {
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    Geometry g;
+    int rc = shape_geometry(shape, &g);
+    if (rc) return rc;
+    if ((rc = mppi_elite_params_check(ep))) return rc;
+    const mbrl_mppi_params* p = &ep->mppi;
+    if (!packed || !actions_out || !states_out || !workspace)
+        return fail(MBRL_EINVAL, "mppi_plan_elite: packed/actions_out/states_out/workspace NULL");
+    if (!s0_in) return fail(MBRL_EINVAL, "mppi_plan_elite: s0 is NULL");
+    MppiWs w = mppi_ws(g, p, workspace, ep->K);
+    if (ws_bytes < w.bytes) return fail(MBRL_EINVAL, "mppi_plan_elite: workspace %zu < %zu", ws_bytes, w.bytes);
+    if ((rc = mppi_range_check(p->N, g.a))) return rc;
+    if ((rc = pair_forced_check(g, p->N))) return rc;
+    return mppi_plan_run(g, packed, norm, cost, s0_in, p, ep, init_mu_rows, init_sigma_rows, mu, sigma, actions_out,
+                         states_out, cost_hist, weight_hist, mu_hist, sigma_hist, elite_hist, rollout_events, w, stream);
 }
 
 // ---- batched planning: B independent CEM plans (one initial state each) in shared launches.
@@ -815,10 +882,12 @@ int mbrl_cem_plan_batch(const mbrl_mlp_shape* shape, const void* packed, const m
 struct MppiBatchWs {
     float *costs, *actions[2], *mu[2], *sigma[2], *s0x, *states;
     TrajScratch traj;
+    int64_t* elites;   // the elite-restricted plan's lists [B][K] and the segmented selection's keys (K == 0: neither)
+    uint32_t* keys;
     size_t bytes;
 };
 
-static MppiBatchWs mppi_batch_ws(const Geometry& g, const mbrl_mppi_params* p, int B, void* base) {
+static MppiBatchWs mppi_batch_ws(const Geometry& g, const mbrl_mppi_params* p, int B, void* base, int K = 0) {
     MppiBatchWs w{};
     WsCursor c(base);
     const size_t BN = (size_t)B * p->N, BHa = (size_t)B * p->H * g.a;
@@ -830,6 +899,10 @@ static MppiBatchWs mppi_batch_ws(const Geometry& g, const mbrl_mppi_params* p, i
     w.sigma[0] = c.take<float>(BHa * 4); w.sigma[1] = c.take<float>(BHa * 4);
     w.s0x = c.take<float>(BN * g.s * 4);
     w.states = c.take<float>((size_t)g.E * p->H * g.s * 4);
+    if (K > 0) {   // (behind mbrl_mppi_plan_batch's layout, which does not move)
+        w.elites = c.take<int64_t>((size_t)B * K * 8);
+        w.keys = c.take<uint32_t>(BN * 4);
+    }
     w.bytes = c.off;
     return w;
 }
@@ -837,9 +910,9 @@ static MppiBatchWs mppi_batch_ws(const Geometry& g, const mbrl_mppi_params* p, i
 // What mbrl_mppi_batch_workspace_bytes answers and the plan demands: the larger of the batched layout and
 // mbrl_mppi_plan's (which may hold a pair area the batch has no use for), so that the answer never shrinks
 // as B grows and at B == 1 one query serves either entry.
-static size_t mppi_batch_ws_bytes(const Geometry& g, const mbrl_mppi_params* p, int B) {
-    const size_t batch = mppi_batch_ws(g, p, B, nullptr).bytes;
-    const size_t single = mppi_ws(g, p, nullptr).bytes;
+static size_t mppi_batch_ws_bytes(const Geometry& g, const mbrl_mppi_params* p, int B, int K = 0) {
+    const size_t batch = mppi_batch_ws(g, p, B, nullptr, K).bytes;
+    const size_t single = mppi_ws(g, p, nullptr, K).bytes;
     return single > batch ? single : batch;
 }
 
@@ -853,24 +926,15 @@ size_t mbrl_mppi_batch_workspace_bytes(const mbrl_mlp_shape* shape, const mbrl_m
 // states expanded to one per candidate and, where the update draws, iteration 0's proposals), then per
 // iteration one rollout over the B N candidates and one update over the B problems (grid (H S, B)), then
 // each problem's final mean rolled out, one trajectory launch each.
-int mbrl_mppi_plan_batch(const mbrl_mlp_shape* shape, const void* packed, const mbrl_norm* norm, const mbrl_cost* cost,
-                         const float* s0, int32_t B, const mbrl_mppi_params* p, const float* init_mu_rows,
-                         const int32_t* input_flags, float* mu, float* sigma, float* actions_out, float* states_out,
-                         float* cost_hist, float* weight_hist, float* mu_hist, float* sigma_hist, void* workspace,
-                         size_t ws_bytes, mbrl_stream_t stream_) {
-    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-    Geometry g;
-    int rc = shape_geometry(shape, &g);
-    if (rc) return rc;
-    if ((rc = mppi_params_check(p))) return rc;
-    if (B < 1) return fail(MBRL_EINVAL, "mppi_plan_batch: B=%d", B);
-    if (!packed || !s0 || !actions_out || !states_out || !workspace)
-        return fail(MBRL_EINVAL, "mppi_plan_batch: packed/s0/actions_out/states_out/workspace NULL");
-    if ((rc = mppi_range_check(p->N, g.a))) return rc;
-    if ((rc = mppi_batch_check(B, p->N))) return rc;
-    const MppiBatchWs w = mppi_batch_ws(g, p, B, workspace);
-    if (const size_t need = mppi_batch_ws_bytes(g, p, B); ws_bytes < need)
-        return fail(MBRL_EWORKSPACE, "mppi_plan_batch: workspace %zu < %zu", ws_bytes, need);
+// With ep (mbrl_mppi_plan_elite_batch): one segmented selection launch before each update, whatever B is, the
+// update restricted to each problem's K best and sigma clamped; sigma_rows [B][H][a] (flags bit 1) only with ep.
+static int mppi_batch_run(const Geometry& g, const void* packed, const mbrl_norm* norm, const mbrl_cost* cost,
+                          const float* s0, int B, const mbrl_mppi_params* p, const mbrl_mppi_elite_params* ep,
+                          const float* init_mu_rows, const float* sigma_rows, const int32_t* input_flags, float* mu,
+                          float* sigma, float* actions_out, float* states_out, float* cost_hist, float* weight_hist,
+                          float* mu_hist, float* sigma_hist, int64_t* elite_hist, const MppiBatchWs& w,
+                          hipStream_t stream) {
+    int rc;
     const int N = p->N, BN = B * N;
     const size_t BHa = (size_t)B * p->H * g.a;
     // the update draws the next proposals itself where mbrl_mppi_plan's would (update_samples, per problem)
@@ -880,6 +944,7 @@ int mbrl_mppi_plan_batch(const mbrl_mlp_shape* shape, const void* packed, const 
         RhInitArgs A{};
         A.seed = p->seed; A.init_mu = p->init_mu; A.init_sigma = p->init_sigma; A.lo = p->lo; A.hi = p->hi;
         A.H = p->H; A.a = g.a; A.N = N; A.s = g.s; A.B = B; A.s0_rep = N; A.mu_rows = init_mu_rows; A.flags = input_flags;
+        A.sigma_rows = sigma_rows;
         A.mu = w.mu[0]; A.sigma = w.sigma[0]; A.actions = fuse_draw ? w.actions[0] : nullptr;
         A.s0_src = s0; A.s0_dst = w.s0x;
         if ((rc = hip_check(launch_rh_init(A, stream), "init launch"))) return rc;
@@ -907,12 +972,73 @@ int mbrl_mppi_plan_batch(const mbrl_mlp_shape* shape, const void* packed, const 
         U.fin_mu = last ? mu : nullptr; U.fin_sigma = last ? sigma : nullptr; U.fin_actions = last ? actions_out : nullptr;
         U.weights_out = weight_hist ? weight_hist + (size_t)it * BN : nullptr;
         U.next_actions = (fuse_draw && !last) ? w.actions[(it + 1) & 1] : nullptr;
-        rc = hip_check(launch_mppi_update_batch(U, U.next_actions ? S : 1, B, stream), "mppi batched update launch");
+        if (ep) {
+            int64_t* elites = elite_hist ? elite_hist + (size_t)it * B * ep->K : w.elites;
+            rc = select_impl(costs, g.E, N, ep->K, MBRL_NAN_LAST, elites, nullptr, w.keys, align256((size_t)BN * 4), stream,
+                             B);
+            if (rc) return rc;
+            rc = hip_check(launch_mppi_update_elite(make_mppi_elite_args(U, elites, ep->K, ep->sigma_min, ep->sigma_max),
+                                                    U.next_actions ? S : 1, B, stream), "mppi batched elite update launch");
+        } else {
+            rc = hip_check(launch_mppi_update_batch(U, U.next_actions ? S : 1, B, stream), "mppi batched update launch");
+        }
         if (rc) return rc;
         cur ^= 1;
         if ((rc = record(it + 1, cur))) return rc;
     }
     return batch_final_trajectories(g, packed, norm, s0, B, p->H, actions_out, states_out, w.states, w.traj, stream);
+}
+
+int mbrl_mppi_plan_batch(const mbrl_mlp_shape* shape, const void* packed, const mbrl_norm* norm, const mbrl_cost* cost,
+                         const float* s0, int32_t B, const mbrl_mppi_params* p, const float* init_mu_rows,
+                         const int32_t* input_flags, float* mu, float* sigma, float* actions_out, float* states_out,
+                         float* cost_hist, float* weight_hist, float* mu_hist, float* sigma_hist, void* workspace,
+                         size_t ws_bytes, mbrl_stream_t stream_) {
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    Geometry g;
+    int rc = shape_geometry(shape, &g);
+    if (rc) return rc;
+    if ((rc = mppi_params_check(p))) return rc;
+    if (B < 1) return fail(MBRL_EINVAL, "mppi_plan_batch: B=%d", B);
+    if (!packed || !s0 || !actions_out || !states_out || !workspace)
+        return fail(MBRL_EINVAL, "mppi_plan_batch: packed/s0/actions_out/states_out/workspace NULL");
+    if ((rc = mppi_range_check(p->N, g.a))) return rc;
+    if ((rc = mppi_batch_check(B, p->N))) return rc;
+    const MppiBatchWs w = mppi_batch_ws(g, p, B, workspace);
+    if (const size_t need = mppi_batch_ws_bytes(g, p, B); ws_bytes < need)
+        return fail(MBRL_EWORKSPACE, "mppi_plan_batch: workspace %zu < %zu", ws_bytes, need);
+    return mppi_batch_run(g, packed, norm, cost, s0, B, p, nullptr, init_mu_rows, nullptr, input_flags, mu, sigma,
+                          actions_out, states_out, cost_hist, weight_hist, mu_hist, sigma_hist, nullptr, w, stream);
+}
+
+size_t mbrl_mppi_elite_workspace_bytes(const mbrl_mlp_shape* shape, const mbrl_mppi_elite_params* params, int32_t B) {
+    Geometry g;
+    if (shape_geometry(shape, &g) != MBRL_OK || mppi_elite_params_check(params) != MBRL_OK || B < 1) return 0;
+    return mppi_batch_ws_bytes(g, &params->mppi, B, params->K);
+}
+
+int mbrl_mppi_plan_elite_batch(const mbrl_mlp_shape* shape, const void* packed, const mbrl_norm* norm,
+                               const mbrl_cost* cost, const float* s0, int32_t B, const mbrl_mppi_elite_params* ep,
+                               const float* init_mu_rows, const float* init_sigma_rows, const int32_t* input_flags,
+                               float* mu, float* sigma, float* actions_out, float* states_out, float* cost_hist,
+                               float* weight_hist, float* mu_hist, float* sigma_hist, int64_t* elite_hist,
+                               void* workspace, size_t ws_bytes, mbrl_stream_t stream_) {
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    Geometry g;
+    int rc = shape_geometry(shape, &g);
+    if (rc) return rc;
+    if ((rc = mppi_elite_params_check(ep))) return rc;
+    const mbrl_mppi_params* p = &ep->mppi;
+    if (B < 1) return fail(MBRL_EINVAL, "mppi_plan_elite_batch: B=%d", B);
+    if (!packed || !s0 || !actions_out || !states_out || !workspace)
+        return fail(MBRL_EINVAL, "mppi_plan_elite_batch: packed/s0/actions_out/states_out/workspace NULL");
+    if ((rc = mppi_range_check(p->N, g.a))) return rc;
+    if ((rc = mppi_batch_check(B, p->N))) return rc;
+    const MppiBatchWs w = mppi_batch_ws(g, p, B, workspace, ep->K);
+    if (const size_t need = mppi_batch_ws_bytes(g, p, B, ep->K); ws_bytes < need)
+        return fail(MBRL_EWORKSPACE, "mppi_plan_elite_batch: workspace %zu < %zu", ws_bytes, need);
+    return mppi_batch_run(g, packed, norm, cost, s0, B, p, ep, init_mu_rows, init_sigma_rows, input_flags, mu, sigma,
+                          actions_out, states_out, cost_hist, weight_hist, mu_hist, sigma_hist, elite_hist, w, stream);
 }
 
 // ---- receding-horizon CEM, single and batched, white and mixed (include/mbrl_cem.h mbrl_cem_plan_rh,

@@ -72,6 +72,8 @@ EXPORTED = (
     "mbrl_sample_actions_mixed", "mbrl_cem_rh_mixed_workspace_bytes", "mbrl_cem_plan_rh_mixed",
     "mbrl_cem_plan_rh_batch_mixed",
     "mbrl_mppi_update_batch", "mbrl_mppi_batch_workspace_bytes", "mbrl_mppi_plan_batch",
+    "mbrl_mppi_update_elite", "mbrl_mppi_update_elite_batch", "mbrl_mppi_elite_workspace_bytes",
+    "mbrl_mppi_plan_elite", "mbrl_mppi_plan_elite_batch",
 )
 
 
@@ -114,6 +116,13 @@ class MppiParams(ctypes.Structure):
     _fields_ = [("N", c_int32), ("H", c_int32), ("iterations", c_int32), ("update_sigma", c_int32),
                 ("temperature", c_float), ("alpha", c_float), ("lo", c_float), ("hi", c_float),
                 ("init_mu", c_float), ("init_sigma", c_float), ("seed", c_uint64)]
+
+
+class MppiEliteParams(ctypes.Structure):
+    """mbrl_mppi_elite_params (include/mbrl_cem.h; added within ABI v13): an MppiParams, the elite count K and
+    the clamp on the refitted sigma."""
+    _fields_ = [("mppi", MppiParams), ("K", c_int32), ("_pad", c_int32), ("sigma_min", c_float),
+                ("sigma_max", c_float)]
 
 
 class AdamTensor(ctypes.Structure):
@@ -210,6 +219,20 @@ def load():
         "mbrl_mppi_batch_workspace_bytes": (c_size_t, [POINTER(MlpShape), POINTER(MppiParams), c_int32]),
         "mbrl_mppi_plan_batch": (c_int32, [POINTER(MlpShape), P, POINTER(Norm), POINTER(Cost), P, c_int32,
                                            POINTER(MppiParams), P, P, P, P, P, P, P, P, P, P, P, c_size_t, P]),
+        # MPPI over the K best: the selection launch before each update, the sigma clamp, carried sigma rows
+        "mbrl_mppi_update_elite": (c_int32, [P, c_int32, c_int32, c_int32, P, POINTER(Sampler), c_int32, c_int32,
+                                             c_float, c_float, c_int32, c_float, c_float, P, P, P, P, P, P, P, c_int32,
+                                             c_int32, P, c_size_t, P]),
+        "mbrl_mppi_update_elite_batch": (c_int32, [P, c_int32, c_int32, c_int32, c_int32, P, POINTER(Sampler), c_int32,
+                                                   c_int32, c_float, c_float, c_int32, c_float, c_float, P, P, P, P, P,
+                                                   P, P, P, c_size_t, P]),
+        "mbrl_mppi_elite_workspace_bytes": (c_size_t, [POINTER(MlpShape), POINTER(MppiEliteParams), c_int32]),
+        "mbrl_mppi_plan_elite": (c_int32, [POINTER(MlpShape), P, POINTER(Norm), POINTER(Cost), P,
+                                           POINTER(MppiEliteParams), P, P, P, P, P, P, P, P, P, P, P, P, P, c_size_t,
+                                           P]),
+        "mbrl_mppi_plan_elite_batch": (c_int32, [POINTER(MlpShape), P, POINTER(Norm), POINTER(Cost), P, c_int32,
+                                                 POINTER(MppiEliteParams), P, P, P, P, P, P, P, P, P, P, P, P, P,
+                                                 c_size_t, P]),
         "mbrl_cem_rh_workspace_bytes": (c_size_t, [POINTER(MlpShape), POINTER(CemRhParams)]),
         "mbrl_cem_plan_rh": (c_int32, [POINTER(MlpShape), P, POINTER(Norm), POINTER(Cost), P, POINTER(CemRhParams),
                                        P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, c_size_t, P]),

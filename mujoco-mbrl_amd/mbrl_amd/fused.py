@@ -664,6 +664,57 @@ def mppi_update_batch(costs, actions, sampler, B, H, a, temperature, alpha, upda
                                           _lib.stream_handle(costs.device)), "mbrl_mppi_update_batch")
 
 
+def mppi_update_elite(costs, actions, sampler, K, H, a, temperature, alpha, update_sigma, mu_out, sigma_out,
+                      sigma_min=0.0, sigma_max=float("inf"), elites=None, weights_out=None, returns_out=None,
+                      stats_out=None, next_actions=None, draw_offset=0, workspace=None):
+    """mbrl_mppi_update_elite: mppi_update restricted to the K best candidates (the stable top-K of the
+    selection, then the update: two launches), the refitted sigma clamped to [sigma_min, sigma_max].
+    weights_out is 0 outside the elites, returns_out the true returns of all N. Returns the elites [K]
+    (int64, ascending candidate index)."""
+    lib = _lib.load()
+    E, N = costs.shape
+    dev = costs.device
+    if elites is None:
+        elites = torch.empty(int(K), dtype=torch.int64, device=dev)
+    need = lib.mbrl_select_workspace_bytes(N)
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+    dn = 0 if next_actions is None else int(next_actions.shape[1])
+    _lib.check(lib.mbrl_mppi_update_elite(_lib.ptr(costs), E, N, int(K), _lib.ptr(actions), ctypes_ref(sampler), H, a,
+                                          float(temperature), float(alpha), int(bool(update_sigma)), float(sigma_min),
+                                          float(sigma_max), _lib.ptr(mu_out), _lib.ptr(sigma_out), _lib.ptr(elites),
+                                          _lib.ptr(weights_out), _lib.ptr(returns_out), _lib.ptr(stats_out),
+                                          _lib.ptr(next_actions), int(draw_offset), dn, _lib.ptr(workspace),
+                                          workspace.numel(), _lib.stream_handle(dev)), "mbrl_mppi_update_elite")
+    return elites
+
+
+def mppi_update_elite_batch(costs, actions, sampler, K, B, H, a, temperature, alpha, update_sigma, mu_out, sigma_out,
+                            sigma_min=0.0, sigma_max=float("inf"), elites=None, weights_out=None, returns_out=None,
+                            stats_out=None, next_actions=None, workspace=None):
+    """mbrl_mppi_update_elite_batch: mppi_update_elite for B problems in two launches, laid out as
+    mppi_update_batch's. Returns the elites [B, K] (int64, indices local to each problem)."""
+    lib = _lib.load()
+    E, BN = costs.shape
+    B = int(B)
+    if B < 1 or BN % B:
+        raise ValueError(f"costs have {BN} columns for B={B} problems")
+    dev = costs.device
+    if elites is None:
+        elites = torch.empty((B, int(K)), dtype=torch.int64, device=dev)
+    need = lib.mbrl_select_workspace_bytes(BN)
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+    _lib.check(lib.mbrl_mppi_update_elite_batch(_lib.ptr(costs), E, BN // B, int(K), B, _lib.ptr(actions),
+                                                ctypes_ref(sampler), H, a, float(temperature), float(alpha),
+                                                int(bool(update_sigma)), float(sigma_min), float(sigma_max),
+                                                _lib.ptr(mu_out), _lib.ptr(sigma_out), _lib.ptr(elites),
+                                                _lib.ptr(weights_out), _lib.ptr(returns_out), _lib.ptr(stats_out),
+                                                _lib.ptr(next_actions), _lib.ptr(workspace), workspace.numel(),
+                                                _lib.stream_handle(dev)), "mbrl_mppi_update_elite_batch")
+    return elites
+
+
 def make_sampler(seed, iteration, mu, sigma, lo, hi):
     return _lib.Sampler(int(seed) & 0xFFFFFFFFFFFFFFFF, int(iteration), 0, _lib.ptr(mu), _lib.ptr(sigma),
                         float(lo), float(hi))

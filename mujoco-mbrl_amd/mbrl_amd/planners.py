@@ -1416,10 +1416,27 @@ class MPPIPlanner(ModelPlanner):
     plan returns (predicted states of the clipped final mean, the clipped final mean); plan_detailed
     adds mu, sigma and, with record=True, costs [I, E, N], weights [I, N], mu_hist / sigma_hist
     [I + 1, H, a] (row 0 the initial distribution). distributed=True and this class's plan_batch are not
-    implemented (NotImplementedError); the batched form is mppi_plan_batch / BatchedMPPIPlanner."""
+    implemented (NotImplementedError); the batched form is mppi_plan_batch / BatchedMPPIPlanner.
+
+    MPPI over the K best (mbrl_mppi_plan_elite; the TD-MPC-style update, all off by default -- the defaults call
+    exactly the entry above, bit for bit):
+    num_elites (None): K in [1, num_candidates]. Only the K best candidates of an iteration (the stable top-K of
+        the returns, ties to the lower index) are softmax-weighted; every other weight is 0. K = num_candidates
+        is the classic update; a large temperature with K < N is CEM's elite mean.
+    min_std (0.0), max_std (None -> +inf): with update_sigma the refitted sigma is clamped to [min_std, max_std],
+        which keeps a warm-started episode from collapsing (or blowing up) the proposal width.
+    warm_std (None): the initial std of a warm-started plan, as CEMPlanner's: None (init_std on every row), a
+        float > 0, or "keep": the previous plan's sigma shifted like the mean (mppi_warm_start_rows(prev, H,
+        shift, 0, inf)), given as plan_detailed(..., prev_sigma=); every entry finite and > 0, checked on the host.
+    Naming min_std, max_std or warm_std without num_elites takes the same path with K = num_candidates.
+    record=True then also returns elites [I, K] (int64, ascending candidate index per iteration). Bad values raise
+    ValueError on the host before any device is looked for; warm_std with callables the fused path does not
+    recognise is not implemented."""
     defaults = dict(num_candidates=1000, num_iterations=1, temperature=1.0, alpha=0.0, update_sigma=False,
                     init_std=None, action_bounds=None, seed=None, shift=1, return_device=False, precision="f32",
                     distributed=False)
+    # the kwargs of the elite-restricted update, beside `defaults` (which other code may compare against)
+    elite_defaults = dict(num_elites=None, min_std=0.0, max_std=None, warm_std=None)
     warm_starts = True
 
     @staticmethod
@@ -1451,21 +1468,73 @@ class MPPIPlanner(ModelPlanner):
         return st
 
     @staticmethod
+    def _settings_full(sample_action, horizon, kwargs):
+        """_settings_build's dict and, under "elite", the elite-restricted update's settings (_elite_settings)."""
+        st = MPPIPlanner._settings_build(sample_action, horizon, kwargs)
+        return dict(st, elite=MPPIPlanner._elite_settings(kwargs, st["N"]))
+
+    @staticmethod
+    def _elite_settings(kwargs, N):
+        """dict(K, min_std, max_std, warm_std) of the elite-restricted update, or None when none of its kwargs
+        is named (the plan then calls the classic entry untouched). Host only."""
+        e = MPPIPlanner.elite_defaults
+        ne, lo, hi, ws = (kwargs.get(k, e[k]) for k in ("num_elites", "min_std", "max_std", "warm_std"))
+        if isinstance(ne, bool) or (ne is not None and int(ne) != ne):
+            raise ValueError(f"num_elites must be an integer count, got {ne!r}")
+        if ne is not None and not 1 <= int(ne) <= N:
+            raise ValueError(f"need 1 <= num_elites ({int(ne)}) <= num_candidates ({N})")
+        lo = float(lo)
+        hi = float("inf") if hi is None else float(hi)
+        if not (lo >= 0.0 and np.isfinite(lo)):
+            raise ValueError(f"min_std must be finite and >= 0, got {lo}")
+        if not hi >= lo:
+            raise ValueError(f"max_std ({hi}) must be >= min_std ({lo})")
+        if ws is not None and ws != "keep":
+            ws = float(ws)
+            if not (ws > 0.0 and np.isfinite(ws)):
+                raise ValueError(f"warm_std must be finite and > 0, got {ws}")
+        if ne is None and lo == 0.0 and hi == float("inf") and ws is None:
+            return None
+        return dict(K=N if ne is None else int(ne), min_std=lo, max_std=hi, warm_std=ws)
+
+    @staticmethod
+    def _sigma_rows(st, rows, prev_sigma):
+        """The initial sigma rows of a warm-started plan (`rows`: its mean rows, or None) under warm_std, or
+        None. Host only; finite and > 0 is checked here, as the C call cannot."""
+        el = st["elite"]
+        if el is None or el["warm_std"] is None or rows is None:
+            return None
+        if el["warm_std"] == "keep":
+            if prev_sigma is None:
+                raise ValueError('warm_std="keep" needs the previous plan\'s sigma: plan_detailed(..., prev_sigma=)')
+            sig = mppi_warm_start_rows(prev_sigma, st["H"], st["shift"], 0.0, np.inf)
+        else:
+            sig = np.full(rows.shape, el["warm_std"], np.float32)
+        if sig.shape != rows.shape:
+            raise ValueError(f"prev_sigma gives {sig.shape} rows, the warm start {rows.shape}")
+        if not (np.isfinite(sig).all() and (sig > 0).all()):
+            raise ValueError("initial sigma rows must be finite and > 0")
+        return sig
+
+    @staticmethod
     def plan_detailed(initial_state, model, cost, sample_action, horizon, initial_trajectory=None, **kwargs):
         """plan() plus diagnostics: dict(states, actions, mu, sigma[, costs, weights, mu_hist, sigma_hist])."""
         _noise_refuse(kwargs, "MPPIPlanner")
-        st = MPPIPlanner._settings_build(sample_action, horizon, kwargs)
-        dev = _device(kwargs)
+        st = MPPIPlanner._settings_full(sample_action, horizon, kwargs)
         rows = None
         if initial_trajectory is not None:
             rows = mppi_warm_start_rows(initial_trajectory[1], st["H"], st["shift"], st["lo"], st["hi"])
+        sig = MPPIPlanner._sigma_rows(st, rows, kwargs.get("prev_sigma"))
+        dev = _device(kwargs)
         with _on_device(dev):
             mdesc, cdesc, prob = fused.describe_problem(model, cost, dev, st["precision"])
             if mdesc is not None and cdesc is not None:
                 if rows is not None and rows.shape[1] != mdesc["a"]:
                     raise ValueError(f"initial_trajectory actions have {rows.shape[1]} dims, the model {mdesc['a']}")
-                res = _mppi_fused_single(prob, initial_state, st, rows)
+                res = _mppi_fused_single(prob, initial_state, st, rows, sig)
             else:
+                if st["elite"] is not None and st["elite"]["warm_std"] is not None:
+                    raise NotImplementedError("MPPIPlanner: warm_std needs closures the fused path recognises")
                 a = st["adim"] if rows is None else rows.shape[1]
                 if a is None:
                     a = sample_action(batch_size=1).shape[1]
@@ -1474,19 +1543,28 @@ class MPPIPlanner(ModelPlanner):
             return _finish(res, st["keep"])
 
 
-def _mppi_fused_single(prob, initial_state, st, rows):
-    """One C-ABI call: mbrl_mppi_plan (every iteration stream-ordered, no host sync)."""
+def _mppi_elite_params(st, mppi):
+    el = st["elite"]
+    return _lib.MppiEliteParams(mppi, el["K"], 0, el["min_std"], el["max_std"])
+
+
+def _mppi_fused_single(prob, initial_state, st, rows, sig=None):
+    """One C-ABI call: mbrl_mppi_plan, or mbrl_mppi_plan_elite with the elite-restricted settings (every
+    iteration stream-ordered, no host sync)."""
     lib = _lib.load()
     dev = prob.device
     md = prob.mdesc
     N, H, I = st["N"], st["H"], st["I"]
     a, s, E = md["a"], md["s"], md["E"]
+    el = st["elite"]
     pkey = ("mppi", N, H, I, st["update_sigma"], st["temperature"], st["alpha"], st["lo"], st["hi"], st["init_std"],
             int(st["seed"]) & 0xFFFFFFFFFFFFFFFF)
 
     def make_params():
         return _lib.MppiParams(N, H, I, int(st["update_sigma"]), st["temperature"], st["alpha"], st["lo"], st["hi"],
                                0.0, st["init_std"], pkey[-1])
+    if el is not None:
+        return _mppi_elite_single(lib, prob, initial_state, st, rows, sig, pkey, make_params)
     _, pref, need = _plan_params(prob, pkey, make_params, lib.mbrl_mppi_workspace_bytes)
     if need == 0:
         _lib.check(_lib.MBRL_EINVAL, "mbrl_mppi_workspace_bytes")
@@ -1508,6 +1586,40 @@ def _mppi_fused_single(prob, initial_state, st, rows):
     return out
 
 
+def _mppi_elite_single(lib, prob, initial_state, st, rows, sig, pkey, make_params):
+    """mbrl_mppi_plan_elite: the plan above with the selection before each update, the clamp and sigma rows."""
+    dev = prob.device
+    md = prob.mdesc
+    N, H, I = st["N"], st["H"], st["I"]
+    a, s, E = md["a"], md["s"], md["E"]
+    el = st["elite"]
+    K = el["K"]
+    ekey = ("mppi_elite", K, el["min_std"], el["max_std"]) + pkey[1:]
+    _, pref, need = _plan_params(prob, ekey, lambda: _mppi_elite_params(st, make_params()),
+                                 lib.mbrl_mppi_elite_workspace_bytes, 1)
+    if need == 0:
+        _lib.check(_lib.MBRL_EINVAL, "mbrl_mppi_elite_workspace_bytes")
+    ws = _workspace(("mppi_elite", str(dev)), need, dev)
+    s0 = initial_state.to(device=dev, dtype=torch.float32).contiguous()
+    up = lambda x: None if x is None else torch.from_numpy(np.ascontiguousarray(x)).to(dev)  # noqa: E731
+    rows_d, sig_d = up(rows), up(sig)
+    out = _device_outputs(dev, H, s, a)
+    rec = st["record"]
+    cost_hist, w_hist, mu_hist, sg_hist = [torch.empty(sh, dtype=torch.float32, device=dev) if rec else None
+                                           for sh in ((I, E, N), (I, N), (I + 1, H, a), (I + 1, H, a))]
+    el_hist = torch.empty((I, K), dtype=torch.int64, device=dev) if rec else None
+    pev = st["plan_events"]
+    _mark(pev, 0)
+    _lib.check(lib.mbrl_mppi_plan_elite(*prob.refs, _lib.ptr(s0), pref, _lib.ptr(rows_d), _lib.ptr(sig_d),
+                                        *_output_ptrs(out), _lib.ptr(cost_hist), _lib.ptr(w_hist), _lib.ptr(mu_hist),
+                                        _lib.ptr(sg_hist), _lib.ptr(el_hist), _events(st, I), _lib.ptr(ws), ws.numel(),
+                                        _lib.stream_handle(dev)), "mbrl_mppi_plan_elite")
+    _mark(pev, 1)
+    if rec:
+        out.update(costs=cost_hist, weights=w_hist, mu_hist=mu_hist, sigma_hist=sg_hist, elites=el_hist)
+    return out
+
+
 def _mppi_generic(model, cost, s0, st, a, dev, rows):
     """MPPI with opaque callables: HIP proposal draw, the callables on device tensors, then the HIP
     weighted update (mbrl_mppi_update), as selection and refit stay in the extension for CEM."""
@@ -1518,17 +1630,28 @@ def _mppi_generic(model, cost, s0, st, a, dev, rows):
     else:
         mu = torch.from_numpy(np.ascontiguousarray(rows)).to(dev)
 
+    el = st["elite"]
+
     def update(sp, costs, acts, mu_out, sigma_out):
         wts = torch.empty(N, dtype=torch.float32, device=dev) if rec else None
-        fused.mppi_update(costs, acts, sp, H, a, st["temperature"], st["alpha"], st["update_sigma"], mu_out,
-                          sigma_out, weights_out=wts)
-        return dict(weights=wts, mu_hist=mu_out.clone(), sigma_hist=sigma_out.clone()) if rec else None
+        kept = {}
+        if el is None:
+            fused.mppi_update(costs, acts, sp, H, a, st["temperature"], st["alpha"], st["update_sigma"], mu_out,
+                              sigma_out, weights_out=wts)
+        else:
+            kept["elites"] = fused.mppi_update_elite(costs, acts, sp, el["K"], H, a, st["temperature"], st["alpha"],
+                                                     st["update_sigma"], mu_out, sigma_out, sigma_min=el["min_std"],
+                                                     sigma_max=el["max_std"], weights_out=wts)
+        return dict(kept, weights=wts, mu_hist=mu_out.clone(), sigma_hist=sigma_out.clone()) if rec else None
     sigma0 = torch.full((H, a), st["init_std"], dtype=torch.float32, device=dev)     # (row 0 of sigma_hist)
-    return _generic_plan(model, cost, s0, st, a, dev, mu, update,
-                         dict(costs=[], weights=[], mu_hist=[mu.clone()], sigma_hist=[sigma0]))
+    hist = dict(costs=[], weights=[], mu_hist=[mu.clone()], sigma_hist=[sigma0])
+    if el is not None:
+        hist["elites"] = []
+    return _generic_plan(model, cost, s0, st, a, dev, mu, update, hist)
 
 
-def mppi_plan_batch(initial_states, model, cost, sample_action, horizon, initial_trajectories=None, **kwargs):
+def mppi_plan_batch(initial_states, model, cost, sample_action, horizon, initial_trajectories=None, prev_sigmas=None,
+                    **kwargs):
     """B independent MPPI plans in shared launches (mbrl_mppi_plan_batch): one per row of initial_states
     [B, s], each with its own warm start, so one GPU planner serves B environments that are each somewhere in
     their own episode. kwargs as MPPIPlanner.plan; num_candidates is per problem. initial_trajectories is a list
@@ -1540,14 +1663,25 @@ def mppi_plan_batch(initial_states, model, cost, sample_action, horizon, initial
     weights [I, B, N] and mu_hist / sigma_hist [I + 1, B, H, a]. Host tensors unless return_device.
     distributed, noise_beta and noise_mix are refused as MPPIPlanner refuses them, and a list that is not B
     long raises ValueError, before anything touches the device. Closures the fused path does not recognise
-    fall back to one MPPIPlanner plan per row."""
+    fall back to one MPPIPlanner plan per row.
+
+    num_elites, min_std, max_std and warm_std as MPPIPlanner's (mbrl_mppi_plan_elite_batch: one segmented selection
+    and one update launch per iteration whatever B is); prev_sigmas (warm_std="keep") is a list of B entries, the
+    previous plan's sigma of each warm-started problem (a None entry: that problem starts from init_std). record=True then adds elites [I, B, K] (local indices)."""
     _noise_refuse(kwargs, "mppi_plan_batch")
-    st = MPPIPlanner._settings_build(sample_action, horizon, kwargs)
+    st = MPPIPlanner._settings_full(sample_action, horizon, kwargs)
     B = int(initial_states.shape[0])
     if B < 1:
         raise ValueError("mppi_plan_batch needs at least one initial state")
     inits = _per_row(initial_trajectories, B, "initial_trajectories")
     rows = [None if x is None else mppi_warm_start_rows(x[1], st["H"], st["shift"], st["lo"], st["hi"]) for x in inits]
+    if "prev_sigma" in kwargs:
+        raise ValueError("mppi_plan_batch takes prev_sigmas, one entry per problem, not prev_sigma")
+    el = st["elite"]
+    # with a prev_sigmas list, a warm-started problem whose entry is None starts from init_std (mixed flags)
+    skip = prev_sigmas is not None and el is not None and el["warm_std"] == "keep"
+    sigs = [None if skip and ps is None else MPPIPlanner._sigma_rows(st, r, ps)
+            for r, ps in zip(rows, _per_row(prev_sigmas, B, "prev_sigmas"))]
     dev = _device(kwargs)
     keep, rec = st["keep"], st["record"]
     with torch.cuda.device(dev):
@@ -1558,8 +1692,9 @@ def mppi_plan_batch(initial_states, model, cost, sample_action, horizon, initial
                     for b in range(B)]
             out = {k: torch.stack([o[k] for o in outs]) for k in ("states", "actions", "mu", "sigma")}
             if rec:
+                hists = ("weights", "mu_hist", "sigma_hist") + (("elites",) if el is not None else ())
                 out.update(costs=torch.cat([o["costs"] for o in outs], 2),
-                           **{k: torch.stack([o[k] for o in outs], 1) for k in ("weights", "mu_hist", "sigma_hist")})
+                           **{k: torch.stack([o[k] for o in outs], 1) for k in hists})
             return {k: _to_host(v, keep) for k, v in out.items()}
         lib = _lib.load()
         N, H, I = st["N"], st["H"], st["I"]
@@ -1574,16 +1709,36 @@ def mppi_plan_batch(initial_states, model, cost, sample_action, horizon, initial
             flags_d = torch.tensor([0 if r is None else RH_FLAG_MU for r in rows], dtype=torch.int32).to(dev)
         params = _lib.MppiParams(N, H, I, int(st["update_sigma"]), st["temperature"], st["alpha"], st["lo"], st["hi"],
                                  0.0, st["init_std"], int(st["seed"]) & 0xFFFFFFFFFFFFFFFF)
-        need = lib.mbrl_mppi_batch_workspace_bytes(fused.ctypes_ref(prob.shape), fused.ctypes_ref(params), B)
-        if need == 0:
-            _lib.check(_lib.MBRL_EINVAL, "mbrl_mppi_batch_workspace_bytes")
-        ws = _workspace(("mppi_batch", str(dev)), need, dev)
         s0 = initial_states.to(device=dev, dtype=torch.float32).reshape(B, s).contiguous()
         e = lambda *sh: torch.empty(sh, dtype=torch.float32, device=dev)  # noqa: E731
         out = dict(states=e(B, H, s), actions=e(B, H, a), mu=e(B, H, a), sigma=e(B, H, a))
         if rec:
             out.update(costs=e(I, E, B * N), weights=e(I, B, N), mu_hist=e(I + 1, B, H, a), sigma_hist=e(I + 1, B, H, a))
         g = lambda k: _lib.ptr(out.get(k))  # noqa: E731
+        if el is not None:
+            sig_d = None
+            if any(x is not None for x in sigs):
+                stacked = np.stack([np.ones((H, a), np.float32) if x is None else x for x in sigs])
+                sig_d = torch.from_numpy(np.ascontiguousarray(stacked)).to(dev)
+                flags = [(0 if r is None else RH_FLAG_MU) | (0 if x is None else RH_FLAG_SIGMA) for r, x in zip(rows, sigs)]
+                flags_d = torch.tensor(flags, dtype=torch.int32).to(dev)
+            eparams = _mppi_elite_params(st, params)
+            need = lib.mbrl_mppi_elite_workspace_bytes(fused.ctypes_ref(prob.shape), fused.ctypes_ref(eparams), B)
+            if need == 0:
+                _lib.check(_lib.MBRL_EINVAL, "mbrl_mppi_elite_workspace_bytes")
+            ws = _workspace(("mppi_elite_batch", str(dev)), need, dev)
+            if rec:
+                out["elites"] = torch.empty((I, B, el["K"]), dtype=torch.int64, device=dev)
+            _lib.check(lib.mbrl_mppi_plan_elite_batch(*prob.refs, _lib.ptr(s0), B, fused.ctypes_ref(eparams),
+                                                      _lib.ptr(rows_d), _lib.ptr(sig_d), _lib.ptr(flags_d), g("mu"),
+                                                      g("sigma"), g("actions"), g("states"), g("costs"), g("weights"),
+                                                      g("mu_hist"), g("sigma_hist"), g("elites"), _lib.ptr(ws),
+                                                      ws.numel(), _lib.stream_handle(dev)), "mbrl_mppi_plan_elite_batch")
+            return {k: _to_host(v, keep) for k, v in out.items()}
+        need = lib.mbrl_mppi_batch_workspace_bytes(fused.ctypes_ref(prob.shape), fused.ctypes_ref(params), B)
+        if need == 0:
+            _lib.check(_lib.MBRL_EINVAL, "mbrl_mppi_batch_workspace_bytes")
+        ws = _workspace(("mppi_batch", str(dev)), need, dev)
         _lib.check(lib.mbrl_mppi_plan_batch(*prob.refs, _lib.ptr(s0), B, fused.ctypes_ref(params), _lib.ptr(rows_d),
                                             _lib.ptr(flags_d), g("mu"), g("sigma"), g("actions"), g("states"),
                                             g("costs"), g("weights"), g("mu_hist"), g("sigma_hist"), _lib.ptr(ws),
@@ -1600,6 +1755,8 @@ class BatchedMPPIPlanner(MPPIPlanner):
 
     @staticmethod
     def plan_batch(initial_states, model, cost, sample_action, horizon, initial_trajectories=None, **kwargs):
-        """B plans at once; returns (states [B, H, s], actions [B, H, a])."""
+        """B plans at once; returns (states [B, H, s], actions [B, H, a]). num_elites, min_std, max_std and a
+        numeric warm_std pass through (mppi_plan_batch); warm_std="keep" needs prev_sigmas, which the planner
+        service does not carry for this planner."""
         res = mppi_plan_batch(initial_states, model, cost, sample_action, horizon, initial_trajectories, **kwargs)
         return res["states"], res["actions"]
