@@ -693,7 +693,8 @@ int mbrl_cem_plan_rh_batch_mixed(const mbrl_mlp_shape* shape, const void* packed
  * agents.py:336-362), stopping once mean |delta a| < stop_condition -- as one launch (forward,
  * backward and the Adam step on the device; no host round trip per iteration): Wpad/16 cooperating
  * workgroups that hand hidden vectors to each other, or one workgroup where those do not apply
- * (reward-head models, shapes outside the cooperative kernel's).
+ * (shapes outside the cooperative kernel's: L == 1, W not one of 64 / 128 / 256 / 512, s + a > 32;
+ * reward-head models run either).
  * actions: [H][a] device, in: the initial sequence, out: the optimised one. states_out: [H+1][s]
  * = the last iteration's rollout (computed before its update, as the reference returns it).
  * iterations_out: device int32 (iterations run) or NULL. Needs ensemble == 1 and a GOAL_STATE cost
@@ -714,6 +715,16 @@ int mbrl_gd_plan_batch(const mbrl_mlp_shape* shape, const void* packed, const mb
                        const float* s0, float* actions, int32_t B, int32_t H, int32_t num_iterations,
                        float stop_condition, float lr, float* states_out, int32_t* iterations_out, void* workspace,
                        size_t ws_bytes, mbrl_stream_t stream);
+/* The gradient one iteration of mbrl_gd_plan_batch consumes (added within ABI v13): the same kernels
+ * through the same dispatch (cooperative or one workgroup, MBRL_OPT_GD_SINGLE / GD_HOP / DEBUG_GD_ABORT,
+ * the groups of a batch) run the forward and backward pass of the given sequences and store
+ * d loss / d actions, the values their Adam step reads, to grad_out [B][H][a] in place of that step.
+ * actions [B][H][a] is only read; states_out [B][H+1][s] is the rollout of the given actions.
+ * workspace >= mbrl_gd_batch_workspace_bytes(shape, H, B); checks and codes as mbrl_gd_plan_batch,
+ * and MBRL_EINVAL for a NULL grad_out. */
+int mbrl_gd_grad(const mbrl_mlp_shape* shape, const void* packed, const mbrl_norm* norm, const mbrl_cost* cost,
+                 const float* s0, const float* actions, int32_t B, int32_t H, float* grad_out, float* states_out,
+                 void* workspace, size_t ws_bytes, mbrl_stream_t stream);
 
 /* ---- model training: torch.optim.Adam.step() for one fp32 parameter group
  * (torch/optim/adam.py _multi_tensor_adam, capturable = False, amsgrad = False, maximize = False),

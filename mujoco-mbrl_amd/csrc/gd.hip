@@ -11,7 +11,7 @@
 // Semantics per iteration (planners.py:117-135 with the GoalStateAgent closures, agents.py:219-233):
 //   s_{t+1} = unnorm(MLP(norm(s_t), norm(a_t)))       for t < H      (states_out rows 1..H)
 //   loss    = sum_t SmoothAbs(s_{t+1}) + CoshLoss(a_t)                (models.py:244-272)
-// or, for a reward-head model behind RewardAgent's closures (agents.py:336-362; one-workgroup kernel):
+// or, for a reward-head model behind RewardAgent's closures (agents.py:336-362; either kernel):
 //   loss    = sum_t unnorm_r(reward head of the trunk at (norm(s_{t+1}), norm(a_t)))
 //   -- a second trunk pass per step, whose activations are saved and back-propagated as well.
 //   grad    = d loss / d a  (reverse mode through the chain; ReLU' = [output > 0] as torch)
@@ -305,6 +305,13 @@ __global__ void __launch_bounds__(GD_THREADS) gd_plan_kernel(const GdArgs A) {
                 }
             }
             __syncthreads();
+        }
+        if (A.grad_out != nullptr) {
+            // mbrl_gd_grad: hand out the gradient the Adam step below would consume, and stop
+            float* grad_out = A.grad_out + (size_t)pb * H * a;
+            for (int i = tid; i < H * a; i += GD_THREADS) grad_out[i] = m.ga[i];
+            done = it + 1;
+            break;
         }
         // ---------------- Adam step and the stop test
         const float k = (float)(it + 1);
@@ -814,6 +821,16 @@ __global__ void __launch_bounds__(GC_THREADS) gd_coop_kernel(const GdArgs A, gc_
             });
             if (!ok) return;
         }
+        if (A.grad_out != nullptr) {
+            // mbrl_gd_grad: workgroup 0 hands out the gradient the Adam step below would consume (every
+            // workgroup holds the same one); the actions stay as given
+            if (p == 0) {
+                float* grad_out = A.grad_out + (size_t)pb * H * a;
+                for (int i = tid; i < H * a; i += GC_THREADS) grad_out[i] = grad[i];
+            }
+            done = it + 1;
+            break;
+        }
         // ================= Adam and the stop test (redundant, bit-identical in every workgroup)
         const float kk = (float)(it + 1);
         const float bc1 = 1.0f - powf(b1, kk), bc2 = 1.0f - powf(b2, kk);
@@ -849,7 +866,8 @@ __global__ void __launch_bounds__(GC_THREADS) gd_coop_kernel(const GdArgs A, gc_
         for (int k = 0; k < GD_NSEG; ++k) g_mbrl_gd_stamps[((size_t)pb * P + p) * GD_NSEG + k] = gseg[k];
 #endif
     if (p == 0) {
-        for (int i = tid; i < H * a; i += GC_THREADS) actions[i] = acts[i];
+        if (A.grad_out == nullptr)
+            for (int i = tid; i < H * a; i += GC_THREADS) actions[i] = acts[i];
         for (int i = tid; i < (H + 1) * s; i += GC_THREADS) states_out[i] = st[i];
         if (tid == 0 && iterations_out != nullptr) *iterations_out = done;
     }
@@ -965,10 +983,12 @@ int mbrl_gd_plan(const mbrl_mlp_shape* shape, const void* packed, const mbrl_nor
                               states_out, iterations_out, workspace, ws_bytes, stream);
 }
 
-int mbrl_gd_plan_batch(const mbrl_mlp_shape* shape, const void* packed, const mbrl_norm* norm, const mbrl_cost* cost,
-                       const float* s0, float* actions, int32_t B, int32_t H, int32_t num_iterations,
-                       float stop_condition, float lr, float* states_out, int32_t* iterations_out, void* workspace,
-                       size_t ws_bytes, mbrl_stream_t stream) {
+// The body of mbrl_gd_plan_batch and mbrl_gd_grad: the checks, the kernel arguments and the launches in
+// groups. grad_out != NULL (mbrl_gd_grad): one iteration whose gradient is stored in place of its Adam step.
+static int gd_run(const mbrl_mlp_shape* shape, const void* packed, const mbrl_norm* norm, const mbrl_cost* cost,
+                  const float* s0, float* actions, int32_t B, int32_t H, int32_t num_iterations, float stop_condition,
+                  float lr, float* states_out, int32_t* iterations_out, float* grad_out, void* workspace,
+                  size_t ws_bytes, mbrl_stream_t stream) {
     Geometry g;
     int rc = shape_geometry(shape, &g);
     if (rc) return rc;
@@ -1023,6 +1043,7 @@ int mbrl_gd_plan_batch(const mbrl_mlp_shape* shape, const void* packed, const mb
         A.actions = actions + (size_t)i * H * g.a;
         A.states_out = states_out + (size_t)i * (H + 1) * g.s;
         A.iterations_out = iterations_out ? iterations_out + i : nullptr;
+        A.grad_out = grad_out ? grad_out + (size_t)i * H * g.a : nullptr;
         A.m = reinterpret_cast<float*>(reinterpret_cast<char*>(w.m) + i * w.plan_ws);
         A.v = reinterpret_cast<float*>(reinterpret_cast<char*>(w.v) + i * w.plan_ws);
         A.hist = reinterpret_cast<float*>(reinterpret_cast<char*>(w.hist) + i * w.plan_ws);
@@ -1050,6 +1071,23 @@ int mbrl_gd_plan_batch(const mbrl_mlp_shape* shape, const void* packed, const mb
         if ((rc = hip_check(launch_gd_plan(A, st), "gd_plan launch"))) return rc;
     }
     return MBRL_OK;
+}
+
+int mbrl_gd_plan_batch(const mbrl_mlp_shape* shape, const void* packed, const mbrl_norm* norm, const mbrl_cost* cost,
+                       const float* s0, float* actions, int32_t B, int32_t H, int32_t num_iterations,
+                       float stop_condition, float lr, float* states_out, int32_t* iterations_out, void* workspace,
+                       size_t ws_bytes, mbrl_stream_t stream) {
+    return gd_run(shape, packed, norm, cost, s0, actions, B, H, num_iterations, stop_condition, lr, states_out,
+                  iterations_out, nullptr, workspace, ws_bytes, stream);
+}
+
+int mbrl_gd_grad(const mbrl_mlp_shape* shape, const void* packed, const mbrl_norm* norm, const mbrl_cost* cost,
+                 const float* s0, const float* actions, int32_t B, int32_t H, float* grad_out, float* states_out,
+                 void* workspace, size_t ws_bytes, mbrl_stream_t stream) {
+    if (!grad_out) return fail(MBRL_EINVAL, "gd_grad: NULL grad_out");
+    // one iteration of the plan; with grad_out set the kernels only read `actions`
+    return gd_run(shape, packed, norm, cost, s0, const_cast<float*>(actions), B, H, 1, 0.0f, 0.0f, states_out, nullptr,
+                  grad_out, workspace, ws_bytes, stream);
 }
 
 }  // extern "C"

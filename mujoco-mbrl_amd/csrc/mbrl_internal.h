@@ -529,6 +529,8 @@ struct GdArgs {
     int iterations;
     float stop, lr;
     int* iterations_out;                   // device int or NULL
+    float* grad_out;                       // [H][a] or NULL. Non-NULL (mbrl_gd_grad): the first iteration's
+                                           // d loss / d actions is stored here, no Adam step, actions only read
     const unsigned* gate;                  // gd_plan_kernel: when non-NULL, run only if *gate != 0
     int debug_abort;                       // gd_coop_kernel: give up at once (MBRL_DEBUG_GD_ABORT)
     int hop_mode;                          // gd_coop_kernel hand-offs, as TrajArgs.hop_mode (MBRL_OPT_GD_HOP)

@@ -74,6 +74,7 @@ EXPORTED = (
     "mbrl_mppi_update_batch", "mbrl_mppi_batch_workspace_bytes", "mbrl_mppi_plan_batch",
     "mbrl_mppi_update_elite", "mbrl_mppi_update_elite_batch", "mbrl_mppi_elite_workspace_bytes",
     "mbrl_mppi_plan_elite", "mbrl_mppi_plan_elite_batch",
+    "mbrl_gd_grad",
 )
 
 
@@ -201,6 +202,8 @@ def load():
                                          c_int32, c_float, c_float, P, P, P, c_size_t, P]),
         "mbrl_gd_plan": (c_int32, [POINTER(MlpShape), P, POINTER(Norm), POINTER(Cost), P, P, c_int32, c_int32,
                                    c_float, c_float, P, P, P, c_size_t, P]),
+        "mbrl_gd_grad": (c_int32, [POINTER(MlpShape), P, POINTER(Norm), POINTER(Cost), P, P, c_int32, c_int32, P, P,
+                                   P, c_size_t, P]),
         "mbrl_adam_step": (c_int32, [POINTER(AdamTensor), c_int32, POINTER(AdamHparams), P]),
         "mbrl_train_workspace_bytes": (c_size_t, [POINTER(TrainModel), c_int32]),
         "mbrl_train_status_offset": (c_size_t, [POINTER(TrainModel), c_int32]),

@@ -178,6 +178,25 @@ def plan_fused_batch(initial_states, mdesc, cdesc, actions, horizon, num_iterati
     return states, acts, iters
 
 
+def grad_fused(initial_states, mdesc, cdesc, actions, horizon, dev):
+    """mbrl_gd_grad: the gradient one iteration of plan_fused_batch consumes, from the same kernels
+    through the same dispatch, for B sequences (initial_states [B, s], actions [B, H, a], left as
+    given). Returns (states [B, H+1, s]: the rollouts of `actions`, grad [B, H, a]: d loss / d actions)."""
+    lib = _lib.load()
+    prob = fused.device_problem(mdesc, cdesc, dev)
+    H, B = int(horizon), int(initial_states.shape[0])
+    s0 = initial_states.to(device=dev, dtype=torch.float32).reshape(B, -1).contiguous()
+    acts = actions.to(device=dev, dtype=torch.float32).reshape(B, H, -1).contiguous()
+    states = torch.empty((B, H + 1, mdesc["s"]), dtype=torch.float32, device=dev)
+    grad = torch.empty_like(acts)
+    need = lib.mbrl_gd_batch_workspace_bytes(fused.ctypes_ref(prob.shape), H, B)
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    _lib.check(lib.mbrl_gd_grad(fused.ctypes_ref(prob.shape), _lib.ptr(prob.packed), fused.ctypes_ref(prob.norm),
+                                fused.ctypes_ref(prob.cost), _lib.ptr(s0), _lib.ptr(acts), B, H, _lib.ptr(grad),
+                                _lib.ptr(states), _lib.ptr(ws), need, _lib.stream_handle(dev)), "mbrl_gd_grad")
+    return states, grad
+
+
 def plan_device(initial_state, mdesc, cdesc, action_list, horizon, num_iterations, stop_condition, dev,
                 use_graph=True, use_fused=True):
     """The reference's _optimize_trajectory (planners.py:103-137) on `dev` for described closures."""

@@ -205,8 +205,9 @@ MOVE_GD_ACTIONS = 1e-3    # |actions| <= 1, so the action bar is at most 1.1e-4:
 # none, and an Adam step does not depend on the gradient's scale (up to its eps = 1e-8), so a GD kernel
 # that ignored unnorm_r / rew_std would return the same actions and states. test_flag_cases.py asserts
 # exactly that on the host loop; "rew:ur" / "rew:none" (and "rew:ur+sn" / "rew:sn") expect the same
-# outputs, and the GD kernels' rew_std factor is covered by no test. The rollout kernels' reward
-# unnormalisation is (family rollout_reward compares the returns).
+# outputs. The GD kernels' rew_std factor is covered where the gradient itself is compared
+# (tests/test_gpu_gd_grad.py, cases "flags_reward_*"), the rollout kernels' reward unnormalisation by
+# family rollout_reward (it compares the returns).
 GD_BLIND = ("unnormalize_reward flipped",)
 
 

@@ -75,6 +75,47 @@ def test_errors_are_reported_not_crashing():
     assert b"unsupported MLP shape" in lib.mbrl_last_error()
     rc = lib.mbrl_select_elites(None, 1, 10, 20, 0, None, None, None, 0, None)
     assert rc == -1
+    # mbrl_gd_grad refuses before anything touches a GPU: a NULL grad_out, then mbrl_gd_plan_batch's checks
+    good = _lib.MlpShape(17, 6, 512, 3, 1)
+    cost = _lib.Cost(_lib.MBRL_COST_GOAL_STATE, 1, 1, 0, None, None, 0.4, 0.25)
+    one = ctypes.c_void_p(16)      # a non-NULL pointer nobody dereferences on these paths
+    assert lib.mbrl_gd_grad(ctypes.byref(good), one, None, ctypes.byref(cost), one, one, 1, 4, None, one, one, 0,
+                            None) == _lib.MBRL_EINVAL
+    assert b"grad_out" in lib.mbrl_last_error()
+    assert lib.mbrl_gd_grad(ctypes.byref(sh), one, None, ctypes.byref(cost), one, one, 1, 4, one, one, one, 0,
+                            None) == _lib.MBRL_EUNSUPPORTED
+    assert lib.mbrl_gd_grad(ctypes.byref(good), one, None, None, one, one, 1, 4, one, one, one, 0,
+                            None) == _lib.MBRL_EUNSUPPORTED
+    assert lib.mbrl_gd_grad(ctypes.byref(good), one, None, ctypes.byref(cost), one, one, 1, 4, one, None, one, 0,
+                            None) == _lib.MBRL_EINVAL
+    assert lib.mbrl_gd_grad(ctypes.byref(good), one, None, ctypes.byref(cost), one, one, 0, 4, one, one, one, 0,
+                            None) == _lib.MBRL_EINVAL
+    # (state cost without weights / goal)
+    assert lib.mbrl_gd_grad(ctypes.byref(good), one, None, ctypes.byref(cost), one, one, 1, 4, one, one, one, 0,
+                            None) == _lib.MBRL_EINVAL
+    cost.has_state_cost = 0
+    assert lib.mbrl_gd_grad(ctypes.byref(good), one, None, ctypes.byref(cost), one, one, 1, 4, one, one, one, 0,
+                            None) == _lib.MBRL_EWORKSPACE
+
+
+def test_gd_entries_take_the_arguments_the_header_declares():
+    """The ctypes signature table against include/mbrl_cem.h for the gradient-descent entries: as many
+    arguments, integers and floats where the header has them, pointers elsewhere."""
+    from mbrl_amd import _lib
+    lib = _lib.load()
+    txt = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    kinds = {"int32_t": ctypes.c_int32, "float": ctypes.c_float, "size_t": ctypes.c_size_t}
+    for name in ("mbrl_gd_grad", "mbrl_gd_plan", "mbrl_gd_plan_batch"):
+        params = re.search(r"\bint\s+%s\s*\(([^)]*)\)" % name, txt).group(1).split(",")
+        want = []
+        for prm in params:
+            words = prm.replace("*", " * ").split()
+            want.append("ptr" if "*" in words or "mbrl_stream_t" in words else kinds[words[-2]])
+        fn = getattr(lib, name)
+        got = ["ptr" if t is ctypes.c_void_p or hasattr(t, "contents") else t for t in fn.argtypes]
+        assert got == want, name
+        assert fn.restype is ctypes.c_int32
+    assert len(lib.mbrl_gd_grad.argtypes) == 13
 
 
 STRUCTS = {

@@ -61,6 +61,21 @@ def test_gd_pair_is_sensitive_in_what_the_gpu_test_compares(family, variant):
             assert d >= fc.MOVE_GD_ACTIONS and not passes, f"{label}: actions move by {d:.3e}"
 
 
+@pytest.mark.parametrize("variant", ["rew:ur+sn", "rew:ur"])
+def test_the_gradient_case_does_show_unnormalize_reward(variant):
+    """What the plan outputs above cannot show (GD_BLIND) the gradient comparison of
+    tests/test_gpu_gd_grad.py can: the same family and variant as a gradient case (gd_grad_cases
+    "flags_reward_*"), with rew_std left out of the backward pass, misses that test's bar tenfold."""
+    import gd_grad_cases as gc
+    name = "flags_reward_" + variant.replace(":", "_").replace("+", "_")
+    cid, over, variants = fc.FAMILIES["gd_reward"]
+    c = gc.CASES[name]
+    assert (c["cid"], c["variant"]) == (cid, variant) and variant in variants
+    assert c["over"] == {k: v for k, v in over.items() if k not in ("N", "H")} and c["H"] == over["H"]
+    e = gc.mutant_errors(name)["rew_std dropped"]
+    assert e >= gc.MUTANT_FACTOR * gc.bar(name), f"rew_std dropped: e = {e:.3e}, bar = {gc.bar(name):.3e}"
+
+
 @pytest.mark.parametrize("family", fc.PLAN_FAMILIES)
 def test_plan_has_no_elite_tie_at_the_bar(family):
     for variant in fc.FAMILIES[family][2]:

@@ -1,6 +1,7 @@
 """GPU: every kernel family under the normaliser-flag subsets and cost parameters of tests/flag_cases.py
 (whose CPU test shows that a kernel ignoring one flag, weight or alpha would miss these bars; the one
-exception, rew_std in the gradient-descent backward, is named at test_gd_kernels), against the CPU
+exception, rew_std in the gradient-descent backward, is named at test_gd_kernels and covered by
+tests/test_gpu_gd_grad.py), against the CPU
 oracle -- itself pinned on these branches by tests/test_oracle_flags.py -- and, for the
 gradient-descent kernels, against the reference's autograd host loop. A cleared flag's
 statistics pointer is really NULL on the device (asserted in device_problem), which is what
@@ -386,7 +387,7 @@ def test_gd_kernels(family, variant, mode, monkeypatch):
     mutant): each state / action normaliser, the weights, both alphas and both cost switches. They
     cannot show unnormalize_reward: rew_std only scales the gradient, and Adam's step does not depend on
     that scale, so "rew:ur" and "rew:none" expect the same actions and states, and the GD kernels'
-    rew_std factor is not covered here (flag_cases.GD_BLIND)."""
+    rew_std factor is not covered here (flag_cases.GD_BLIND) but in tests/test_gpu_gd_grad.py."""
     from mbrl_amd import _lib, gd
     ref_states, ref_actions = _gd_reference(family, variant, monkeypatch)
     p, A, _, _ = case(family, variant)
