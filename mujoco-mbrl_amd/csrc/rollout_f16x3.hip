@@ -210,10 +210,12 @@ struct SplitRollout {
     __device__ __forceinline__ int row_of(int r) const { return 16 * r + 4 * (wave & 3) + (lane >> 4); }
 
     // ring slot G of the step sequence (wrapping into the next step): chunk G / SUB, fragments
-    // [FS (G % SUB), FS (G % SUB + 1)) of this wave's slice
+    // [FS (G % SUB), FS (G % SUB + 1)) of this wave's slice. G < css + SNB - 1, and a step can be as
+    // short as two slots (L = 1 at T = 4 with two tiles per slot), so G may lie two steps ahead.
     __device__ __forceinline__ void load_slot(f32x4 (&dst)[FS], int G) {
         const int css = A.CS * SUB;
-        const int gp = G < css ? G : G - css;
+        int gp = G < css ? G : G - css;
+        if (gp >= css) gp -= css;
         const unsigned soff = (unsigned)(gp / SUB) * (unsigned)(SW * FR * 1024) + (unsigned)((gp % SUB) * FS * 1024);
         sload<FS>(dst, rsrc, voff, soff);
     }

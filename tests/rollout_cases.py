@@ -129,35 +129,46 @@ def run_outcome(case):
 
 
 # ------------------------------------------------------------------------------------------------
-def rollout_f64(problem, s0, actions):
-    """oracle.cem.rollout's arithmetic (every normaliser on, both cost terms, unit or given weights, or
-    the reward head) in float64 from the same float32 inputs: costs [E, N]."""
+def rollout_f64(problem, s0, actions, store_states=False):
+    """oracle.cem.rollout's arithmetic (the problem's normaliser flags, both cost terms, unit or given weights,
+    or the reward head) in float64 from the same float32 inputs: costs [E, N], and with store_states the
+    states [E, H, N, s] as well."""
+    from oracle import cem as ocem
     nm, cost = problem["norm"], problem["cost"]
     f = lambda x: np.asarray(x, dtype=np.float64)
+    on = lambda k: ocem.norm_flag(nm, k)  # noqa: E731
     H, N, _ = actions.shape
-    out = []
+    out, states = [], []
     for layers in problem["model"]:
         def mlp(x):
             for w, b in layers[:-1]:
                 x = np.maximum(x @ f(w).T + f(b), 0.0)
             return x @ f(layers[-1][0]).T + f(layers[-1][1])
+
+        def inp(st, t):
+            an = (f(actions[t]) - f(nm["act_mean"])) / f(nm["act_std"]) if on("normalize_action") else f(actions[t])
+            sn = (st - f(nm["obs_mean"])) / f(nm["obs_std"]) if on("normalize_state") else st
+            return np.concatenate([sn, an], axis=1)
         st = np.broadcast_to(f(s0), (N, f(s0).shape[-1])).copy()
         ns = st.shape[1]
         total = np.zeros(N)
+        member = []
         for t in range(H):
-            an = (f(actions[t]) - f(nm["act_mean"])) / f(nm["act_std"])
-            st = mlp(np.concatenate([(st - f(nm["obs_mean"])) / f(nm["obs_std"]), an], axis=1))[:, :ns]
-            st = st * f(nm["obs_std"]) + f(nm["obs_mean"])
+            st = mlp(inp(st, t))[:, :ns]
+            if on("unnormalize_state"):
+                st = st * f(nm["obs_std"]) + f(nm["obs_mean"])
+            member.append(st)
             if cost.get("kind") == "reward":
-                r = mlp(np.concatenate([(st - f(nm["obs_mean"])) / f(nm["obs_std"]), an], axis=1))[:, ns]
-                total += r * f(nm["rew_std"])[0] + f(nm["rew_mean"])[0]
+                r = mlp(inp(st, t))[:, ns]
+                total += r * f(nm["rew_std"])[0] + f(nm["rew_mean"])[0] if on("unnormalize_reward") else r
             else:
                 x = (st - f(cost["goal"])) * f(cost["weights"])
                 sc = np.sum(np.sqrt(x * x + cost["alpha_state"] ** 2) - cost["alpha_state"], axis=-1)
                 aa = cost["alpha_action"]
                 total += sc + aa * aa * np.mean(np.cosh(f(actions[t]) / aa) - 1.0, axis=-1)
         out.append(total)
-    return np.stack(out)
+        states.append(np.stack(member))
+    return (np.stack(out), np.stack(states)) if store_states else np.stack(out)
 
 
 def given_inputs(case, problem):

@@ -17,8 +17,12 @@ half) and checks the constants against the sources; tests/test_gpu_envelope.py r
 where a shape the model calls refused must be refused with that message and one it calls accepted must run
 and match the oracle (the LDS half).
 
-Not modelled: the F16X3 / F16X6 precisions, the column-split pairs (a plan's workspace offers them only
-at Wpad = 512 with at most 256 workgroups; a lone mbrl_rollout_cost never) and the opt-in 4-candidate tile.
+  split_kernel()      the F16X3 / F16X6 block of rollout_impl (the `g.precision` branch), make_geometry's K0S /
+                      NOS / CS with the parity bump, rollout_split_supported, split_lds / rollout_split_lds_bytes
+                      and split_ts (csrc/rollout_f16x3.hip), and the redo pass's rollout_lds_bytes(X, 32) check
+
+Not modelled: the column-split pairs (a plan's workspace offers them only at Wpad = 512 with at most 256
+workgroups; a lone mbrl_rollout_cost never) and the opt-in 4-candidate tile.
 """
 from collections import namedtuple
 
@@ -159,6 +163,85 @@ def dispatch(s, a, W, L, E=1, reward=0, *, N, cus=MI355X_CUS, rollout_tile=0, gr
     GS = bool(ring and NW == 8 and T <= 8 and seam)
     return Instance("m16", T, R, NW, k0c_t, not_t, GS, bool(alias), g["reward"], fallback,
                     lds_launch_bytes(g, 16 * R, NW, alias))
+
+
+# ---- the split-operand kernels (rollout_f16x3.hip): precision F16X3 (P = 2) / F16X6 (P = 3)
+SPLIT_SHAPES = ((1, 1), (2, 2), (3, 1), (1, 3), (3, 3))   # MBRL_SPLIT_SHAPES: (K0S, NOS)
+SPLIT_T = (4, 8)               # make_geometry split_ok, rollout_split_supported
+SPLIT_MAX_A = 48               # 16 * SMAXA
+SPLIT_R2_MIN_N = 256 * 32      # plan.hip: `int RS = N >= 256 * 32 ? 2 : 1;`
+SPLIT_WAVES = 8                # SW
+
+Split = namedtuple("Split", "kind T R P K0S NOS TS lds_bytes")
+F32 = namedtuple("F32", "kind reason")
+
+
+def split_geometry(g):
+    """make_geometry's split fields: (K0S, NOS, CS); K0S + NOS is made even by a zero-padded layer-0 chunk."""
+    K0S, NOS = (g["s"] + g["a"] + 31) // 32, g["NOT"] // 2
+    if (K0S + NOS) & 1:
+        K0S += 1
+    return K0S, NOS, K0S + (g["L"] - 1) * 2 * g["T"] + NOS
+
+
+def split_ts(R, P, K0S, NOS):
+    """split_ts: tiles per weight ring slot."""
+    return 2 if (P == 2 or (R == 1 and K0S <= 2 and NOS <= 2)) else 1
+
+
+def split_lds_need_bytes(g, R, P):
+    """split_lds(...).bytes: every block rounded up to 16 bytes."""
+    r16 = lambda b: (b + 15) & ~15  # noqa: E731
+    K0S = split_geometry(g)[0]
+    M, sr = 16 * R, P * max(g["Wpad"], 32 * K0S) + 8
+    o = r16(M * sr * 2) * (2 if R == 1 else 1)                # x, y (R = 2: one buffer)
+    o += r16(SPLIT_WAVES * M * g["pw"] * 4) + r16(2 * M * 4)  # part, acs
+    o += 4 * r16(g["s"] * 4) + 2 * r16(g["a"] * 4)            # obs_mean, obs_std, goal, cw; act_mean, act_std
+    o += r16((g["L"] * g["Wpad"] + 16 * g["NOT"]) * 4) + r16(16)   # hbias, flag
+    return o
+
+
+def _split_refusal(g, R, P):
+    """rollout_split_supported, as the reason it returns false for (None: supported)."""
+    K0S, NOS, CS = split_geometry(g)
+    if R != 1 and not (R == 2 and g["NOT"] == 2):
+        return "R = 2 needs one output chunk"
+    if g["reward"] or g["T"] not in SPLIT_T or g["a"] > SPLIT_MAX_A:
+        return "reward, T or a"
+    assert g["s"] <= 16 * g["NOT"] and g["NOT"] == 2 * (CS - K0S - (g["L"] - 1) * 2 * g["T"])
+    if max(split_lds_need_bytes(g, R, P), LDS_FLOOR) > LDS_LIMIT:
+        return "split LDS"
+    if (K0S, NOS) not in SPLIT_SHAPES:
+        return "shape class (%d, %d)" % (K0S, NOS)
+    return None
+
+
+def split_kernel(s, a, W, L, E=1, reward=0, *, N, P, split_tile=0):
+    """What mbrl_rollout_cost launches for a problem of precision F16X3 (P = 2) or F16X6 (P = 3):
+    Split("split", T, R, P, K0S, NOS, TS, lds_bytes) -- the template arguments of rollout_split_kernel and
+    its dynamic LDS -- or F32("f32", reason): the fp32 path alone (dispatch() says which kernel, or that
+    the call is refused). split_tile: MBRL_OPT_SPLIT_TILE (0 auto, 16, 32)."""
+    assert P in (2, 3)
+    g = geometry(s, a, W, L, E, reward)
+    nw16 = 8 if g is not None and g["T"] >= 2 else 4
+    if g is None or 16 * a > ACTION_SLOTS or lds_need_bytes(g, 16, nw16, _alias_ok(g, nw16)) > LDS_LIMIT:
+        return F32("f32", "refused")        # dispatch()'s three refusals: rollout_validate comes first
+    if g["T"] not in SPLIT_T:
+        return F32("f32", "T = %d" % g["T"])
+    if g["reward"]:
+        return F32("f32", "reward head")
+    R = 2 if N >= SPLIT_R2_MIN_N else 1
+    if split_tile:
+        R = 2 if split_tile == 32 else 1
+    # the redo pass at 32 rows: 4 waves, partials not aliased (part_alias is set after this block)
+    if R == 2 and (_split_refusal(g, 2, P) or lds_launch_bytes(g, 32, 4, False) > LDS_LIMIT):
+        R = 1
+    why = _split_refusal(g, R, P)
+    if why:
+        return F32("f32", why)
+    K0S, NOS, _ = split_geometry(g)
+    return Split("split", g["T"], R, P, K0S, NOS, split_ts(R, P, K0S, NOS),
+                 max(split_lds_need_bytes(g, R, P), LDS_FLOOR))
 
 
 # ---- the single-trajectory kernels (traj.hip)

@@ -159,7 +159,11 @@ def test_f16x3_weight_out_of_range_falls_back_to_f32(precision):
 
 @pytest.mark.parametrize("precision", SPLITS)
 def test_f16x3_batched_and_sharded_paths_accept_precision(precision):
-    """plan_batch with precision='f16x3' equals B single plans of the same precision."""
+    """plan_batch with precision='f16x3' equals B single plans of the same precision. Problem b of a batch draws
+    candidates [b N, (b + 1) N) of the Philox stream and a single plan candidates [0, N), so each start state is
+    compared where the two draw alike: as problem 0 of the batch rotated to start with it, states and actions
+    bit for bit (test_gpu_plan_batch.py's check). The rows behind it (other draws) only repeat across the
+    rotations' shapes."""
     from mbrl_amd import CEMPlanner
     p = ocem.synth_problem(3, N=512, H=8)
     _, model_fn, cost_fn, sample_action = build(p)
@@ -168,3 +172,9 @@ def test_f16x3_batched_and_sharded_paths_accept_precision(precision):
     kw = dict(num_candidates=512, num_iterations=2, seed=21, precision=precision)
     states, actions = CEMPlanner.plan_batch(s0, model_fn, cost_fn, sample_action, 8, **kw)
     assert actions.shape == (B, 8, p["cfg"]["a"]) and torch.isfinite(states).all()
+    for b in range(B):
+        st, ac = (states, actions) if b == 0 else \
+            CEMPlanner.plan_batch(torch.roll(s0, -b, 0), model_fn, cost_fn, sample_action, 8, **kw)
+        s1, a1 = CEMPlanner.plan(s0[b], model_fn, cost_fn, sample_action, 8, **kw)
+        assert st.shape == states.shape and torch.isfinite(st).all()
+        assert torch.equal(st[0], s1) and torch.equal(ac[0], a1), b

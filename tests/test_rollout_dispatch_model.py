@@ -232,3 +232,115 @@ def test_float32_oracle_is_within_a_tenth_of_the_bar_of_float64():
     print("float32 oracle vs float64, worst relative distance per case:",
           ", ".join("%s %.2g" % kv for kv in sorted(worst.items(), key=lambda kv: -kv[1])[:8]))
     assert not bad, bad
+
+
+# ------------------------------------------------------------------------------------------------ split kernels
+# The 28 instantiations launch_rollout_split lists: (T, R, P, K0S, NOS), R = 2 only where NOS = 1.
+SPLIT_LISTED = {(T, R, P, k, n) for T in rdm.SPLIT_T for P in (2, 3) for k, n in rdm.SPLIT_SHAPES
+                for R in ((1, 2) if n == 1 else (1,))}
+# NOS = 3 needs s > 64, and then s + a > 64 gives K0S = 3: a goal-state model cannot have (K0S, NOS) = (1, 3)
+SPLIT_UNREACHABLE = {(T, 1, P, 1, 3) for T in rdm.SPLIT_T for P in (2, 3)}
+
+
+def _inst(o):
+    return (o.T, o.R, o.P, o.K0S, o.NOS)
+
+
+def test_split_model_reaches_24_of_the_28_listed_instantiations():
+    """s in 1..100, a in 0..50, W in {129, 256, 257, 512}, L in 1..4, N = 40, split_tile 0 /
+    32, both precisions: every listed instantiation but the four (1, 3) ones is reached, and nothing else.
+    (1, 3) stays listed in launch_rollout_split; it is dead code for goal-state models."""
+    import split_cases as sc
+    assert len(SPLIT_LISTED) == 28
+    reached, ts = set(), set()
+    for s in range(1, 101):
+        for a in range(0, 51):
+            for W in (129, 256, 257, 512):
+                for L in range(1, 5):
+                    for P in (2, 3):
+                        for N, tile in ((sc.N, 0), (sc.N, 32)):      # (N >= 8192 asks what split_tile = 32 asks)
+                            o = rdm.split_kernel(s, a, W, L, N=N, P=P, split_tile=tile)
+                            if o.kind == "split":
+                                reached.add(_inst(o))
+                                ts.add((o.R, o.P, o.K0S, o.NOS, o.TS))
+                                assert o.lds_bytes <= rdm.LDS_LIMIT
+                            else:
+                                assert o.reason != "refused" or a == 0 or a > rdm.SPLIT_MAX_A, (s, a, W, L)
+    assert reached == SPLIT_LISTED - SPLIT_UNREACHABLE and len(reached) == 24
+    assert {t[-1] for t in ts} == {1, 2} and all(TS == 2 for R, P, k, n, TS in ts if P == 2)
+    # N >= 8192 asks for R = 2 by itself, split_tile = 16 overrides it
+    assert rdm.split_kernel(17, 6, 512, 3, N=8192, P=2).R == 2 and rdm.split_kernel(17, 6, 512, 3, N=8191, P=2).R == 1
+    assert rdm.split_kernel(17, 6, 512, 3, N=8192, P=2, split_tile=16).R == 1
+    for sh in ((17, 6, 512, 3), (49, 49, 512, 2), (500, 12, 64, 2), (67, 21, 512, 2), (5, 1, 1025, 2)):
+        refused = isinstance(rdm.dispatch(*sh, N=sc.N), rdm.Refusal)
+        assert (rdm.split_kernel(*sh, N=sc.N, P=3) == rdm.F32("f32", "refused")) == refused, sh
+
+
+def test_every_split_case_lands_where_it_was_built_to_and_the_table_reaches_every_instantiation():
+    import split_cases as sc
+    ids = [c.id for c in sc.ACCEPTED + sc.DECLINED]
+    assert len(set(ids)) == len(ids)
+    hit = set()
+    for c in sc.ACCEPTED + sc.DECLINED:
+        assert c.N == sc.N and c.H in (1, 2, 3), c.id
+        for P in (2, 3):
+            o = sc.outcome(c, P)
+            for k, v in c.built_for.items():
+                assert getattr(o, k) == v, (c.id, P, k, getattr(o, k), v)
+            if o.kind == "split":
+                hit.add(_inst(o))
+    assert hit == SPLIT_LISTED - SPLIT_UNREACHABLE, sorted(SPLIT_LISTED - SPLIT_UNREACHABLE - hit)
+    # dropping a case that alone reaches an instantiation leaves it unreached
+    for victim in ("c22_t4", "c33_t4", "c31_bump_t8_r2"):
+        rest = {_inst(sc.outcome(c, P)) for c in sc.ACCEPTED if c.id != victim for P in (2, 3)}
+        assert rest < hit, victim
+    # what the table promises beside the instantiations
+    acc = sc.ACCEPTED
+    assert {c.mode for c in acc} == {"given", "per_cand", "sampled"} and {c.H for c in acc} == {1, 2, 3}
+    depth = lambda T: {sc.shape_of(c)[3] for c in acc if sc.outcome(c, 2).T == T and sc.outcome(c, 2).K0S == 1}  # noqa: E731
+    assert depth(4) == {1, 2, 3, 4} and depth(8) == {1, 2, 3, 4}
+    assert {sc.shape_of(c)[2] for c in acc} >= {129, 200, 257, 300} and {sc.shape_of(c)[1] for c in acc} >= {16, 17, 32, 33, 48}
+    assert any(sc.shape_of(c)[4] == 2 and sc.outcome(c, 2).NOS == 1 for c in acc)
+    assert any(sc.shape_of(c)[4] == 2 and sc.outcome(c, 2).NOS == 3 for c in acc)
+    # the parity bump: 32 K0S covers a whole chunk more than s + a needs
+    bumped = [c for c in acc if 32 * sc.outcome(c, 2).K0S - sum(sc.shape_of(c)[:2]) >= 32]
+    assert {c.id for c in bumped} >= {"c31_bump_t4", "c31_bump_t4_r2", "c31_bump_t8", "c31_bump_t8_r2"}
+    # the weight ring of one step is two slots (L = 1, T = 4, two tiles per slot): the prefetch wraps twice
+    assert any(sc.shape_of(c)[3] == 1 and sc.outcome(c, 2).T == 4 and c.H == 3 for c in acc)
+    # R = 2 requests turned down keep the split kernel on 16-candidate tiles; each reason is there
+    for cid in sc.R2_DECLINED:
+        assert sc.tile_of(sc.by_id(cid)) == 32 and sc.outcome(sc.by_id(cid), 2).R == 1
+    g = rdm.geometry(20, 48, 512, 3)
+    assert rdm._split_refusal(g, 2, 3) is None and rdm.lds_launch_bytes(g, 32, 4, False) > rdm.LDS_LIMIT
+    assert {c.built_for["reason"] for c in sc.DECLINED} >= {"shape class (4, 2)", "refused", "T = 2", "T = 16", "reward head"}
+    assert any(sc.shape_of(c)[0] == 100 for c in sc.DECLINED)
+
+
+def test_split_model_constants_are_the_sources():
+    def src(name):
+        with open(os.path.join(CSRC, name)) as f:
+            return f.read()
+
+    def one(text, pattern):
+        assert len(re.findall(pattern, text)) == 1, pattern
+
+    hdr, plan, split = src("mbrl_internal.h"), src("plan.hip"), src("rollout_f16x3.hip")
+    one(hdr, r"g->split_ok = \(T == 4 \|\| T == 8\) \? 1 : 0;")
+    one(hdr, r"g->K0S = \(s \+ a \+ 31\) / 32;\n    g->NOS = g->NOT / 2;\n    if \(\(g->K0S \+ g->NOS\) & 1\) g->K0S \+= 1;")
+    one(hdr, r"g->CS = g->K0S \+ \(L - 1\) \* 2 \* T \+ g->NOS;")
+    one(plan, r"S\.sr = P \* \(g\.Wpad > 32 \* g\.K0S \? g\.Wpad : 32 \* g\.K0S\) \+ 8;")
+    one(plan, r"int RS = N >= 256 \* 32 \? 2 : 1;")
+    one(plan, r"if \(const int o = opt\(MBRL_OPT_SPLIT_TILE\)\) RS = o == 32 \? 2 : 1;")
+    one(plan, r"X\.nw = RS == 1 && g\.T >= 2 \? 8 : 4;")
+    one(plan, r"if \(RS == 2 && \(!rollout_split_supported\(S, g\.T, 2, P\) \|\| rollout_lds_bytes\(X, 32\) > 160 \* 1024\)\) \{")
+    shapes = re.findall(r"X\((\d), (\d)\)", re.search(r"#define MBRL_SPLIT_SHAPES\(X\)(.*)", split).group(1))
+    assert tuple((int(k), int(n)) for k, n in shapes) == rdm.SPLIT_SHAPES
+    one(split, r"constexpr int SW = 8;") and one(split, r"constexpr int SMAXA = 3;")
+    one(split, r"if \(R != 1 && !\(R == 2 && A\.NOT == 2\)\) return false;")
+    one(split, r"if \(A\.reward \|\| \(T != 4 && T != 8\) \|\| A\.a > 16 \* SMAXA\) return false;")
+    one(split, r"if \(rollout_split_lds_bytes\(A, R\) > 160 \* 1024\) return false;")
+    one(split, r"constexpr int split_ts\(\) \{ return \(P == 2 \|\| \(R == 1 && K0S <= 2 && NOS <= 2\)\) \? 2 : 1; \}")
+    one(split, r"o \+= \(bytes \+ 15\) & ~\(size_t\)15;")
+    one(split, r"L\.y = R == 1 \? static_cast<_Float16\*>\(take\(M \* A\.sr \* 2\)\) : L\.x;")
+    one(split, r"L\.part = static_cast<float\*>\(take\(\(size_t\)SW \* M \* A\.pw \* 4\)\);")
+    assert rdm.SPLIT_WAVES == 8 and rdm.SPLIT_MAX_A == 48 and rdm.SPLIT_R2_MIN_N == 8192
