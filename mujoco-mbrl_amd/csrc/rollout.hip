@@ -32,16 +32,12 @@
 #include <type_traits>
 
 #include "mbrl_internal.h"
+#include "mbrl_rollout_dev.h"
 
 // Waves per workgroup for the rollout: 8 (two per SIMD, T/2 tiles each) for R = 1, and for R = 2 where
 // the aliased output partials fit LDS; else 4. The weight stream goes through buffer_load (SGPR
 // descriptor + 32-bit offsets). Measured on cheetah, rollout ms (r01; the other forms were removed in
 // r06): global 4 waves 1.083 | buffer 4 waves 1.044 | global 8 waves 1.171 | buffer 8 waves 1.035
-// State slots per lane (ceil(s / 16)) up to which the 8/16-candidate epilogues keep their per-lane
-// parameter copies in registers; wider states read them from LDS (the copies spilled on humanoid).
-#ifndef MBRL_EPI_REG_SLOTS
-#define MBRL_EPI_REG_SLOTS 2
-#endif
 // Timing ablation only (results are garbage): -DMBRL_PAIR_DIAG=1 keeps the column-split pairs' LDS
 // hand-off flow but drops every cross-workgroup store, poll and load.
 #ifndef MBRL_PAIR_DIAG
@@ -57,7 +53,6 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 // Diagnostic build only (make diag, -DMBRL_STAMPS): per-wave s_memtime sums per kernel segment,
 // written to a buffer set by mbrl_diag_set_stamps(). The timed kernel never contains stamps.
 #ifdef MBRL_STAMPS
-constexpr int NSEG = 8;
 __device__ unsigned long long* g_mbrl_stamps;
 #define STAMP(k)                                                   \
     do {                                                           \
@@ -189,86 +184,6 @@ __device__ __forceinline__ void zero_acc(f32x4 (&acc)[R][T]) {
     for (int r = 0; r < R; ++r)
 #pragma unroll
         for (int j = 0; j < T; ++j) acc[r][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-}
-
-// Sum over the 16 lanes of a DPP row (row_ror 8, 4, 2, 1): every lane of the row gets the total.
-__device__ __forceinline__ float rowsum16(float v) {
-    v += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0x128, 0xF, 0xF, false));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0x124, 0xF, 0xF, false));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0x122, 0xF, 0xF, false));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0x121, 0xF, 0xF, false));
-    return v;
-}
-
-// Epilogue mapping: lane l of wave w owns candidate row m = 16r + 4w + (l >> 4) and the feature
-// slots d = (l & 15) + 16k of that row, so per-row reductions are one DPP row sum.
-constexpr int MAX_A_PER_LANE = 3;  // action_dim <= 48
-
-__device__ __forceinline__ int epi_row(int r, int wave, int lane) { return 16 * r + 4 * wave + (lane >> 4); }
-
-// a_t for this lane's (row, slots), loaded early and unconditionally (clamped indices) so hipcc
-// emits no branch-around-load with its vmcnt(0) (cdna_hip_programming.md §5, trap (c)).
-template <int R>
-__device__ __forceinline__ void fetch_actions(const RolloutArgs& A, int tile, int t, int wave, int lane,
-                                              float (&av)[R][MAX_A_PER_LANE]) {
-    constexpr int M = 16 * R;
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        const int n = min(tile * M + epi_row(r, wave, lane), A.N - 1);
-        const float* src = A.actions + ((size_t)t * A.N + n) * A.a;
-#pragma unroll
-        for (int k = 0; k < MAX_A_PER_LANE; ++k) av[r][k] = src[min((lane & 15) + 16 * k, A.a - 1)];
-    }
-}
-
-// Per-lane copies of the step-invariant epilogue operands (this lane's feature slots d = (l&15) +
-// 16k), loaded once so the per-step epilogue issues no LDS parameter reads.
-template <int SS>
-struct EpiParams {
-    float om[SS], os[SS], goal[SS], cw[SS], bo[SS];   // state slots
-    float am[MAX_A_PER_LANE], as[MAX_A_PER_LANE];    // action slots
-};
-
-template <int SS>
-__device__ __forceinline__ void load_epi_params(const RolloutArgs& A, const LdsMap& L, int lane, EpiParams<SS>& P) {
-    const float* bout = L.hbias + A.L * A.Wpad;
-#pragma unroll
-    for (int k = 0; k < SS; ++k) {
-        const int d = min((lane & 15) + 16 * k, A.s - 1);
-        P.om[k] = L.obs_mean[d]; P.os[k] = L.obs_std[d]; P.goal[k] = L.goal[d]; P.cw[k] = L.cw[d]; P.bo[k] = bout[d];
-    }
-#pragma unroll
-    for (int k = 0; k < MAX_A_PER_LANE; ++k) {
-        const int d = min((lane & 15) + 16 * k, A.a - 1);
-        P.am[k] = L.act_mean[d]; P.as[k] = L.act_std[d];
-    }
-}
-
-// a_t -> normalised MLP input columns [s, s+a); returns this lane's share of sum_d (cosh(a_d/alpha)-1).
-template <int R, int SS, bool REG = (SS <= MBRL_EPI_REG_SLOTS)>
-__device__ __forceinline__ void stage_actions(const RolloutArgs& A, const EpiParams<SS>& P, const LdsMap& L, float* act,
-                                              int wave, int lane, const float (&av)[R][MAX_A_PER_LANE],
-                                              float (&acp)[R], int lda) {
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        const int m = epi_row(r, wave, lane);
-        float c = 0.f;
-#pragma unroll
-        for (int k = 0; k < MAX_A_PER_LANE; ++k) {
-            const int d = (lane & 15) + 16 * k;
-            if (d < A.a) {
-                const float x = av[r][k];
-                // wide states keep no per-lane copies (see MBRL_EPI_REG_SLOTS): same values from LDS
-                const float am = REG ? P.am[k] : L.act_mean[d];
-                const float as = REG ? P.as[k] : L.act_std[d];
-                const float xn = A.norm_a ? (x - am) / as : x;
-                act[m * lda + A.s + d] = xn;
-                if (A.reward) L.aterm[m * A.a + d] = xn;   // the state pass re-reads a_t
-                if (A.has_ac) c += coshf(x / A.alpha_a) - 1.0f;
-            }
-        }
-        acp[r] = c;
-    }
 }
 
 // ---- column-split pairs (rollout_kernel PAIR) --------------------------------------------------
@@ -459,6 +374,7 @@ __global__ void __launch_bounds__(64 * NW, 1) rollout_kernel(const RolloutArgs A
     float av[R][MAX_A_PER_LANE];
     float acp[R];  // this lane's share of the current step's CoshLoss sum, per row
     if (actw) fetch_actions<R>(A, tile, 0, awave, lane, av);
+    // (inline, not stage_params / stage_s0: through the helpers the column-split pair instances' step loops grew)
     for (int i = tid; i < A.s; i += NT) {
         L.obs_mean[i] = A.obs_mean ? A.obs_mean[i] : 0.f;
         L.obs_std[i] = A.obs_std ? A.obs_std[i] : 1.f;
@@ -486,12 +402,7 @@ __global__ void __launch_bounds__(64 * NW, 1) rollout_kernel(const RolloutArgs A
     load_epi_params<SS>(A, L, lane, P);
     if (actw) {
         stage_actions<R, SS, EREG>(A, P, L, actX, awave, lane, av, acp, lda);
-        if (split)
-#pragma unroll
-            for (int r = 0; r < R; ++r) {
-                const float v = rowsum16(acp[r]);      // all 16 lanes of the row take part in the DPP sum
-                if ((lane & 15) == 0) acs[epi_row(r, awave, lane)] = v;
-            }
+        if (split) publish_action_cost<R>(acs, 0, M, awave, lane, acp);
     }
     // reward-head models: two MLP passes per step (state pass on (s_t, a_t), reward pass on
     // (s_{t+1}, a_t)); the normalised s_{t+1} and a_t are kept in LDS across the passes
@@ -660,8 +571,7 @@ __global__ void __launch_bounds__(64 * NW, 1) rollout_kernel(const RolloutArgs A
                 partials();
                 if (t + 1 < A.H) {
                     stage_actions<R, SS, EREG>(A, P, L, actX, awave, lane, av, acp, lda);
-                    const float v = rowsum16(acp[0]);
-                    if ((lane & 15) == 0) acs[((t + 1) & 1) * M + epi_row(0, awave, lane)] = v;
+                    publish_action_cost<R>(acs, (t + 1) & 1, M, awave, lane, acp);
                 }
                 __syncthreads();         // epilogue done
             }
@@ -941,11 +851,7 @@ __global__ void __launch_bounds__(64 * NW, 1) rollout_kernel(const RolloutArgs A
         } else if (split && actw && t + 1 < A.H) {
             // waves 4-7, concurrently: a_{t+1} into the next MLP input, its CoshLoss row sum into LDS
             stage_actions<R, SS, EREG>(A, P, L, actX, awave, lane, av, acp, lda);
-#pragma unroll
-            for (int r = 0; r < R; ++r) {
-                const float v = rowsum16(acp[r]);
-                if ((lane & 15) == 0) acs[((t + 1) & 1) * M + epi_row(r, awave, lane)] = v;
-            }
+            publish_action_cost<R>(acs, (t + 1) & 1, M, awave, lane, acp);
         }
         __syncthreads();
         STAMP(6);
@@ -953,20 +859,9 @@ __global__ void __launch_bounds__(64 * NW, 1) rollout_kernel(const RolloutArgs A
 #undef MBRL_HIDDEN_CHUNK
 #undef MBRL_LOAD_CHUNK
 #ifdef MBRL_STAMPS
-    seg[NSEG - 1] = __builtin_amdgcn_s_memrealtime() - rt0;
-    if (lane == 0 && g_mbrl_stamps != nullptr) {
-        unsigned long long* dst = g_mbrl_stamps + (((size_t)e * ntiles + tile) * NW + wave) * NSEG;
-#pragma unroll
-        for (int k = 0; k < NSEG; ++k) dst[k] = seg[k];
-    }
+    write_stamps(g_mbrl_stamps, seg, rt0, (size_t)e * ntiles + tile, NW, wave, lane);
 #endif
-    if (epi && (lane & 15) == 0 && (!PAIR || half == 0)) {
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            const int n = tile * M + epi_row(r, wave, lane);
-            if (n < A.N) A.costs[(size_t)e * A.N + n] = total[r];
-        }
-    }
+    if (epi && half == 0) write_costs<R>(A, tile, e, wave, lane, total);   // PAIR: half 0 writes the tile's returns
 }
 
 // The ring instances compile the LDS row strides in (rollout_kernel LDAC / PWC): the geometry must
@@ -975,6 +870,19 @@ template <int T, int K0C_T, int NOT_T>
 static bool ring_strides_ok(const RolloutArgs& A) {
     if constexpr (K0C_T == 0) return true;
     else return A.lda == (64 * T > 16 * K0C_T ? 64 * T : 16 * K0C_T) + 4 && A.pw == 16 * NOT_T + 4;
+}
+
+// One workgroup of `threads` per M-candidate tile and member (a flat grid under xcd_map), with the
+// tile height's LDS footprint. A.nw is set by the caller: the footprint depends on it.
+template <class Fn>
+static hipError_t launch_tiles(Fn fn, const RolloutArgs& A, int M, int threads, hipStream_t stream) {
+    const int ntiles = (A.N + M - 1) / M;
+    const dim3 grid = A.xcd_map ? dim3(ntiles * A.E) : dim3(ntiles, A.E);
+    const size_t lds = rollout_lds_bytes(A, M);
+    hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(fn), 160 * 1024);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(fn, grid, dim3(threads), lds, stream, A);
+    return hipGetLastError();
 }
 
 template <int T, int R, int K0C_T, int NOT_T, int NW, bool GS = false>
@@ -987,15 +895,7 @@ static hipError_t launch_rollout_tr(const RolloutArgs& A_in, hipStream_t stream)
     RolloutArgs A = A_in;
     A.nw = NW;
     if (!ring_strides_ok<T, K0C_T, NOT_T>(A)) return hipErrorInvalidValue;
-    const int M = 16 * R;
-    const int ntiles = (A.N + M - 1) / M;
-    const dim3 grid = A.xcd_map ? dim3(ntiles * A.E) : dim3(ntiles, A.E);
-    const size_t lds = rollout_lds_bytes(A, M);
-    const auto fn = &rollout_kernel<T, R, K0C_T, NOT_T, NW, false, GS>;
-    hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(fn), 160 * 1024);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(fn, grid, dim3(64 * NW), lds, stream, A);
-    return hipGetLastError();
+    return launch_tiles(&rollout_kernel<T, R, K0C_T, NOT_T, NW, false, GS>, A, 16 * R, 64 * NW, stream);
 }
 
 template <int T, int R, int NW>
@@ -1104,6 +1004,26 @@ hipError_t launch_rollout_pair(const RolloutArgs& A, int T, hipStream_t stream) 
 constexpr bool m8_kp(int T, int NOT) { return T == 4 && NOT == 2; }
 constexpr int m8_waves(int T, int NOT) { return m8_kp(T, NOT) ? 8 : T; }
 
+// The 8- and 4-candidate kernels' weight ring: chunk g of the step sequence into one slot of RSL
+// float4 per lane. g wraps into the next step past the CSQ slots of a step (C real chunks, then the
+// ring-alignment slots, which reload chunk C - 1); a chunk is 4096 T bytes, a load 1 KiB.
+template <int RSL>
+__device__ __forceinline__ void ring_load4x4(f32x4 (&dst)[RSL], __amdgpu_buffer_rsrc_t rsrc, unsigned lane_off, int g,
+                                             int C, int CSQ, int T) {
+    if (g >= CSQ) g -= CSQ;
+    g = g < C ? g : C - 1;
+    const int so = g * (4096 * T);
+#pragma unroll
+    for (int s = 0; s < RSL; ++s)
+        dst[s] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, lane_off + s * 1024, so, 0));
+}
+
+// B fragments of one 16-deep chunk: X[cand][col + 4 q .. + 3], q = 0..3
+__device__ __forceinline__ void read_b4(f32x4 (&b)[4], const float* in, int cand, int lda, int col) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) b[q] = *reinterpret_cast<const f32x4*>(in + cand * lda + col + 4 * q);
+}
+
 // K0L > 0 (compile time): every real input index k = s + a is below K0L, so layer-0 MFMAs whose k is
 // >= K0L (zero padding: weight and activation both +0) are not issued -- bit-identical, since the
 // accumulator starts at +0 and a round-to-nearest sum never turns +0 into -0. Instantiated for
@@ -1157,42 +1077,15 @@ __global__ void __launch_bounds__(64 * m8_waves(T, NOT_T), 1) rollout_m8_kernel(
     const int rofc = 2 * FPW * wave >= 64 * T ? KH / 2 : 0;
     float av[1][MAX_A_PER_LANE];
     float acp[1];
-    auto fetch_a = [&](int t) {
-        const int n = min(tile * M + epi_row(0, awave, lane), A.N - 1);
-        const float* src = A.actions + ((size_t)t * A.N + n) * A.a;
-#pragma unroll
-        for (int k = 0; k < MAX_A_PER_LANE; ++k) av[0][k] = src[min((lane & 15) + 16 * k, A.a - 1)];
-    };
-    if (actw) fetch_a(0);
-    for (int i = tid; i < A.s; i += NT) {
-        L.obs_mean[i] = A.obs_mean ? A.obs_mean[i] : 0.f;
-        L.obs_std[i] = A.obs_std ? A.obs_std[i] : 1.f;
-        L.goal[i] = A.goal ? A.goal[i] : 0.f;
-        L.cw[i] = A.cw ? A.cw[i] : 0.f;
-    }
-    for (int i = tid; i < A.a; i += NT) {
-        L.act_mean[i] = A.act_mean ? A.act_mean[i] : 0.f;
-        L.act_std[i] = A.act_std ? A.act_std[i] : 1.f;
-    }
-    const float* bias_src = member + A.stream_floats;
-    for (int i = tid; i < A.L * A.Wpad + 16 * A.NOT; i += NT) L.hbias[i] = bias_src[i];
+    if (actw) fetch_actions<1, M>(A, tile, 0, awave, lane, av);
+    stage_params(A, L, member, tid, NT);
     __syncthreads();
-    for (int i = tid; i < M * A.s; i += NT) {
-        const int m = i / A.s, d = i - (i / A.s) * A.s;
-        const int n = min(tile * M + m, A.N - 1);
-        const float sv = A.s0_per_cand ? A.s0[(size_t)n * A.s + d] : A.s0[d];
-        actX[m * lda + d] = A.norm_s ? (sv - L.obs_mean[d]) / L.obs_std[d] : sv;
-    }
-    for (int i = tid; i < M * A.k0pad_extra; i += NT) {
-        const int m = i / A.k0pad_extra, j = i - (i / A.k0pad_extra) * A.k0pad_extra;
-        actX[m * lda + A.s + A.a + j] = 0.f;
-    }
+    stage_s0<M>(A, L, actX, lda, tile, tid, NT);
     EpiParams<SS> P;
     load_epi_params<SS>(A, L, lane, P);
     if (actw) {
         stage_actions<1, SS>(A, P, L, actX, awave, lane, av, acp, lda);
-        const float v = rowsum16(acp[0]);
-        if ((lane & 15) == 0) acs[epi_row(0, awave, lane)] = v;
+        publish_action_cost<1>(acs, 0, M, awave, lane, acp);
     }
     if (tid < NW) lflag[tid] = 0;
     __syncthreads();
@@ -1204,30 +1097,18 @@ __global__ void __launch_bounds__(64 * m8_waves(T, NOT_T), 1) rollout_m8_kernel(
         const_cast<float*>(member + A.m8_off), 0, (int)((size_t)C8 * 4096 * T), 0x00020000);
     const unsigned lane_off = (unsigned)(wave * RSL * 1024 + lane * 16);
     f32x4 ring[NB][RSL];
-#define M8_LOAD(SLOT, G)                                                                          \
-    do {                                                                                          \
-        int gg_ = (G);                                                                            \
-        if (gg_ >= CSQ) gg_ -= CSQ;                                                               \
-        gg_ = gg_ < C8 ? gg_ : C8 - 1;                                                            \
-        const int so_ = gg_ * (4096 * T);                                                         \
-        _Pragma("unroll") for (int s_ = 0; s_ < RSL; ++s_) ring[SLOT][s_] = __builtin_bit_cast(   \
-            f32x4, __builtin_amdgcn_raw_buffer_load_b128(wrsrc, lane_off + s_ * 1024, so_, 0));   \
-    } while (0)
+    auto ring_load = [&](f32x4 (&dst)[RSL], int G) { ring_load4x4<RSL>(dst, wrsrc, lane_off, G, C8, CSQ, T); };
 #pragma unroll
-    for (int q = 0; q < NB - 1; ++q) M8_LOAD(q, q);
+    for (int q = 0; q < NB - 1; ++q) ring_load(ring[q], q);
     f32x4 bb[2][4];     // B: X[cand][16 kc + 4 q' .. +3], double-buffered over chunks
     f32x4 acc[TPW];
     f32x4 bias[TPW];
-    float total = 0.f;
+    float total[1] = {0.f};
 #ifdef MBRL_STAMPS
     unsigned long long seg[NSEG] = {0, 0, 0, 0, 0, 0, 0, 0};
     unsigned long long tprev = __builtin_amdgcn_s_memtime();
     const unsigned long long rt0 = __builtin_amdgcn_s_memrealtime();   // 100 MHz: seg[7] -> clock
 #endif
-    auto read_b = [&](f32x4 (&b)[4], const float* in, int col) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) b[q] = *reinterpret_cast<const f32x4*>(in + cand * lda + col + 4 * q);
-    };
     auto mma_pair = [&](const f32x4 (&w)[RSL], const f32x4 (&b)[4]) {
         if constexpr (KP) {
             // pair i: chunk positions 2i (ABID 0) and 2i + 1 (ABID 1), position p = 4 s + q
@@ -1291,10 +1172,10 @@ __global__ void __launch_bounds__(64 * m8_waves(T, NOT_T), 1) rollout_m8_kernel(
         for (int u = 0; u < TPW; ++u) acc[u] = f32x4{0.f, 0.f, 0.f, 0.f};
     };
 // one hidden-type chunk: refill the slot chunk c-1 vacated, read the next chunk's B, MFMAs of chunk c
-#define M8_CHUNK(SLOT, KC, NK, IN)                                          \
-    do {                                                                    \
-        M8_LOAD(((SLOT) + NB - 1) % NB, g + NB - 1);                         \
-        if ((KC) + 1 < (NK)) read_b(bb[((KC) + 1) & 1], IN, 16 * ((KC) + 1)); \
+#define M8_CHUNK(SLOT, KC, NK, IN)                                                        \
+    do {                                                                                  \
+        ring_load(ring[((SLOT) + NB - 1) % NB], g + NB - 1);                              \
+        if ((KC) + 1 < (NK)) read_b4(bb[((KC) + 1) & 1], IN, cand, lda, 16 * ((KC) + 1)); \
         mma_pair(ring[SLOT], bb[(KC) & 1]);                                 \
         MBRL_PIN();                                                         \
         ++g;                                                                \
@@ -1302,19 +1183,19 @@ __global__ void __launch_bounds__(64 * m8_waves(T, NOT_T), 1) rollout_m8_kernel(
 
     for (int t = 0; t < A.H; ++t) {
         int g = 0;
-        if (actw && t + 1 < A.H) fetch_a(t + 1);
+        if (actw && t + 1 < A.H) fetch_actions<1, M>(A, tile, t + 1, awave, lane, av);
         // ---- layer 0: actX [s | a | 0-pad] -> actY
         zero_acc8();
         load_bias8(L.hbias);
-        read_b(bb[0], actX, 0);
+        read_b4(bb[0], actX, cand, lda, 0);
         if constexpr (K0L > 0) {
             static_assert(K0C_T == 2, "K0L instance");
-            M8_LOAD((0 + NB - 1) % NB, g + NB - 1);
-            read_b(bb[1], actX, 16);
+            ring_load(ring[(0 + NB - 1) % NB], g + NB - 1);
+            read_b4(bb[1], actX, cand, lda, 16);
             mma_pair_l0(ring[0], bb[0], std::integral_constant<int, 0>());
             MBRL_PIN();
             ++g;
-            M8_LOAD((1 + NB - 1) % NB, g + NB - 1);
+            ring_load(ring[(1 + NB - 1) % NB], g + NB - 1);
             mma_pair_l0(ring[1], bb[1], std::integral_constant<int, 1>());
             MBRL_PIN();
             ++g;
@@ -1334,7 +1215,7 @@ __global__ void __launch_bounds__(64 * m8_waves(T, NOT_T), 1) rollout_m8_kernel(
             // the half-rotated K order (rollout_kernel): position kc reads chunk (kc + rofc) mod KH
             const float* const inLo = in + 16 * rofc;
             const float* const inHi = in - 16 * rofc;
-            read_b(bb[0], inLo, 0);
+            read_b4(bb[0], inLo, cand, lda, 0);
 #pragma unroll
             for (int kc = 0; kc < KH; ++kc) M8_CHUNK((K0C_T + kc) % NB, kc, KH, (kc + 1 < KH / 2 ? inLo : inHi));
             STAMP(2);
@@ -1358,9 +1239,9 @@ __global__ void __launch_bounds__(64 * m8_waves(T, NOT_T), 1) rollout_m8_kernel(
 #pragma unroll
                 for (int o = 0; o < 2; ++o) {
                     f32x4 b[4];
-                    read_b(b, in, 32 * wave + 16 * o);
+                    read_b4(b, in, cand, lda, 32 * wave + 16 * o);
                     constexpr int base = K0C_T;
-                    M8_LOAD((base + o + NB - 1) % NB, g + NB - 1);
+                    ring_load(ring[(base + o + NB - 1) % NB], g + NB - 1);
 #pragma unroll
                     for (int i = 0; i < 8; ++i) {
                         const float a = ring[(base + o) % NB][i >> 2][i & 3];
@@ -1377,10 +1258,10 @@ __global__ void __launch_bounds__(64 * m8_waves(T, NOT_T), 1) rollout_m8_kernel(
 #pragma unroll
                 for (int o = 0; o < 2; ++o) {
                     f32x4 b0[4], b1[4];
-                    read_b(b0, in, FPW * wave + 32 * o);
-                    read_b(b1, in, FPW * wave + 32 * o + 16);
+                    read_b4(b0, in, cand, lda, FPW * wave + 32 * o);
+                    read_b4(b1, in, cand, lda, FPW * wave + 32 * o + 16);
                     constexpr int base = K0C_T;
-                    M8_LOAD((base + o + NB - 1) % NB, g + NB - 1);
+                    ring_load(ring[(base + o + NB - 1) % NB], g + NB - 1);
                     const int j0 = (2 * o) / TW16, j1 = (2 * o + 1) / TW16;
                     // chain s: chunk 2o (q = 0..3, ABID 0), then chunk 2o + 1 (ABID 1) -- the
                     // 16-candidate kernel's kc-then-q order
@@ -1402,11 +1283,11 @@ __global__ void __launch_bounds__(64 * m8_waves(T, NOT_T), 1) rollout_m8_kernel(
 #pragma unroll
             for (int kc = 0; kc < 4; ++kc) {
                 f32x4 b[4];
-                read_b(b, in, FPW * wave + 16 * kc);
+                read_b4(b, in, cand, lda, FPW * wave + 16 * kc);
 #pragma unroll
                 for (int p = 0; p < NOP; ++p) {
                     constexpr int base = K0C_T;   // slots fold: kc, p are unrolled
-                    M8_LOAD(((base + kc * NOP + p) + NB - 1) % NB, g + NB - 1);
+                    ring_load(ring[((base + kc * NOP + p) + NB - 1) % NB], g + NB - 1);
                     const int j = kc / TW16;
 #pragma unroll
                     for (int s = 0; s < 4; ++s)
@@ -1425,7 +1306,7 @@ __global__ void __launch_bounds__(64 * m8_waves(T, NOT_T), 1) rollout_m8_kernel(
             }
 #pragma unroll
             for (int d = 0; d < DUM; ++d) {
-                M8_LOAD((K0C_T + NOC + d + NB - 1) % NB, g + NB - 1);
+                ring_load(ring[(K0C_T + NOC + d + NB - 1) % NB], g + NB - 1);
                 ++g;
             }
 #pragma unroll
@@ -1476,29 +1357,19 @@ __global__ void __launch_bounds__(64 * m8_waves(T, NOT_T), 1) rollout_m8_kernel(
             for (int d = A.s + A.a + j; d < A.s + A.a + A.k0pad_extra; d += 16) actX[m * lda + d] = 0.f;
             sc = rowsum16(sc);
             const float ac = acs[(t & 1) * M + m];
-            total += sc + A.alpha_a2 * (ac / (float)A.a);
+            total[0] += sc + A.alpha_a2 * (ac / (float)A.a);
         } else if (actw && t + 1 < A.H) {
             stage_actions<1, SS>(A, P, L, actX, awave, lane, av, acp, lda);
-            const float v = rowsum16(acp[0]);
-            if ((lane & 15) == 0) acs[((t + 1) & 1) * M + epi_row(0, awave, lane)] = v;
+            publish_action_cost<1>(acs, (t + 1) & 1, M, awave, lane, acp);
         }
         __syncthreads();
         STAMP(6);
     }
 #ifdef MBRL_STAMPS
-    seg[NSEG - 1] = __builtin_amdgcn_s_memrealtime() - rt0;
-    if (lane == 0 && g_mbrl_stamps != nullptr) {
-        unsigned long long* dst = g_mbrl_stamps + (((size_t)e * ntiles + tile) * 8 + wave) * NSEG;
-#pragma unroll
-        for (int k = 0; k < NSEG; ++k) dst[k] = seg[k];
-    }
+    write_stamps(g_mbrl_stamps, seg, rt0, (size_t)e * ntiles + tile, 8, wave, lane);
 #endif
 #undef M8_CHUNK
-#undef M8_LOAD
-    if (epi && (lane & 15) == 0) {
-        const int n = tile * M + epi_row(0, wave, lane);
-        if (n < A.N) A.costs[(size_t)e * A.N + n] = total;
-    }
+    if (epi) write_costs<1, M>(A, tile, e, wave, lane, total);
 }
 
 bool rollout_m8_supported(const RolloutArgs& A, int T) {
@@ -1512,13 +1383,7 @@ static hipError_t launch_m8_tr(const RolloutArgs& A_in, hipStream_t stream) {
     RolloutArgs A = A_in;
     A.nw = 8;   // output partials: the 8-wave kernel's count
     if (!ring_strides_ok<T, K0C_T, NOT_T>(A)) return hipErrorInvalidValue;
-    const dim3 grid = A.xcd_map ? dim3((A.N + 7) / 8 * A.E) : dim3((A.N + 7) / 8, A.E);
-    const size_t lds = rollout_lds_bytes(A, 8);
-    const auto fn = &rollout_m8_kernel<T, K0C_T, NOT_T, K0L>;
-    hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(fn), 160 * 1024);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(fn, grid, dim3(64 * m8_waves(T, NOT_T)), lds, stream, A);
-    return hipGetLastError();
+    return launch_tiles(&rollout_m8_kernel<T, K0C_T, NOT_T, K0L>, A, 8, 64 * m8_waves(T, NOT_T), stream);
 }
 
 template <int T>
@@ -1588,42 +1453,15 @@ __global__ void __launch_bounds__(64 * T, 1) rollout_m4_kernel(const RolloutArgs
     const int cand = lane & 3;
     float av[1][MAX_A_PER_LANE];
     float acp[1];
-    auto fetch_a = [&](int t) {
-        const int n = min(tile * M + epi_row(0, awave, lane), A.N - 1);
-        const float* src = A.actions + ((size_t)t * A.N + n) * A.a;
-#pragma unroll
-        for (int k = 0; k < MAX_A_PER_LANE; ++k) av[0][k] = src[min((lane & 15) + 16 * k, A.a - 1)];
-    };
-    if (actw) fetch_a(0);
-    for (int i = tid; i < A.s; i += NT) {
-        L.obs_mean[i] = A.obs_mean ? A.obs_mean[i] : 0.f;
-        L.obs_std[i] = A.obs_std ? A.obs_std[i] : 1.f;
-        L.goal[i] = A.goal ? A.goal[i] : 0.f;
-        L.cw[i] = A.cw ? A.cw[i] : 0.f;
-    }
-    for (int i = tid; i < A.a; i += NT) {
-        L.act_mean[i] = A.act_mean ? A.act_mean[i] : 0.f;
-        L.act_std[i] = A.act_std ? A.act_std[i] : 1.f;
-    }
-    const float* bias_src = member + A.stream_floats;
-    for (int i = tid; i < A.L * A.Wpad + 16 * A.NOT; i += NT) L.hbias[i] = bias_src[i];
+    if (actw) fetch_actions<1, M>(A, tile, 0, awave, lane, av);
+    stage_params(A, L, member, tid, NT);
     __syncthreads();
-    for (int i = tid; i < M * A.s; i += NT) {
-        const int m = i / A.s, d = i - (i / A.s) * A.s;
-        const int n = min(tile * M + m, A.N - 1);
-        const float sv = A.s0_per_cand ? A.s0[(size_t)n * A.s + d] : A.s0[d];
-        actX[m * lda + d] = A.norm_s ? (sv - L.obs_mean[d]) / L.obs_std[d] : sv;
-    }
-    for (int i = tid; i < M * A.k0pad_extra; i += NT) {
-        const int m = i / A.k0pad_extra, j = i - (i / A.k0pad_extra) * A.k0pad_extra;
-        actX[m * lda + A.s + A.a + j] = 0.f;
-    }
+    stage_s0<M>(A, L, actX, lda, tile, tid, NT);
     EpiParams<SS> P;
     load_epi_params<SS>(A, L, lane, P);
     if (actw) {
         stage_actions<1, SS>(A, P, L, actX, awave, lane, av, acp, lda);
-        const float v = rowsum16(acp[0]);
-        if ((lane & 15) == 0) acs[epi_row(0, awave, lane)] = v;
+        publish_action_cost<1>(acs, 0, M, awave, lane, acp);
     }
     __syncthreads();
 
@@ -1634,26 +1472,14 @@ __global__ void __launch_bounds__(64 * T, 1) rollout_m4_kernel(const RolloutArgs
         const_cast<float*>(member + A.m4_off), 0, (int)((size_t)C4 * 4096 * T), 0x00020000);
     const unsigned lane_off = (unsigned)(wave * 4 * 1024 + lane * 16);
     f32x4 ring[NB][4];
-#define M4_LOAD(SLOT, G)                                                                          \
-    do {                                                                                          \
-        int gg_ = (G);                                                                            \
-        if (gg_ >= CSQ) gg_ -= CSQ;                                                               \
-        gg_ = gg_ < C4 ? gg_ : C4 - 1;                                                            \
-        const int so_ = gg_ * (4096 * T);                                                         \
-        _Pragma("unroll") for (int s_ = 0; s_ < 4; ++s_) ring[SLOT][s_] = __builtin_bit_cast(     \
-            f32x4, __builtin_amdgcn_raw_buffer_load_b128(wrsrc, lane_off + s_ * 1024, so_, 0));   \
-    } while (0)
+    auto ring_load = [&](f32x4 (&dst)[4], int G) { ring_load4x4<4>(dst, wrsrc, lane_off, G, C4, CSQ, T); };
 #pragma unroll
-    for (int q = 0; q < NB - 1; ++q) M4_LOAD(q, q);
+    for (int q = 0; q < NB - 1; ++q) ring_load(ring[q], q);
     f32x4 bb[2][4];     // B: X[cand][16 kc + 4 q' .. +3], double-buffered over chunks
     f32x4 acc;
     f32x4 bias;
-    float total = 0.f;
+    float total[1] = {0.f};
     const int row0 = 64 * wave + 32 * ((lane >> 2) & 1) + 4 * (lane >> 3);   // this lane's 4 D rows
-    auto read_b = [&](f32x4 (&b)[4], const float* in, int col) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) b[q] = *reinterpret_cast<const f32x4*>(in + cand * lda + col + 4 * q);
-    };
     auto mma_chunk = [&](const f32x4 (&w)[4], const f32x4 (&b)[4]) {
 #pragma unroll
         for (int s = 0; s < 4; ++s)
@@ -1673,10 +1499,10 @@ __global__ void __launch_bounds__(64 * T, 1) rollout_m4_kernel(const RolloutArgs
         v = __builtin_elementwise_max(v, f32x4{0.f, 0.f, 0.f, 0.f});
         *reinterpret_cast<f32x4*>(out + cand * lda + row0) = v;
     };
-#define M4_CHUNK(SLOT, KC, NK, IN)                                          \
-    do {                                                                    \
-        M4_LOAD(((SLOT) + NB - 1) % NB, g + NB - 1);                         \
-        if ((KC) + 1 < (NK)) read_b(bb[((KC) + 1) & 1], IN, 16 * ((KC) + 1)); \
+#define M4_CHUNK(SLOT, KC, NK, IN)                                                        \
+    do {                                                                                  \
+        ring_load(ring[((SLOT) + NB - 1) % NB], g + NB - 1);                              \
+        if ((KC) + 1 < (NK)) read_b4(bb[((KC) + 1) & 1], IN, cand, lda, 16 * ((KC) + 1)); \
         mma_chunk(ring[SLOT], bb[(KC) & 1]);                                \
         MBRL_PIN();                                                         \
         ++g;                                                                \
@@ -1684,19 +1510,19 @@ __global__ void __launch_bounds__(64 * T, 1) rollout_m4_kernel(const RolloutArgs
 
     for (int t = 0; t < A.H; ++t) {
         int g = 0;
-        if (actw && t + 1 < A.H) fetch_a(t + 1);
+        if (actw && t + 1 < A.H) fetch_actions<1, M>(A, tile, t + 1, awave, lane, av);
         // ---- layer 0: actX [s | a | 0-pad] -> actY
         acc = f32x4{0.f, 0.f, 0.f, 0.f};
         bias = *reinterpret_cast<const f32x4*>(L.hbias + row0);
-        read_b(bb[0], actX, 0);
+        read_b4(bb[0], actX, cand, lda, 0);
         if constexpr (K0L > 0) {
             static_assert(K0C_T == 2, "K0L instance");
-            M4_LOAD((0 + NB - 1) % NB, g + NB - 1);
-            read_b(bb[1], actX, 16);
+            ring_load(ring[(0 + NB - 1) % NB], g + NB - 1);
+            read_b4(bb[1], actX, cand, lda, 16);
             mma_chunk_l0(ring[0], bb[0], std::integral_constant<int, 0>());
             MBRL_PIN();
             ++g;
-            M4_LOAD((1 + NB - 1) % NB, g + NB - 1);
+            ring_load(ring[(1 + NB - 1) % NB], g + NB - 1);
             mma_chunk_l0(ring[1], bb[1], std::integral_constant<int, 1>());
             MBRL_PIN();
             ++g;
@@ -1715,7 +1541,7 @@ __global__ void __launch_bounds__(64 * T, 1) rollout_m4_kernel(const RolloutArgs
             const int rof = 2 * wave >= T ? 16 * (KH / 2) : 0;
             const float* const inLo = in + rof;
             const float* const inHi = in - rof;
-            read_b(bb[0], inLo, 0);
+            read_b4(bb[0], inLo, cand, lda, 0);
 #pragma unroll
             for (int kc = 0; kc < KH; ++kc) M4_CHUNK((K0C_T + kc) % NB, kc, KH, (kc + 1 < KH / 2 ? inLo : inHi));
             store_layer(out);
@@ -1737,7 +1563,7 @@ __global__ void __launch_bounds__(64 * T, 1) rollout_m4_kernel(const RolloutArgs
                 for (int q = 0; q < 4; ++q)
                     hq[q] = *reinterpret_cast<const f32x4*>(in + cand * lda + 64 * wave + 16 * o + 4 * q);
                 constexpr int base = K0C_T;   // output chunk o sits in slot (K0C + KH + o) % NB
-                M4_LOAD(((base + o) + NB - 1) % NB, g + NB - 1);
+                ring_load(ring[((base + o) + NB - 1) % NB], g + NB - 1);
                 const int h = o / KPH;
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
@@ -1751,7 +1577,7 @@ __global__ void __launch_bounds__(64 * T, 1) rollout_m4_kernel(const RolloutArgs
             }
 #pragma unroll
             for (int d = 0; d < DUM; ++d) {
-                M4_LOAD((K0C_T + NOC + d + NB - 1) % NB, g + NB - 1);
+                ring_load(ring[(K0C_T + NOC + d + NB - 1) % NB], g + NB - 1);
                 ++g;
             }
             // (c0 + c1) + (c2 + c3): chains c ^ 1 / c ^ 2 sit 4 / 8 lanes away
@@ -1805,20 +1631,15 @@ __global__ void __launch_bounds__(64 * T, 1) rollout_m4_kernel(const RolloutArgs
             for (int d = A.s + A.a + j; d < A.s + A.a + A.k0pad_extra; d += 16) actX[m * lda + d] = 0.f;
             sc = rowsum16(sc);
             const float ac = acs[(t & 1) * M + m];
-            total += sc + A.alpha_a2 * (ac / (float)A.a);
+            total[0] += sc + A.alpha_a2 * (ac / (float)A.a);
         } else if (actw && t + 1 < A.H) {
             stage_actions<1, SS>(A, P, L, actX, awave, lane, av, acp, lda);
-            const float v = rowsum16(acp[0]);
-            if ((lane & 15) == 0) acs[((t + 1) & 1) * M + epi_row(0, awave, lane)] = v;
+            publish_action_cost<1>(acs, (t + 1) & 1, M, awave, lane, acp);
         }
         __syncthreads();
     }
 #undef M4_CHUNK
-#undef M4_LOAD
-    if (epi && (lane & 15) == 0) {
-        const int n = tile * M + epi_row(0, 0, lane);
-        if (n < A.N) A.costs[(size_t)e * A.N + n] = total;
-    }
+    if (epi) write_costs<1, M>(A, tile, e, 0, lane, total);
 }
 
 bool rollout_m4_supported(const RolloutArgs& A, int T, int NG) {
@@ -1832,14 +1653,7 @@ static hipError_t launch_m4_tr(const RolloutArgs& A_in, hipStream_t stream) {
     RolloutArgs A = A_in;
     A.nw = 8;   // output partials: the canonical 8
     if (!ring_strides_ok<T, K0C_T, (NG + 1) & ~1>(A)) return hipErrorInvalidValue;
-    const int ntiles = (A.N + 3) / 4;
-    const dim3 grid = A.xcd_map ? dim3(ntiles * A.E) : dim3(ntiles, A.E);
-    const size_t lds = rollout_lds_bytes(A, 4);
-    const auto fn = &rollout_m4_kernel<T, K0C_T, NG, K0L>;
-    hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(fn), 160 * 1024);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(fn, grid, dim3(64 * T), lds, stream, A);
-    return hipGetLastError();
+    return launch_tiles(&rollout_m4_kernel<T, K0C_T, NG, K0L>, A, 4, 64 * T, stream);
 }
 
 template <int T, int K0C_T>

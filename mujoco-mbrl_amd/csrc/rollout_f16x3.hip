@@ -39,6 +39,7 @@
 #include <stdint.h>
 
 #include "mbrl_internal.h"
+#include "mbrl_rollout_dev.h"
 
 namespace mbrl {
 
@@ -160,14 +161,6 @@ __device__ __forceinline__ f32x4 layer_out(const f32x4 (&acc)[TW], const float* 
     return __builtin_elementwise_max(v, f32x4{0.f, 0.f, 0.f, 0.f});
 }
 
-__device__ __forceinline__ float rowsum16(float v) {
-    v += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0x128, 0xF, 0xF, false));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0x124, 0xF, 0xF, false));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0x122, 0xF, 0xF, false));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0x121, 0xF, 0xF, false));
-    return v;
-}
-
 template <int T, int R, int P, int TS, int K0S, int NOS>
 struct SplitRollout {
     static constexpr int M = 16 * R;        // candidates per workgroup (R 16-column B tiles)
@@ -261,18 +254,7 @@ struct SplitRollout {
     }
 
     __device__ void prologue() {
-        for (int i = threadIdx.x; i < A.s; i += 64 * SW) {
-            L.obs_mean[i] = A.obs_mean ? A.obs_mean[i] : 0.f;
-            L.obs_std[i] = A.obs_std ? A.obs_std[i] : 1.f;
-            L.goal[i] = A.goal ? A.goal[i] : 0.f;
-            L.cw[i] = A.cw ? A.cw[i] : 0.f;
-        }
-        for (int i = threadIdx.x; i < A.a; i += 64 * SW) {
-            L.act_mean[i] = A.act_mean ? A.act_mean[i] : 0.f;
-            L.act_std[i] = A.act_std ? A.act_std[i] : 1.f;
-        }
-        const float* bias_src = A.packed + (size_t)e * A.member_stride + A.stream_floats;
-        for (int i = threadIdx.x; i < A.L * A.Wpad + 16 * A.NOT; i += 64 * SW) L.hbias[i] = bias_src[i];
+        stage_params(A, L, A.packed + (size_t)e * A.member_stride, threadIdx.x, 64 * SW);
         if (threadIdx.x == 0) L.flag[0] = 0;
         if (actw) fetch_actions(0);
         __syncthreads();
