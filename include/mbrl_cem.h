@@ -814,6 +814,37 @@ int mbrl_train_epoch(const mbrl_train_model* model, const mbrl_train_data* data,
                      const mbrl_adam_hparams* hparams, const float* step_sizes, const float* bc2_sqrt, float* losses,
                      void* workspace, size_t ws_bytes, mbrl_stream_t stream);
 
+/* ---- ensemble training (added within ABI v13): E members of one shape -- a PETS-style ensemble, each
+ * member on its own bootstrap resample of one dataset -- trained in shared launches. `members` is a host
+ * array of E mbrl_train_model with equal state_dim, action_dim, hidden, n_hidden, reward_head and
+ * horizon and with their own weight, bias and gradient buffers. Member e's result -- gradients,
+ * parameters, Adam state and losses -- is that of mbrl_train_grads / mbrl_train_epoch on that member
+ * alone with its own rows, bit for bit.
+ * Launches per batch: 2 (n_hidden + 1) of the tiled product kernel (the MBRL_OPT_TRAIN_SPLIT layout with
+ * the layer-0 weight gradient in its own launch, the member on a grid axis) and, in the epoch call, one
+ * Adam launch over all E * count tensors (up to 64 tensors per launch; more take further launches) --
+ * whatever E is. None of these launches waits on another workgroup: every hand-off is a kernel boundary
+ * on the stream. The training options (MBRL_OPT_TRAIN_*) other than MBRL_OPT_TRAIN_TILE do not apply.
+ * batch_idx: [E][batch] device rows; orders: [E][rows] device rows (indices may repeat; each
+ * < transitions, not checked on the device). tensors: [E][count] host; step_sizes, bc2_sqrt:
+ * [batches][E * count] host; loss_out: [E][3], losses: [batches][E][3] device floats or NULL.
+ * workspace >= mbrl_train_ensemble_workspace_bytes(members, E, batch) (0 for a bad shape); it needs no
+ * zeroing and holds no status word.
+ * Before any launch: MBRL_EINVAL for E < 1, members whose shapes differ, any NULL mbrl_train_epoch
+ * rejects, or a weight, bias or gradient pointer bound twice among the members; MBRL_EUNSUPPORTED for
+ * E > MBRL_TRAIN_MAX_MEMBERS (the members' pointer table travels in the launch arguments);
+ * MBRL_EWORKSPACE for a workspace that is too small. */
+#define MBRL_TRAIN_MAX_MEMBERS 8
+size_t mbrl_train_ensemble_workspace_bytes(const mbrl_train_model* members, int32_t E, int32_t batch);
+int mbrl_train_grads_ensemble(const mbrl_train_model* members, int32_t E, const mbrl_train_data* data,
+                              const int64_t* batch_idx, int32_t batch, float* loss_out, void* workspace,
+                              size_t ws_bytes, mbrl_stream_t stream);
+int mbrl_train_epoch_ensemble(const mbrl_train_model* members, int32_t E, const mbrl_train_data* data,
+                              const int64_t* orders, int64_t rows, int32_t batch_size, const mbrl_adam_tensor* tensors,
+                              int32_t count, const mbrl_adam_hparams* hparams, const float* step_sizes,
+                              const float* bc2_sqrt, float* losses, void* workspace, size_t ws_bytes,
+                              mbrl_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -605,12 +605,23 @@ struct TrainGather {
     int slot;
 };
 bool train_fused_applies(const TrainShape& t, int batch);
+// E members of one shape in shared launches (mbrl_train_*_ensemble): launch_train_grads is called with
+// member 0's tensors, rows, loss_out and workspace; member e's rows, loss_out and workspace lie e strides
+// on, and its parameters and gradients come from members[e]. The multi-launch layout only (t.fold == 0,
+// t.split == 1, no Adam step): no launch waits on another workgroup.
+struct TrainEnsemble {
+    const mbrl_train_model* members;
+    int E;
+    int64_t ws_stride;    // floats
+    int64_t idx_stride;   // rows
+    int loss_stride;      // floats
+};
 hipError_t launch_train_grads(const TrainShape& t, const TrainTensors& w, const int64_t* idx, int batch,
                               float* loss_out, float* ws, hipStream_t stream, const mbrl_adam_tensor* adam = nullptr,
                               const mbrl_adam_hparams* hp = nullptr, int arith = 0,
                               const mbrl_adam_tensor* prior = nullptr, int prior_n = 0,
                               mbrl_adam_tensor* pending = nullptr, int* pending_n = nullptr,
-                              const TrainGather* gather = nullptr);
+                              const TrainGather* gather = nullptr, const TrainEnsemble* ens = nullptr);
 
 // ---- cooperative single-candidate kernels (traj.hip, gd.hip): the dot of one 16-row slice, one row
 // per half-wave (32 lanes), and its reduction

@@ -27,13 +27,18 @@ namespace mbrl {
 constexpr int ADAM_THREADS = 256;
 constexpr int ADAM_CHUNK = ADAM_THREADS * 4;   // elements per workgroup (one float4 per lane)
 
-struct AdamLaunch {
-    mbrl_adam_tensor t[ADAM_MAX_TENSORS];
-    int first_block[ADAM_MAX_TENSORS + 1];      // workgroup prefix over the tensors' chunks
+// CAP tensors per launch: ADAM_MAX_TENSORS for one model's group; ADAM_ENS_TENSORS for an ensemble's
+// members together (mbrl_train_epoch_ensemble), the most a launch's argument block holds.
+template <int CAP>
+struct AdamLaunchT {
+    mbrl_adam_tensor t[CAP];
+    int first_block[CAP + 1];                   // workgroup prefix over the tensors' chunks
     int count;
     mbrl_adam_hparams hp;
     int arith;                                  // AdamArith bits
 };
+using AdamLaunch = AdamLaunchT<ADAM_MAX_TENSORS>;
+constexpr int ADAM_ENS_TENSORS = 64;
 
 // One element of the chain. Bits of `arith` select which of torch's expressions were contracted to
 // a fused multiply-add by the compiler that built torch (ForeachFunctors.cuh / Lerp.h):
@@ -64,7 +69,8 @@ __device__ __forceinline__ void adam_element(float& p, float g, float& m, float&
     p = (arith & ADAM_FMA_ADDCDIV) ? fmaf(step_size, q, p) : p + step_size * q;
 }
 
-__global__ __launch_bounds__(ADAM_THREADS) void adam_step_kernel(const AdamLaunch L) {
+template <int CAP>
+__global__ __launch_bounds__(ADAM_THREADS) void adam_step_kernel(const AdamLaunchT<CAP> L) {
     const int blk = blockIdx.x;
     int ti = 0;
     while (ti + 1 < L.count && blk >= L.first_block[ti + 1]) ++ti;
@@ -99,17 +105,18 @@ __global__ __launch_bounds__(ADAM_THREADS) void adam_step_kernel(const AdamLaunc
     }
 }
 
-hipError_t launch_adam_step(const mbrl_adam_tensor* tensors, int count, const mbrl_adam_hparams& hp, int arith,
-                            hipStream_t stream) {
-    AdamLaunch L{};
+template <int CAP>
+static hipError_t launch_adam_step_cap(const mbrl_adam_tensor* tensors, int count, const mbrl_adam_hparams& hp,
+                                       int arith, hipStream_t stream) {
+    AdamLaunchT<CAP> L{};
     L.hp = hp;
     L.arith = arith;
     int blocks = 0;
     for (int i = 0; i <= count; ++i) {
         // launch when the table is full or the tensors are exhausted
-        if (L.count == ADAM_MAX_TENSORS || (i == count && L.count > 0)) {
+        if (L.count == CAP || (i == count && L.count > 0)) {
             L.first_block[L.count] = blocks;
-            hipLaunchKernelGGL(adam_step_kernel, dim3(blocks), dim3(ADAM_THREADS), 0, stream, L);
+            hipLaunchKernelGGL(adam_step_kernel<CAP>, dim3(blocks), dim3(ADAM_THREADS), 0, stream, L);
             const hipError_t e = hipGetLastError();
             if (e != hipSuccess) return e;
             L.count = 0;
@@ -122,6 +129,11 @@ hipError_t launch_adam_step(const mbrl_adam_tensor* tensors, int count, const mb
         ++L.count;
     }
     return hipSuccess;
+}
+
+hipError_t launch_adam_step(const mbrl_adam_tensor* tensors, int count, const mbrl_adam_hparams& hp, int arith,
+                            hipStream_t stream) {
+    return launch_adam_step_cap<ADAM_MAX_TENSORS>(tensors, count, hp, arith, stream);
 }
 
 // ================================================================================================
@@ -156,7 +168,7 @@ __device__ unsigned long long* g_train_stamps;
 #define TSTAMP(k)                                                                                    \
     do {                                                                                             \
         const unsigned probe_ = L.nd > 1 ? (unsigned)L.d[0].tiles : gridDim.x - 1;                 \
-        if (g_train_stamps && threadIdx.x == 0 && (blockIdx.x == 0 || blockIdx.x == probe_))        \
+        if (g_train_stamps && threadIdx.x == 0 && blockIdx.y == 0 && (blockIdx.x == 0 || blockIdx.x == probe_)) \
             g_train_stamps[L.slot * 8 + (blockIdx.x == 0 ? 0 : 4) + (k)] = __builtin_amdgcn_s_memrealtime(); \
     } while (0)
 // the fused kernels: slot `slot_`, first workgroup and the last
@@ -432,7 +444,9 @@ __device__ __forceinline__ void wait_arrivals(const unsigned* counter, unsigned 
 // DI: which of the launch's products, a constant index into the kernel arguments. Always inlined: a
 // call that is not would take the argument block's address, and the compiler copies the whole block
 // (1.5 KB) to scratch per lane for that (the 4-wave backward launch did until r04).
-template <int NW, int AK, int BK, int TMX, int DI>
+// PLAIN (the ensemble launches, train_gemm_ens_kernel): the tile of the multi-launch layout only -- no
+// in-place Adam step, no dW_0 fold, no ticket, granule or wait of any kind is compiled in.
+template <int NW, int AK, int BK, int TMX, int DI, bool PLAIN = false>
 __device__ __forceinline__ void gemm_tile(const GemmLaunch& L, int tile, float (*red)[TT * TMX][TT + 1],
                                           float (*xs)[FOLD_K0MAX]) {
     const GemmDesc& D = L.d[DI];
@@ -462,7 +476,7 @@ __device__ __forceinline__ void gemm_tile(const GemmLaunch& L, int tile, float (
         if (m >= D.M || n >= D.N) continue;
         if (O.mode == EPI_ACT) pre[j] = n < O.bsplit ? O.b0[n] : O.b1[n - O.bsplit];
         else if (O.mode == EPI_MASK) pre[j] = O.mask[(int64_t)m * O.ldm + n];
-        else if (O.mode == EPI_GRAD && O.adam) {   // the in-place Adam step's operands (only this tile
+        else if (!PLAIN && O.mode == EPI_GRAD && O.adam) {   // the in-place Adam step's operands (only this tile
             const int64_t i = (int64_t)m * O.ldc + n;   // writes them; the weight is only read by others)
             ap[j] = O.aw.param[i];
             am[j] = O.aw.exp_avg[i];
@@ -478,7 +492,7 @@ __device__ __forceinline__ void gemm_tile(const GemmLaunch& L, int tile, float (
     // K loop (its latency then hides behind the products')
     constexpr int XPT = TM * FOLD_K0MAX / NT;
     float xv[XPT];
-    const bool xstage = O.mode == EPI_MASK && O.fold && O.fold_k0 <= FOLD_K0MAX;
+    const bool xstage = !PLAIN && O.mode == EPI_MASK && O.fold && O.fold_k0 <= FOLD_K0MAX;
     if (xstage) {
 #pragma unroll
         for (int j = 0; j < XPT; ++j) {
@@ -553,11 +567,13 @@ __device__ __forceinline__ void gemm_tile(const GemmLaunch& L, int tile, float (
     }
     __syncthreads();
     // every wave's K loop is done: this tile no longer reads the weight block (its loads were consumed)
-    if (O.mode == EPI_MASK && O.arrive_ticket && tid == 0)
-        __hip_atomic_fetch_add(O.arrive_ticket + n0 / TT, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if constexpr (!PLAIN) {
+        if (O.mode == EPI_MASK && O.arrive_ticket && tid == 0)
+            __hip_atomic_fetch_add(O.arrive_ticket + n0 / TT, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 
-    if (O.mode == EPI_GRAD && O.adam && O.wait_ticket)
-        wait_arrivals(O.wait_ticket + n0 / TT, O.wait_count, O.wait_status);
+        if (O.mode == EPI_GRAD && O.adam && O.wait_ticket)
+            wait_arrivals(O.wait_ticket + n0 / TT, O.wait_count, O.wait_status);
+    }
     TSTAMP(2);
 
     // the fused epilogue, EPT C elements per thread; each element sums the waves' partials in wave
@@ -584,11 +600,11 @@ __device__ __forceinline__ void gemm_tile(const GemmLaunch& L, int tile, float (
         }
         keep[j] = v;
         // (with the dW_0 fold nothing reads dH_0 after this launch: its tiles keep it in LDS only)
-        if (!(O.mode == EPI_MASK && O.fold)) {
+        if (PLAIN || !(O.mode == EPI_MASK && O.fold)) {
             float* dst = m < O.split ? O.c0 + (int64_t)m * O.ldc : O.c1 + (int64_t)(m - O.split) * O.ldc;
             dst[n] = v;
         }
-        if (O.mode == EPI_GRAD && O.adam) {
+        if (!PLAIN && O.mode == EPI_GRAD && O.adam) {
             const int64_t i = (int64_t)m * O.ldc + n;
             adam_element(ap[j], v, am[j], av[j], O.aw.step_size, O.aw.bc2_sqrt, L.hp, L.arith);
             O.aw.param[i] = ap[j];
@@ -602,7 +618,7 @@ __device__ __forceinline__ void gemm_tile(const GemmLaunch& L, int tile, float (
         const int m = m0 + tid;
         const float g = ordered_sum<false>(O.colsum_in + m, D.M, O.colsum_tiles);
         (m < O.split ? O.g0[m] : O.g1[m - O.split]) = g;
-        if (O.adam)
+        if (!PLAIN && O.adam)
             adam_element(O.ab.param[m], g, O.ab.exp_avg[m], O.ab.exp_avg_sq[m], O.ab.step_size, O.ab.bc2_sqrt, L.hp,
                          L.arith);
     }
@@ -619,15 +635,21 @@ __device__ __forceinline__ void gemm_tile(const GemmLaunch& L, int tile, float (
             float t = red[0][TT * sub][col];
             for (int r = 1; r < TT; ++r) t = t + red[0][TT * sub + r][col];
             const int64_t di = (int64_t)(tm * TMX + sub) * D.N + n0 + col;
-            if (O.fold)   // read by fold_sum (dW_1 tile (0, n0 / 32)) as a tagged granule
-                __hip_atomic_store(O.cs_gran + di, granule(t, *O.fold_serial), __ATOMIC_RELAXED,
-                                   __HIP_MEMORY_SCOPE_AGENT);
-            else
+            if constexpr (PLAIN) {
                 O.colsum_out[di] = t;
+            } else {
+                if (O.fold)   // read by fold_sum (dW_1 tile (0, n0 / 32)) as a tagged granule
+                    __hip_atomic_store(O.cs_gran + di, granule(t, *O.fold_serial), __ATOMIC_RELAXED,
+                                       __HIP_MEMORY_SCOPE_AGENT);
+                else
+                    O.colsum_out[di] = t;
+            }
         }
-        if (O.mode == EPI_MASK && O.fold) fold_dw0<NW, TMX, DI>(L, tm, n0, red, xs);
+        if constexpr (!PLAIN)
+            if (O.mode == EPI_MASK && O.fold) fold_dw0<NW, TMX, DI>(L, tm, n0, red, xs);
     }
-    if (O.mode == EPI_GRAD && O.fold_sum && tm == 0) fold_sum<NW>(L, n0);
+    if constexpr (!PLAIN)
+        if (O.mode == EPI_GRAD && O.fold_sum && tm == 0) fold_sum<NW>(L, n0);
     if (O.mode == EPI_LOSS) {   // the tile's loss: a butterfly per wave, then the waves in order
 #pragma unroll
         for (int o = 32; o >= 1; o >>= 1) {
@@ -832,6 +854,30 @@ __device__ __forceinline__ void fold_sum(const GemmLaunch& L, int n0) {
     }
 }
 
+// The loss workgroup: partials of the output-layer launch, summed in tile order into loss_out[0..2].
+__device__ __forceinline__ void loss_workgroup(const GemmLaunch& L) {
+    if (threadIdx.x < 2 && L.loss_out) {   // (loads 16 at a time in flight, sums in the same order)
+        float t = 0.0f, u = 0.0f;
+        for (int i0 = 0; i0 < L.loss_parts; i0 += 16) {
+            float ps[16], pr[16];
+#pragma unroll
+            for (int k = 0; k < 16; ++k) {
+                const bool in = i0 + k < L.loss_parts;
+                ps[k] = in ? L.loss_part[(i0 + k) * 2] : 0.0f;
+                pr[k] = in ? L.loss_part[(i0 + k) * 2 + 1] : 0.0f;
+            }
+#pragma unroll
+            for (int k = 0; k < 16; ++k)
+                if (i0 + k < L.loss_parts) {
+                    t = t + (threadIdx.x == 0 ? ps[k] : pr[k]);
+                    u = u + ps[k] + pr[k];
+                }
+        }
+        L.loss_out[1 + threadIdx.x] = t;
+        if (threadIdx.x == 0) L.loss_out[0] = u;
+    }
+}
+
 // NW waves per workgroup; A0/B0 (A1/B1): operand kinds of the launch's first (second) product, fixed
 // at compile time so each instantiation carries only its own load paths.
 template <int NW, int A0, int B0, int A1, int B1, int TMX>
@@ -873,27 +919,117 @@ __global__ __launch_bounds__(64 * NW) void train_gemm_kernel(const GemmLaunch L)
                          L.arith);
         return;
     }
-    // the loss workgroup: partials of the output-layer launch, summed in tile order
-    if (threadIdx.x < 2 && L.loss_out) {   // (loads 16 at a time in flight, sums in the same order)
-        float t = 0.0f, u = 0.0f;
-        for (int i0 = 0; i0 < L.loss_parts; i0 += 16) {
-            float ps[16], pr[16];
+    loss_workgroup(L);
+}
+
+// ================================================================================================
+// Ensemble training (mbrl_train_grads_ensemble / mbrl_train_epoch_ensemble): E members of one shape in
+// the launches of the multi-launch layout, the member on grid axis y. Workgroup (x, e) runs exactly
+// the tile x of member e's own launch -- the same loads, MFMA chains and sums in the same order -- so
+// member e's gradients and losses are a single-model call's bit for bit. The launch struct is member
+// 0's; the kernel moves every workspace pointer by e workspaces and the batch's rows by e orders, and
+// takes the member's parameter and gradient pointers (at most ENS_MODEL_PTRS per launch) from a table.
+// Nothing in these launches waits on another workgroup (gemm_tile's PLAIN form): every hand-off is a
+// kernel boundary on the stream, so any number of members' tiles may queue behind the CUs.
+constexpr int ENS_MODEL_PTRS = 6;
+
+struct EnsLaunch {
+    GemmLaunch g;          // member 0's launch
+    int64_t ws_stride;     // floats between two members' workspaces
+    int64_t idx_stride;    // rows between two members' orders
+    int loss_stride;       // floats between two members' loss_out
+    // forward / output launches: B.p0, B.p1, out.b0, out.b1; backward: d[0].B.p0, d[0].B.p1 (layer >= 1),
+    // then the weight-gradient product's out.c0, out.c1, out.g0, out.g1
+    const float* mp[MBRL_TRAIN_MAX_MEMBERS][ENS_MODEL_PTRS];
+};
+
+template <class T>
+__device__ __forceinline__ void ens_move(T*& p, int64_t by) {
+    if (p) p += by;
+}
+
+// Member e's launch from member 0's. KIND: 0 forward / output layer, 1 backward of a layer >= 1 (dH and
+// dW products), 2 backward of layer 0 (dW only).
+template <int KIND>
+__device__ __forceinline__ void ens_member(GemmLaunch& L, const EnsLaunch& P, int e) {
+    const int64_t by = (int64_t)e * P.ws_stride;
+    L.idx += (int64_t)e * P.idx_stride;
+    ens_move(L.xstore, by);
+    ens_move(L.loss_part, by);
+    ens_move(L.loss_out, (int64_t)e * P.loss_stride);
+    const float* m[ENS_MODEL_PTRS];
 #pragma unroll
-            for (int k = 0; k < 16; ++k) {
-                const bool in = i0 + k < L.loss_parts;
-                ps[k] = in ? L.loss_part[(i0 + k) * 2] : 0.0f;
-                pr[k] = in ? L.loss_part[(i0 + k) * 2 + 1] : 0.0f;
-            }
+    for (int i = 0; i < ENS_MODEL_PTRS; ++i) {   // (constant indices into the kernel arguments only)
+        m[i] = P.mp[0][i];
 #pragma unroll
-            for (int k = 0; k < 16; ++k)
-                if (i0 + k < L.loss_parts) {
-                    t = t + (threadIdx.x == 0 ? ps[k] : pr[k]);
-                    u = u + ps[k] + pr[k];
-                }
-        }
-        L.loss_out[1 + threadIdx.x] = t;
-        if (threadIdx.x == 0) L.loss_out[0] = u;
+        for (int k = 1; k < MBRL_TRAIN_MAX_MEMBERS; ++k)
+            if (e == k) m[i] = P.mp[k][i];
     }
+    GemmDesc& D0 = L.d[0];
+    if constexpr (KIND == 0) {
+        ens_move(D0.A.p0, by);
+        ens_move(D0.A.p1, by);
+        D0.B.p0 = m[0]; D0.B.p1 = m[1];
+        D0.out.b0 = m[2]; D0.out.b1 = m[3];
+        ens_move(D0.out.c0, by);
+        ens_move(D0.out.c1, by);
+        ens_move(D0.out.colsum_out, by);
+        ens_move(D0.out.loss_part, by);
+    } else {
+        constexpr int DG = KIND == 1 ? 1 : 0;     // the weight-gradient product
+        if constexpr (KIND == 1) {
+            ens_move(D0.A.p0, by);
+            ens_move(D0.A.p1, by);
+            D0.B.p0 = m[0]; D0.B.p1 = m[1];
+            ens_move(D0.out.c0, by);
+            ens_move(D0.out.c1, by);
+            ens_move(D0.out.mask, by);
+            ens_move(D0.out.colsum_out, by);
+        }
+        GemmDesc& G = L.d[DG];
+        ens_move(G.A.p0, by);
+        ens_move(G.A.p1, by);
+        ens_move(G.B.p0, by);
+        ens_move(G.B.p1, by);
+        G.out.c0 = const_cast<float*>(m[2]); G.out.c1 = const_cast<float*>(m[3]);
+        G.out.g0 = const_cast<float*>(m[4]); G.out.g1 = const_cast<float*>(m[5]);
+        ens_move(G.out.colsum_in, by);
+    }
+}
+
+template <int NW, int A0, int B0, int A1, int B1, int TMX>
+__global__ __launch_bounds__(64 * NW) void train_gemm_ens_kernel(const EnsLaunch P) {
+    __shared__ __attribute__((aligned(16))) float red[NW][TT * TMX][TT + 1];
+    constexpr int KIND = B0 == OP_DIRECT ? 0 : A0 == OP_DIRECT ? 1 : 2;
+    GemmLaunch L = P.g;
+    int e = blockIdx.y, b = blockIdx.x;
+#ifdef MBRL_ENS_XCD_MAJOR
+    // Measurement build (profiles/train_ensemble): the members XCD-major instead of member-major. Workgroup
+    // w = y * gridDim.x + x runs on XCD w % 8 (round-robin dispatch) as that XCD's (w / 8)-th; numbering the
+    // workgroups XCD by XCD gives member e a contiguous run of them, so a member's tiles share one or two
+    // XCDs' L2 and all members run side by side. A bijection when the grid is a multiple of 8; the same bits.
+    {
+        const unsigned gx = gridDim.x, total = gx * gridDim.y, w = blockIdx.y * gx + blockIdx.x;
+        if ((total & 7u) == 0) {
+            const unsigned v = (w & 7u) * (total >> 3) + (w >> 3);
+            e = (int)(v / gx);
+            b = (int)(v - (v / gx) * gx);
+        }
+    }
+#endif
+    ens_member<KIND>(L, P, e);
+    TSTAMP(0);   // (member 0's workgroups only)
+    if (b < L.d[0].tiles) {
+        gemm_tile<NW, A0, B0, TMX, 0, true>(L, b, red, nullptr);
+        return;
+    }
+    if constexpr (A1 >= 0) {
+        if (L.nd > 1 && b - L.d[0].tiles < L.d[1].tiles) {
+            gemm_tile<NW, A1, B1, TMX, 1, true>(L, b - L.d[0].tiles, red, nullptr);
+            return;
+        }
+    }
+    loss_workgroup(L);
 }
 
 // ================================================================================================
@@ -1630,6 +1766,53 @@ static hipError_t launch_gemm(GemmLaunch& L, bool loss_wg, hipStream_t stream) {
     return hipGetLastError();
 }
 
+// The same launch for every member of an ensemble (train_gemm_ens_kernel), or launch_gemm without one.
+// `layer`: the Linear whose parameters (forward) or gradients (backward) the launch touches.
+template <int A0, int B0, int A1 = -1, int B1 = -1, int TMX = 1>
+static hipError_t launch_gemm_any(GemmLaunch& G, bool loss_wg, hipStream_t stream, const TrainEnsemble* ens,
+                                  const TrainShape& t, int layer) {
+    if (!ens) return launch_gemm<A0, B0, A1, B1, TMX>(G, loss_wg, stream);
+    if (ens->E < 1 || ens->E > MBRL_TRAIN_MAX_MEMBERS || G.adam_count != 0) return hipErrorInvalidValue;
+    constexpr int KIND = B0 == OP_DIRECT ? 0 : A0 == OP_DIRECT ? 1 : 2;
+    EnsLaunch P{};
+    const bool heads = layer == t.L && t.reward;   // the output layer's second storage block: the reward head
+    bool vec = true;
+    for (int e = 0; e < ens->E; ++e) {
+        const mbrl_train_model& m = ens->members[e];
+        const int l2 = heads ? t.L + 1 : layer;
+        if (KIND == 0) {
+            P.mp[e][0] = m.weight[layer]; P.mp[e][1] = m.weight[l2];
+            P.mp[e][2] = m.bias[layer]; P.mp[e][3] = m.bias[l2];
+            vec = vec && ((reinterpret_cast<uintptr_t>(m.weight[layer]) | reinterpret_cast<uintptr_t>(m.weight[l2])) & 15) == 0;
+        } else {
+            P.mp[e][0] = m.weight[layer]; P.mp[e][1] = m.weight[l2];
+            P.mp[e][2] = m.weight_grad[layer]; P.mp[e][3] = m.weight_grad[l2];
+            P.mp[e][4] = m.bias_grad[layer]; P.mp[e][5] = m.bias_grad[l2];
+        }
+    }
+    if (KIND == 0 && !vec) G.d[0].B.vec = 0;   // one load path for all members (the values are the same)
+    if (!loss_wg) G.loss_out = nullptr;
+    G.xcd = 0;
+    ++G.slot;
+    P.g = G;
+    P.ws_stride = ens->ws_stride; P.idx_stride = ens->idx_stride; P.loss_stride = ens->loss_stride;
+    int blocks = loss_wg ? 1 : 0;
+    for (int i = 0; i < G.nd; ++i) blocks += G.d[i].tiles;
+    const int nw = launch_waves(G);
+    const dim3 grid(blocks, ens->E);
+    if constexpr (TMX == 2) {
+        if (nw != 16) return hipErrorInvalidValue;
+        hipLaunchKernelGGL((train_gemm_ens_kernel<16, A0, B0, A1, B1, TMX>), grid, dim3(64 * 16), 0, stream, P);
+    } else if (nw == 16) {
+        hipLaunchKernelGGL((train_gemm_ens_kernel<16, A0, B0, A1, B1, TMX>), grid, dim3(64 * 16), 0, stream, P);
+    } else if (nw == 8) {
+        hipLaunchKernelGGL((train_gemm_ens_kernel<8, A0, B0, A1, B1, TMX>), grid, dim3(64 * 8), 0, stream, P);
+    } else {
+        hipLaunchKernelGGL((train_gemm_ens_kernel<4, A0, B0, A1, B1, TMX>), grid, dim3(64 * 4), 0, stream, P);
+    }
+    return hipGetLastError();
+}
+
 // Workspace (floats, each piece 256-byte aligned): hidden activations H_0..H_{L-1} [R][W], two
 // backward buffers dH [R][W], dY [R][J], loss partials, the gathered input [R][s + a], and the
 // per-row-tile column sums of dY [tiles][J] and of the two dH [tiles][W].
@@ -1730,7 +1913,8 @@ bool train_fused_applies(const TrainShape& t, int batch) {
 hipError_t launch_train_grads(const TrainShape& t, const TrainTensors& w, const int64_t* idx, int batch,
                               float* loss_out, float* ws, hipStream_t stream, const mbrl_adam_tensor* adam,
                               const mbrl_adam_hparams* hp, int arith, const mbrl_adam_tensor* prior, int prior_n,
-                              mbrl_adam_tensor* pending, int* pending_n, const TrainGather* gather) {
+                              mbrl_adam_tensor* pending, int* pending_n, const TrainGather* gather,
+                              const TrainEnsemble* ens) {
     const int R = batch * t.H, W = t.W, K0 = t.s + t.a, J = t.s + (t.reward ? 1 : 0), L = t.L;
     const int tiles_r = (R + TT - 1) / TT;
     const int fold_nw = fold_waves(t, R);
@@ -1738,6 +1922,8 @@ hipError_t launch_train_grads(const TrainShape& t, const TrainTensors& w, const 
     if (pending_n) *pending_n = 0;
     if ((prior_n > 0 && !prior) || prior_n > ADAM_FUSED_MAX || (adam && fold_nw && (!pending || !pending_n)))
         return hipErrorInvalidValue;
+    // an ensemble runs the multi-launch layout only: gradients, no fold, no Adam step in the launches
+    if (ens && (fused || fold_nw || adam || prior_n > 0)) return hipErrorInvalidValue;
     TrainWs B = train_ws(t, batch, ws);
     // the fused step's gather slot: the caller alternates them when F gathers the next batch
     float *xnext = B.xbuf2, *tnext = B.tgt2;
@@ -1842,7 +2028,8 @@ hipError_t launch_train_grads(const TrainShape& t, const TrainTensors& w, const 
             for (int i = 0; i < prior_n; ++i) G.adam_t[G.adam_count++] = prior[i];
         }
         G.xcd = xcd_opt;
-        e = l == 0 ? launch_gemm<OP_GATHER, OP_DIRECT>(G, false, stream) : launch_gemm<OP_DIRECT, OP_DIRECT>(G, false, stream);
+        e = l == 0 ? launch_gemm_any<OP_GATHER, OP_DIRECT>(G, false, stream, ens, t, l)
+                   : launch_gemm_any<OP_DIRECT, OP_DIRECT>(G, false, stream, ens, t, l);
         G.zero_words = nullptr;
         G.serial = nullptr;
         G.adam_count = 0;
@@ -1863,7 +2050,7 @@ hipError_t launch_train_grads(const TrainShape& t, const TrainTensors& w, const 
         finish(D, R, J, W);
         G.nd = 1;
         G.xcd = xcd_opt;
-        if ((e = launch_gemm<OP_DIRECT, OP_DIRECT>(G, false, stream)) != hipSuccess) return e;
+        if ((e = launch_gemm_any<OP_DIRECT, OP_DIRECT>(G, false, stream, ens, t, L)) != hipSuccess) return e;
     }
     const int loss_parts = fused ? tiles_r : G.d[0].tiles;
     // backward: layer l = L (output) .. 0; launch l: dH_{l-1} (l >= 1) and dW_l, db_l. With the fold
@@ -1944,9 +2131,9 @@ hipError_t launch_train_grads(const TrainShape& t, const TrainTensors& w, const 
         G.loss_part = B.loss_part; G.loss_parts = loss_parts; G.loss_out = loss_out;
         const bool loss_wg = l == l_end && loss_out != nullptr;
         G.xcd = xcd_opt;
-        e = l == 0    ? launch_gemm<OP_TRANS, OP_TRANS>(G, loss_wg, stream)
-            : tmx == 2 ? launch_gemm<OP_DIRECT, OP_TRANS, OP_TRANS, OP_TRANS, 2>(G, loss_wg, stream)
-                       : launch_gemm<OP_DIRECT, OP_TRANS, OP_TRANS, OP_TRANS>(G, loss_wg, stream);
+        e = l == 0    ? launch_gemm_any<OP_TRANS, OP_TRANS>(G, loss_wg, stream, ens, t, l)
+            : tmx == 2 ? launch_gemm_any<OP_DIRECT, OP_TRANS, OP_TRANS, OP_TRANS, 2>(G, loss_wg, stream, ens, t, l)
+                       : launch_gemm_any<OP_DIRECT, OP_TRANS, OP_TRANS, OP_TRANS>(G, loss_wg, stream, ens, t, l);
         if (e != hipSuccess) return e;
     }
     if (adam && fold_nw && !fused) {   // layer 1's step (launch 0's passenger before the fold): the next forward launch's
@@ -2107,6 +2294,127 @@ int mbrl_train_epoch(const mbrl_train_model* model, const mbrl_train_data* data,
     if (carry_n > 0)
         if (int rc = hip_check(launch_adam_step(carry[batches & 1], carry_n, *hparams, ar, st), "train_epoch adam tail"))
             return rc;
+    return MBRL_OK;
+}
+
+// ---- ensembles: E members in shared launches (train_gemm_ens_kernel)
+
+// The members' common shape in the layout the ensemble launches run: the multi-launch one, the layer-0
+// weight gradient in its own launch (the only layout without a wait between workgroups).
+static int ensemble_shape(const char* what, const mbrl_train_model* members, int32_t E, TrainShape* t) {
+    if (!members) return fail(MBRL_EINVAL, "%s: NULL members", what);
+    if (E < 1) return fail(MBRL_EINVAL, "%s: E = %d members", what, E);
+    if (E > MBRL_TRAIN_MAX_MEMBERS)
+        return fail(MBRL_EUNSUPPORTED, "%s: E = %d members exceeds MBRL_TRAIN_MAX_MEMBERS = %d", what, E,
+                    MBRL_TRAIN_MAX_MEMBERS);
+    if (int rc = train_shape(&members[0], t)) return rc;
+    for (int e = 1; e < E; ++e) {
+        const mbrl_train_model &a = members[0], &b = members[e];
+        if (a.state_dim != b.state_dim || a.action_dim != b.action_dim || a.hidden != b.hidden ||
+            a.n_hidden != b.n_hidden || a.reward_head != b.reward_head || a.horizon != b.horizon)
+            return fail(MBRL_EINVAL, "%s: member %d's shape differs from member 0's", what, e);
+    }
+    t->fold = 0;
+    t->split = 1;
+    t->xcd = 0;
+    return MBRL_OK;
+}
+
+// NULL layers, and no parameter or gradient buffer bound twice (two members stepping one buffer would race)
+static int ensemble_members(const char* what, const mbrl_train_model* members, int32_t E, const TrainShape& t) {
+    const int layers = t.L + 1 + t.reward;
+    std::vector<const void*> seen;
+    for (int e = 0; e < E; ++e)
+        for (int l = 0; l < layers; ++l) {
+            const mbrl_train_model& m = members[e];
+            if (!m.weight[l] || !m.bias[l] || !m.weight_grad[l] || !m.bias_grad[l])
+                return fail(MBRL_EINVAL, "%s: member %d, layer %d: NULL weight, bias or gradient", what, e, l);
+            seen.insert(seen.end(), {m.weight[l], m.bias[l], m.weight_grad[l], m.bias_grad[l]});
+        }
+    std::sort(seen.begin(), seen.end());
+    if (std::adjacent_find(seen.begin(), seen.end()) != seen.end())
+        return fail(MBRL_EINVAL, "%s: a parameter or gradient pointer is bound twice", what);
+    return MBRL_OK;
+}
+
+static bool ensemble_data_ok(const mbrl_train_data* data, const TrainShape& t) {
+    return data && data->states && data->next_states && (t.a == 0 || data->actions) && (!t.reward || data->rewards);
+}
+
+size_t mbrl_train_ensemble_workspace_bytes(const mbrl_train_model* members, int32_t E, int32_t batch) {
+    TrainShape t;
+    if (batch < 1 || ensemble_shape("train_ensemble_workspace_bytes", members, E, &t) != MBRL_OK) return 0;
+    return (size_t)E * train_ws_floats(t, batch) * sizeof(float);
+}
+
+int mbrl_train_grads_ensemble(const mbrl_train_model* members, int32_t E, const mbrl_train_data* data,
+                              const int64_t* batch_idx, int32_t batch, float* loss_out, void* workspace,
+                              size_t ws_bytes, mbrl_stream_t stream) {
+    const char* what = "train_grads_ensemble";
+    TrainShape t;
+    if (int rc = ensemble_shape(what, members, E, &t)) return rc;
+    if (!ensemble_data_ok(data, t) || !batch_idx || !workspace) return fail(MBRL_EINVAL, "%s: NULL argument", what);
+    if (batch < 1 || (int64_t)batch > data->transitions)
+        return fail(MBRL_EINVAL, "%s: batch %d outside [1, %lld]", what, batch, (long long)data->transitions);
+    if (int rc = ensemble_members(what, members, E, t)) return rc;
+    const size_t stride = train_ws_floats(t, batch), need = (size_t)E * stride * sizeof(float);
+    if (ws_bytes < need) return fail(MBRL_EWORKSPACE, "%s: workspace %zu < %zu bytes", what, ws_bytes, need);
+    const mbrl_train_model& m0 = members[0];
+    TrainTensors w{m0.weight, m0.bias, m0.weight_grad, m0.bias_grad,
+                   data->states, data->actions, data->next_states, data->rewards};
+    const TrainEnsemble ens{members, E, (int64_t)stride, batch, 3};
+    return hip_check(launch_train_grads(t, w, batch_idx, batch, loss_out, static_cast<float*>(workspace),
+                                        reinterpret_cast<hipStream_t>(stream), nullptr, nullptr, 0, nullptr, 0, nullptr,
+                                        nullptr, nullptr, &ens), what);
+}
+
+int mbrl_train_epoch_ensemble(const mbrl_train_model* members, int32_t E, const mbrl_train_data* data,
+                              const int64_t* orders, int64_t rows, int32_t batch_size, const mbrl_adam_tensor* tensors,
+                              int32_t count, const mbrl_adam_hparams* hparams, const float* step_sizes,
+                              const float* bc2_sqrt, float* losses, void* workspace, size_t ws_bytes,
+                              mbrl_stream_t stream) {
+    const char* what = "train_epoch_ensemble";
+    TrainShape t;
+    if (int rc = ensemble_shape(what, members, E, &t)) return rc;
+    if (!ensemble_data_ok(data, t) || !orders || !workspace || !tensors || count < 1 || !hparams || !step_sizes ||
+        !bc2_sqrt)
+        return fail(MBRL_EINVAL, "%s: NULL argument", what);
+    if (batch_size < 1 || rows < 1 || rows > data->transitions)
+        return fail(MBRL_EINVAL, "%s: rows %lld / batch %d outside [1, %lld]", what, (long long)rows, batch_size,
+                    (long long)data->transitions);
+    if (int rc = ensemble_members(what, members, E, t)) return rc;
+    const int total = E * count;
+    for (int i = 0; i < total; ++i)
+        if (tensors[i].numel < 0 || (tensors[i].numel > 0 && (!tensors[i].param || !tensors[i].grad ||
+                                                              !tensors[i].exp_avg || !tensors[i].exp_avg_sq)))
+            return fail(MBRL_EINVAL, "%s: member %d, Adam tensor %d: NULL pointer or negative numel", what, i / count,
+                        i % count);
+    const int bs = (int)std::min<int64_t>(batch_size, rows);
+    const size_t stride = train_ws_floats(t, bs), need = (size_t)E * stride * sizeof(float);
+    if (ws_bytes < need) return fail(MBRL_EWORKSPACE, "%s: workspace %zu < %zu bytes", what, ws_bytes, need);
+    const mbrl_train_model& m0 = members[0];
+    TrainTensors w{m0.weight, m0.bias, m0.weight_grad, m0.bias_grad,
+                   data->states, data->actions, data->next_states, data->rewards};
+    const int arith = opt(MBRL_OPT_ADAM_ARITH), ar = arith ? arith - 1 : ADAM_ARITH_TORCH;
+    const hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const TrainEnsemble ens{members, E, (int64_t)stride, rows, 3};
+    std::vector<mbrl_adam_tensor> table(tensors, tensors + total);
+    const int64_t batches = (rows + batch_size - 1) / batch_size;
+    for (int64_t b = 0; b < batches; ++b) {
+        const int n = (int)std::min<int64_t>(batch_size, rows - b * batch_size);
+        if (int rc = hip_check(launch_train_grads(t, w, orders + b * batch_size, n,
+                                                  losses ? losses + 3 * (int64_t)E * b : nullptr,
+                                                  static_cast<float*>(workspace), st, nullptr, nullptr, 0, nullptr, 0,
+                                                  nullptr, nullptr, nullptr, &ens), what))
+            return rc;
+        for (int i = 0; i < total; ++i) {
+            table[i].step_size = step_sizes[b * total + i];
+            table[i].bc2_sqrt = bc2_sqrt[b * total + i];
+        }
+        // every member's step in one launch (ADAM_ENS_TENSORS per launch: E x count beyond that takes more)
+        if (int rc = hip_check(launch_adam_step_cap<ADAM_ENS_TENSORS>(table.data(), total, *hparams, ar, st), what))
+            return rc;
+    }
     return MBRL_OK;
 }
 

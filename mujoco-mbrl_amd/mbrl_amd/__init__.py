@@ -8,7 +8,8 @@ from . import agents, data, env, env_wrappers, gd, models, parallel, planners  #
 from .agents import MPCPolicy  # noqa: F401
 from .env_wrappers import EnvWrapper  # noqa: F401
 from .models import (CoshLoss, CostModel, DynamicsModel, EnsembleModel, LinearModel, Model,  # noqa: F401
-                     ModelWithReward, QuadraticCost, SmoothAbsLoss, compose, goal_state_cost, state_action_cost)
+                     ModelWithReward, QuadraticCost, SmoothAbsLoss, compose, goal_state_cost, member_order,
+                     state_action_cost)
 from .planners import (BatchedMPPIPlanner, CEMPlanner, GradientDescentPlanner, ModelPlanner, MPPIPlanner,  # noqa: F401
                        RandomShootingPlanner, RecedingHorizonCEMPlanner, cem_plan_batch_rh, cem_shift_carry,
                        mppi_plan_batch)

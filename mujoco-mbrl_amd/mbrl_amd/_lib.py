@@ -75,6 +75,7 @@ EXPORTED = (
     "mbrl_mppi_update_elite", "mbrl_mppi_update_elite_batch", "mbrl_mppi_elite_workspace_bytes",
     "mbrl_mppi_plan_elite", "mbrl_mppi_plan_elite_batch",
     "mbrl_gd_grad",
+    "mbrl_train_ensemble_workspace_bytes", "mbrl_train_grads_ensemble", "mbrl_train_epoch_ensemble",
 )
 
 
@@ -137,6 +138,7 @@ class AdamHparams(ctypes.Structure):
 
 
 TRAIN_MAX_LAYERS = 10
+TRAIN_MAX_MEMBERS = 8      # MBRL_TRAIN_MAX_MEMBERS: members per mbrl_train_*_ensemble call
 
 
 class TrainModel(ctypes.Structure):
@@ -210,6 +212,12 @@ def load():
         "mbrl_train_grads": (c_int32, [POINTER(TrainModel), POINTER(TrainData), P, c_int32, P, P, c_size_t, P]),
         "mbrl_train_epoch": (c_int32, [POINTER(TrainModel), POINTER(TrainData), P, c_int64, c_int32, POINTER(AdamTensor),
                                        c_int32, POINTER(AdamHparams), P, P, P, P, c_size_t, P]),
+        "mbrl_train_ensemble_workspace_bytes": (c_size_t, [POINTER(TrainModel), c_int32, c_int32]),
+        "mbrl_train_grads_ensemble": (c_int32, [POINTER(TrainModel), c_int32, POINTER(TrainData), P, c_int32, P, P,
+                                                c_size_t, P]),
+        "mbrl_train_epoch_ensemble": (c_int32, [POINTER(TrainModel), c_int32, POINTER(TrainData), P, c_int64, c_int32,
+                                                POINTER(AdamTensor), c_int32, POINTER(AdamHparams), P, P, P, P,
+                                                c_size_t, P]),
         "mbrl_cem_plan": (c_int32, [POINTER(MlpShape), P, POINTER(Norm), POINTER(Cost), P, POINTER(CemParams),
                                     P, P, P, P, P, P, P, P, P, c_size_t, P]),
         "mbrl_mppi_update": (c_int32, [P, c_int32, c_int32, P, POINTER(Sampler), c_int32, c_int32, c_float, c_float,
@@ -268,6 +276,22 @@ def load():
         raise ImportError(f"mbrl_amd ABI version mismatch: {lib.mbrl_abi_version()} != {ABI_VERSION}")
     _lib = lib
     return lib
+
+
+def load_other(path):
+    """Another build of the extension (an A/B partner: a measurement build, a library built from an
+    earlier commit), typed like the loaded one for every entry it exports; entries it lacks stay absent.
+    models.native_library(lib) makes the training calls go through it."""
+    lib, other = load(), ctypes.CDLL(os.path.abspath(path))
+    for name in EXPORTED:
+        try:
+            fn = getattr(other, name)
+        except AttributeError:
+            continue
+        fn.restype, fn.argtypes = getattr(lib, name).restype, getattr(lib, name).argtypes
+    if other.mbrl_abi_version() != ABI_VERSION:
+        raise ImportError(f"{path}: ABI version {other.mbrl_abi_version()} != {ABI_VERSION}")
+    return other
 
 
 def source_digest():
@@ -413,5 +437,5 @@ def require_gpu(t):
 __all__ = ["load", "check", "ptr", "stream_handle", "MlpShape", "Norm", "Cost", "Sampler", "CemParams", "CemRhParams", "MppiParams",
            "EXPORTED", "MBRL_NAN_LAST", "MBRL_NAN_FIRST", "MBRL_COST_GOAL_STATE", "MBRL_COST_MODEL_REWARD",
            "ABI_VERSION", "c_int64", "MBRL_PRECISION_F32", "MBRL_PRECISION_F16X3", "MBRL_PRECISION_F16X6",
-           "precision_code", "option", "OPTIONS", "AdamTensor", "AdamHparams",
-           "TrainModel", "TrainData", "TRAIN_MAX_LAYERS", "HostStaging"]
+           "precision_code", "load_other", "option", "OPTIONS", "AdamTensor", "AdamHparams",
+           "TrainModel", "TrainData", "TRAIN_MAX_LAYERS", "TRAIN_MAX_MEMBERS", "HostStaging"]

@@ -6,6 +6,7 @@ autograd off it runs the one-step batch through the same HIP rollout kernel the 
 (H = 1, per-row start states); otherwise (training, CPU tensors) it is plain PyTorch, exactly the
 reference's arithmetic.
 """
+import contextlib
 import ctypes
 import functools
 import threading
@@ -99,6 +100,29 @@ NATIVE_TRAINING = True
 
 # model -> (binding key, _NativeGrads) of its last native train_model call (_NativeGrads.cached)
 _NATIVE_CACHE = weakref.WeakKeyDictionary()
+# ensemble -> (binding key, _NativeEnsemble) of its last native train_members call
+_NATIVE_ENS_CACHE = weakref.WeakKeyDictionary()
+
+_LIB_OVERRIDE = None
+
+
+@contextlib.contextmanager
+def native_library(lib):
+    """Within the block, train_model / train_members bind their native training calls to `lib`
+    (_lib.load_other: another build of the extension with the same structs) instead of the loaded
+    library -- the A/B hook of tools/train_ensemble_bench.py. Objects cached for one library are not
+    reused for another."""
+    global _LIB_OVERRIDE
+    saved, _LIB_OVERRIDE = _LIB_OVERRIDE, lib
+    try:
+        yield
+    finally:
+        _LIB_OVERRIDE = saved
+
+
+def _native_lib():
+    from . import _lib
+    return _LIB_OVERRIDE if _LIB_OVERRIDE is not None else _lib.load()
 
 
 class _NativeGrads:
@@ -109,7 +133,7 @@ class _NativeGrads:
 
     def __init__(self, model, ins, outs, horizon, batch_size, reward):
         from . import _lib
-        self.lib = _lib.load()
+        self.lib = _native_lib()
         dev = _device_of(model)
         lins = model.linears()
         self.params = [t for lin in lins for t in (lin.weight, lin.bias)]
@@ -145,7 +169,7 @@ class _NativeGrads:
         workspace (host time the GPU idles through at the start of every call,
         tools/train_startup.py). Rebuilt when a non-contiguous input would need a fresh contiguous
         copy."""
-        key = (str(_device_of(model)), int(horizon), int(batch_size), bool(reward),
+        key = (str(_device_of(model)), int(horizon), int(batch_size), bool(reward), id(_LIB_OVERRIDE),
                tuple(t.data_ptr() for lin in model.linears() for t in (lin.weight, lin.bias)),
                tuple((x.data_ptr(), tuple(x.shape), x.is_contiguous()) for x in (*ins, *outs)))
         hit = _NATIVE_CACHE.get(model)
@@ -247,21 +271,27 @@ class _NativeGrads:
         return loss[0], [loss[1], loss[2]]
 
 
-def _train_loop(model, dataset, optimizer, batch_size, num_epochs, step_loss, writer, tags, criterion=None):
+def _train_loop(model, dataset, optimizer, batch_size, num_epochs, step_loss, writer, tags, criterion=None,
+                order_fn=None, iter0=0):
     """models.py:53-93 / 165-217 on the model's device: per batch, the loss summed over the horizon
     steps, zero_grad, backward, step -- the reference's order of operations. Batches are gathered
     from device-resident transitions (TransitionsDataset.stacked) instead of per-sample collation;
     on a GPU the full-size batches replay one captured graph (_GraphStep), and a plain Adam steps
-    through mbrl_adam_step (optim.AdamStep: one launch, torch's arithmetic bit for bit)."""
+    through mbrl_adam_step (optim.AdamStep: one launch, torch's arithmetic bit for bit).
+    order_fn (EnsembleModel.train_members): epoch k visits the rows order_fn(k) instead of a shuffle
+    drawn from the global RNG, batch by batch (no whole-epoch device call: its order ring draws), and
+    the writer's batch index goes on from iter0 (the batches a shared-launch part of the call ran)."""
     dev = _device_of(model)
     if dev.type == "cuda":
         with torch.cuda.device(dev):       # launches and workspaces on the model's GPU
             return _train_loop_on(dev, model, dataset, optimizer, batch_size, num_epochs, step_loss, writer, tags,
-                                  criterion)
-    return _train_loop_on(dev, model, dataset, optimizer, batch_size, num_epochs, step_loss, writer, tags, criterion)
+                                  criterion, order_fn, iter0)
+    return _train_loop_on(dev, model, dataset, optimizer, batch_size, num_epochs, step_loss, writer, tags, criterion,
+                          order_fn, iter0)
 
 
-def _train_loop_on(dev, model, dataset, optimizer, batch_size, num_epochs, step_loss, writer, tags, criterion):
+def _train_loop_on(dev, model, dataset, optimizer, batch_size, num_epochs, step_loss, writer, tags, criterion,
+                   order_fn=None, iter0=0):
     if dataset.num_transitions() == 0:    # the reference's DataLoader yields no batch
         model.train_iterations += 1
         return
@@ -283,8 +313,8 @@ def _train_loop_on(dev, model, dataset, optimizer, batch_size, num_epochs, step_
     # parameters the optimizer steps that the native gradient call does not overwrite each batch
     own = set() if native is None else {id(p) for p in native.params}
     extra = [p for g in optimizer.param_groups for p in g["params"] if id(p) not in own] if native is not None else []
-    num_iters = 0
-    whole = native is not None and fast is not None
+    num_iters = iter0
+    whole = native is not None and fast is not None and order_fn is None
     if whole and num_epochs > 0:
         # The device path issues the epochs back to back with no host round trip between them (a
         # per-epoch copy of the row order from pageable memory waited for the previous epoch to drain).
@@ -303,7 +333,7 @@ def _train_loop_on(dev, model, dataset, optimizer, batch_size, num_epochs, step_
             if ep >= 1:
                 ring.copied[ep % ring.K].wait(main)   # epoch ep's order has landed
         else:
-            host = _epoch_order(dataset)
+            host = _epoch_order(dataset) if order_fn is None else order_fn(ep)
             order = torch.from_numpy(host).to(dev)
         losses = native.epoch(order, batch_size, fast) if whole else None
         if whole and ep + 1 < num_epochs:
@@ -388,11 +418,15 @@ class _OrderRing:
                 self.copied[r].record(self.side)
             self.copied[r].synchronize()
 
-    def draw(self, e):
-        """Epoch e's order (models._epoch_order's draws: NumPy's shuffle of arange(n), in place)."""
+    def draw(self, e, fill=None):
+        """Epoch e's order (models._epoch_order's draws: NumPy's shuffle of arange(n), in place), or
+        what fill(row) writes into the pinned row (train_members: the members' orders, end to end)."""
         r = e % self.K
         self.copied[r].synchronize()                # the copy that last read this pinned row is done
         row = self.host[r, :self.n]
+        if fill is not None:
+            fill(row)
+            return
         np.copyto(row, self.arange[:self.n])
         np.random.shuffle(row)                      # (in place on the view: the draws of a fresh arange(n))
 
@@ -451,7 +485,9 @@ class DynamicsModel(nn.Module):
         self.train_iterations = 0
 
     def train_model(self, dataset, optimizer, batch_size=512, num_epochs=50, criterion=None, writer=None):
-        """models.py:53-93 (state_only / obs_only data modes: inputs (s, a), outputs (r, s'))."""
+        """models.py:53-93 (state_only / obs_only data modes: inputs (s, a), outputs (r, s')). On an
+        EnsembleModel this fits the member mean; EnsembleModel.train_members trains each member on its
+        own bootstrap order."""
         criterion = criterion or torch.nn.MSELoss()
 
         def step_loss(inp, out):
@@ -561,6 +597,212 @@ class EnsembleModel(DynamicsModel):
 
     def _forward(self, x):
         return torch.stack([m._forward(x) for m in self.members]).mean(0)
+
+    def train_members(self, dataset, optimizers, batch_size=512, num_epochs=50, bootstrap=True, seed=0,
+                      criterion=None, writer=None):
+        """Train every member on its own view of `dataset`: the bootstrap training a PETS-style
+        ensemble's diversity comes from (train_model, inherited, fits the member MEAN with one optimizer
+        and one data order, so every member sees the same signal).
+
+        optimizers: a list of E optimizers, one per member over that member's parameters, or a factory
+        member -> optimizer. Member e's epoch k visits the rows member_order(seed, e, k, n, bootstrap):
+        with bootstrap=True n draws WITH replacement, a fresh resample every epoch (each epoch then sees
+        ~63% of the rows, and over the epochs every member sees all of them in its own proportions --
+        the per-epoch form of the bootstrap; a resample fixed per member would be k-independent);
+        with bootstrap=False a permutation. The draws come from np.random.default_rng([seed, e, k]): the
+        global NumPy RNG is not touched. Each member minimises train_model's loss for a Model (the
+        criterion of its predicted next state, summed over the horizon steps).
+
+        On a GPU, members the native gradient supports (train_model's test) with plain Adam optimizers
+        of equal betas, eps and weight decay train together: one mbrl_train_epoch_ensemble call per
+        epoch, the members on a grid axis of shared launches, each member's result bit-identical to that
+        member trained alone by mbrl_train_epoch on its order. Anything else -- CPU, `noise` on a
+        member, another optimizer or criterion -- trains the members one after another on the same
+        orders -- as do more than 8 members (MBRL_TRAIN_MAX_MEMBERS) or a member listed twice. Writer
+        tags: loss/state/member{e}/{iteration}. train_iterations counts one per call on the ensemble and
+        on each member. Returns the number of epochs that ran in the shared launches (0: member by
+        member)."""
+        members = list(self.members)
+        opts = [optimizers(m) for m in members] if callable(optimizers) else list(optimizers)
+        if len(opts) != len(members):
+            raise ValueError(f"train_members needs one optimizer per member ({len(members)}), got {len(opts)}")
+        criterion = criterion or torch.nn.MSELoss()
+        n = dataset.num_transitions()
+        first = 0
+        if n > 0 and num_epochs > 0 and _device_of(self).type == "cuda":
+            with torch.cuda.device(_device_of(self)):
+                first = _train_members_native(self, members, opts, dataset, batch_size, num_epochs, bootstrap, seed,
+                                              criterion, writer)
+        if first < num_epochs or n == 0 or num_epochs <= 0:
+            for e, (m, opt) in enumerate(zip(members, opts)):
+                def step_loss(inp, out, m=m):
+                    (states, actions), (_, next_states) = inp, out
+                    return [criterion(m.forward(states, actions, normalize_action=None, normalize_state=None,
+                                                unnormalize_state=None), next_states)]
+                if first > 0:                 # (the native epochs counted this call already)
+                    m.train_iterations -= 1
+                _train_loop(m, dataset, opt, batch_size, num_epochs - first, step_loss, writer,
+                            [f"loss/state/member{e}/{{}}"], criterion,
+                            order_fn=lambda k, e=e: member_order(seed, e, first + k, n, bootstrap),
+                            iter0=first * ((n + batch_size - 1) // batch_size))
+        self.train_iterations += 1
+        return first
+
+
+def member_order(seed, e, k, n, bootstrap=True):
+    """The rows member e visits in epoch k of EnsembleModel.train_members (int64 [n]): n draws with
+    replacement (bootstrap) or a permutation, from np.random.default_rng([seed, e, k])."""
+    rng = np.random.default_rng([int(seed), int(e), int(k)])
+    if bootstrap:
+        return rng.integers(0, n, size=n, dtype=np.int64)
+    return rng.permutation(n).astype(np.int64, copy=False)
+
+
+class _NativeEnsemble:
+    """mbrl_train_epoch_ensemble for E supported members: per member the gradient buffers and
+    mbrl_train_model of _NativeGrads, one dataset, one workspace of E member slices."""
+
+    def __init__(self, members, ins, outs, horizon, batch_size):
+        from . import _lib
+        self._lib, self.lib = _lib, _native_lib()
+        self.dev = _device_of(members[0])
+        self.E = len(members)
+        self.params, self.grads = [], []
+        self.models = (_lib.TrainModel * self.E)()
+        for e, model in enumerate(members):
+            lins = model.linears()
+            params = [t for lin in lins for t in (lin.weight, lin.bias)]
+            grads = [torch.zeros_like(t) for t in params]
+            m = self.models[e]
+            m.state_dim, m.action_dim, m.hidden = model.state_dim, model.action_dim, model.hidden_units
+            m.n_hidden, m.reward_head, m.horizon = model.n_hidden, 0, int(horizon)
+            for i, lin in enumerate(lins):
+                m.weight[i], m.bias[i] = lin.weight.data_ptr(), lin.bias.data_ptr()
+                m.weight_grad[i], m.bias_grad[i] = grads[2 * i].data_ptr(), grads[2 * i + 1].data_ptr()
+            self.params.append(params)
+            self.grads.append(grads)
+        (states, actions), (rewards, next_states) = ins, outs
+        self.keep = [x.contiguous() for x in (states, actions, next_states, rewards)]
+        self.data = _lib.TrainData()
+        d = self.data
+        d.states, d.actions, d.next_states, d.rewards = [x.data_ptr() for x in self.keep]
+        d.transitions = states.shape[0]
+        need = self.lib.mbrl_train_ensemble_workspace_bytes(self.models, self.E, int(batch_size))
+        if need == 0:
+            _lib.check(-1, "mbrl_train_ensemble_workspace_bytes")
+        self.ws = torch.empty(need, dtype=torch.uint8, device=self.dev)
+        self.ptrs = [t.data_ptr() for params in self.params for t in params]
+
+    @classmethod
+    def cached(cls, owner, members, ins, outs, horizon, batch_size):
+        """The object of the ensemble's previous train_members call while nothing it binds has changed
+        (_NativeGrads.cached's rule): a call then allocates no gradients, workspace or tables."""
+        key = (str(_device_of(members[0])), int(horizon), int(batch_size), id(_LIB_OVERRIDE),
+               tuple(t.data_ptr() for m in members for lin in m.linears() for t in (lin.weight, lin.bias)),
+               tuple((x.data_ptr(), tuple(x.shape), x.is_contiguous()) for x in (*ins, *outs)))
+        hit = _NATIVE_ENS_CACHE.get(owner)
+        if hit is not None and hit[0] == key:
+            return hit[1]
+        obj = cls(members, ins, outs, horizon, batch_size)
+        if all(x.is_contiguous() for x in (*ins, *outs)):
+            _NATIVE_ENS_CACHE[owner] = (key, obj)
+        else:
+            _NATIVE_ENS_CACHE.pop(owner, None)
+        return obj
+
+    def epoch(self, orders, rows, batch_size, adams):
+        """One epoch of every member over the device orders [E * rows]. Returns the losses
+        [batches, E, 3] (device), or None when an optimizer's state does not allow the whole-epoch
+        call or the optimizers' hyper-parameters differ (nothing has been launched then)."""
+        for params, grads in zip(self.params, self.grads):
+            for p, g in zip(params, grads):
+                if p.grad is not g:
+                    p.grad = g
+        if [t.data_ptr() for params in self.params for t in params] != self.ptrs:
+            raise RuntimeError("model parameters moved during training")
+        steps = (rows + batch_size - 1) // batch_size
+        plans = [adam.epoch_plan(params, steps) for adam, params in zip(adams, self.params)]
+        if any(pl is None for pl in plans):
+            return None
+        hp = plans[0][1]
+        fields = [f for f, _ in hp._fields_]
+        if any(getattr(pl[1], f) != getattr(hp, f) for pl in plans for f in fields):
+            return None
+        count = len(self.params[0])
+        table = (self._lib.AdamTensor * (self.E * count))()
+        for e, pl in enumerate(plans):
+            for i in range(count):
+                src, dst = pl[0][i], table[e * count + i]
+                dst.param, dst.grad, dst.exp_avg, dst.exp_avg_sq, dst.numel = \
+                    src.param, src.grad, src.exp_avg, src.exp_avg_sq, src.numel
+        # [batches][E * count], member-major within a batch
+        ss = np.stack([np.ctypeslib.as_array(pl[2]).reshape(steps, count) for pl in plans], axis=1)
+        bc = np.stack([np.ctypeslib.as_array(pl[3]).reshape(steps, count) for pl in plans], axis=1)
+        ss, bc = np.ascontiguousarray(ss, np.float32), np.ascontiguousarray(bc, np.float32)
+        losses = torch.empty((steps, self.E, 3), dtype=torch.float32, device=self.dev)
+        self._lib.check(self.lib.mbrl_train_epoch_ensemble(
+            self.models, self.E, ctypes.byref(self.data), ctypes.c_void_p(orders.data_ptr()), int(rows),
+            int(batch_size), table, count, ctypes.byref(hp), ctypes.c_void_p(ss.ctypes.data),
+            ctypes.c_void_p(bc.ctypes.data), ctypes.c_void_p(losses.data_ptr()), ctypes.c_void_p(self.ws.data_ptr()),
+            self.ws.numel(), self._lib.stream_handle(self.dev)), "mbrl_train_epoch_ensemble")
+        for adam, params in zip(adams, self.params):
+            adam.epoch_done(params)
+        return losses
+
+
+def _train_members_native(owner, members, opts, dataset, batch_size, num_epochs, bootstrap, seed, criterion, writer):
+    """The epochs of train_members the shared launches can take, from the first: returns how many ran
+    (0: not supported here; the caller trains the rest member by member). Orders are staged as
+    _train_loop_on stages them: epoch k + 1's rows are drawn into a pinned ring row while epoch k
+    runs and copied on the side stream, with no host round trip between epochs."""
+    from . import _lib
+    dev = _device_of(members[0])
+    E = len(members)
+    if E > _lib.TRAIN_MAX_MEMBERS or len({id(m) for m in members}) != E:
+        return 0
+    _, ins, outs = dataset.stacked(dev)
+    if any(_NativeGrads.supported(m, dataset, ins, outs, criterion) is not False for m in members):
+        return 0
+    adams = [AdamStep.maybe(opt) for opt in opts]
+    if any(a is None for a in adams):
+        return 0
+    n = dataset.num_transitions()
+    native = _NativeEnsemble.cached(owner, members, ins, outs, dataset.horizon, batch_size)
+    ring = _order_ring(dev, E * n)
+    main = torch.cuda.current_stream(dev)
+
+    def fill(k):
+        def write(row):
+            for e in range(E):
+                row[e * n:(e + 1) * n] = member_order(seed, e, k, n, bootstrap)
+        return write
+    ring.draw(0, fill(0))
+    ring.copy(0, main)
+    epoch_losses, done = [], 0
+    for ep in range(num_epochs):
+        _, order = ring.rows(ep)
+        if ep >= 1:
+            ring.copied[ep % ring.K].wait(main)       # epoch ep's orders have landed
+        losses = native.epoch(order, n, batch_size, adams)
+        if losses is None:
+            break
+        if ep + 1 < num_epochs:
+            ring.draw(ep + 1, fill(ep + 1))
+            ring.copy(ep + 1, ring.side)
+        ring.consumed[ep % ring.K].record(main)       # the ring row is free once this epoch has run
+        epoch_losses.append(losses)
+        done += 1
+    if writer is not None:
+        it = 0
+        for losses in epoch_losses:
+            for row in losses.cpu().tolist():
+                it += 1
+                for e, m in enumerate(members):
+                    writer.add_scalar(f"loss/state/member{e}/{m.train_iterations}", row[e][0], it)
+    if done:
+        for m in members:
+            m.train_iterations += 1
+    return done
 
 
 class ModelWithReward(nn.Module):
