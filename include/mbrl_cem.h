@@ -12,6 +12,15 @@
  *   - Nothing here allocates or frees device memory, synchronises the device, or retains a pointer
  *     after it returns; scratch comes from the caller's workspace. Every call is stream-ordered on
  *     `stream` (a hipStream_t) and may be captured into a HIP graph.
+ *   - A workspace may hold ANY bytes on entry: no call's result depends on what its workspace held
+ *     before, and a call writes only its workspace's first *_workspace_bytes bytes and its outputs. One
+ *     buffer may therefore be reused, without clearing, by calls of different entries, shapes and sizes
+ *     that follow each other on one stream (every plan clears the flags, hand-off granules, gates and
+ *     status words it polls in its own first launch or with a memset it enqueues itself). Calls that may
+ *     be in flight at once -- on two streams, or from two threads -- need a workspace each. The one
+ *     exception is the single-model training workspace (mbrl_train_grads / mbrl_train_epoch): the caller
+ *     zeroes it once before its first use and then reuses it as it is (see mbrl_train_status_offset).
+ *     tests/test_gpu_workspace_independence.py holds every entry to this.
  *   - Return value: MBRL_OK (0) or a negative MBRL_E* code; mbrl_last_error() then holds a
  *     thread-local message. The Python layer turns a nonzero code into RuntimeError, matching the
  *     reference's exceptions-only convention.

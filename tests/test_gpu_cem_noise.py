@@ -127,9 +127,10 @@ def test_null_mix_is_the_white_draw_and_a_long_horizon_is_refused():
 
 
 def c_plan_mixed(prob, p, N, H, K, I, mix, keep=0, init_mu_rows=None, init_sigma_rows=None, carry_in=None,
-                 record=True, expect=0, ws_bytes=None, null=()):
+                 record=True, expect=0, ws_bytes=None, null=(), make_ws=None, alloc=None):
     """mbrl_cem_plan_rh_mixed through ctypes (c_plan_rh's shapes; the proposals of the last iteration are not
-    recorded by the ABI). With `expect` nonzero: asserts that code and that nothing was written."""
+    recorded by the ABI). With `expect` nonzero: asserts that code and that nothing was written. make_ws(nbytes) -> the uint8 workspace and
+    alloc(*shape, dt=) -> an output tensor replace the private allocations (tests/workspace_cases.py)."""
     from mbrl_amd import _lib
     lib = _lib.load()
     md = prob.mdesc
@@ -137,8 +138,9 @@ def c_plan_mixed(prob, p, N, H, K, I, mix, keep=0, init_mu_rows=None, init_sigma
     params = _params(p, N, H, K, I, keep)
     need = lib.mbrl_cem_rh_mixed_workspace_bytes(ctypes.byref(prob.shape), ctypes.byref(params), 1)
     dev = torch.device(DEV)
-    ws = torch.empty(max(need if ws_bytes is None else ws_bytes, 256), dtype=torch.uint8, device=dev)
-    e = lambda *sh, dt=torch.float32: torch.full(sh, -7, dtype=dt, device=dev)  # noqa: E731
+    ws = make_ws(need) if make_ws else torch.empty(max(need if ws_bytes is None else ws_bytes, 256), dtype=torch.uint8,
+                                                   device=dev)
+    e = alloc or (lambda *sh, dt=torch.float32: torch.full(sh, -7, dtype=dt, device=dev))  # noqa: E731
     out = dict(mu=e(H, a), sigma=e(H, a), actions=e(H, a), states=e(H, s))
     Kc = max(keep, 0)
     if Kc:
@@ -283,8 +285,9 @@ def test_a_nan_kept_row_sorts_last_in_the_mixed_plan():
     assert _bits(got["mu"]) == _bits(ref["mu_out"]) and _bits(got["carry"]) == _bits(ref["carry"])
 
 
-def c_plan_batch_mixed(prob, p, s0s, N, H, K, I, mix, keep=0, ins=None, record=True, expect=0, ws_bytes=None):
-    """mbrl_cem_plan_rh_batch_mixed through ctypes (c_plan_rh_batch's shapes)."""
+def c_plan_batch_mixed(prob, p, s0s, N, H, K, I, mix, keep=0, ins=None, record=True, expect=0, ws_bytes=None,
+                       make_ws=None, alloc=None):
+    """mbrl_cem_plan_rh_batch_mixed through ctypes (c_plan_rh_batch's shapes; make_ws / alloc as c_plan_rh's)."""
     from mbrl_amd import _lib
     lib = _lib.load()
     md = prob.mdesc
@@ -293,8 +296,9 @@ def c_plan_batch_mixed(prob, p, s0s, N, H, K, I, mix, keep=0, ins=None, record=T
     params = _params(p, N, H, K, I, keep)
     need = lib.mbrl_cem_rh_mixed_workspace_bytes(ctypes.byref(prob.shape), ctypes.byref(params), B)
     dev = torch.device(DEV)
-    ws = torch.empty(max(need if ws_bytes is None else ws_bytes, 256), dtype=torch.uint8, device=dev)
-    e = lambda *sh, dt=torch.float32: torch.full(sh, -7, dtype=dt, device=dev)  # noqa: E731
+    ws = make_ws(need) if make_ws else torch.empty(max(need if ws_bytes is None else ws_bytes, 256), dtype=torch.uint8,
+                                                   device=dev)
+    e = alloc or (lambda *sh, dt=torch.float32: torch.full(sh, -7, dtype=dt, device=dev))  # noqa: E731
     out = dict(mu=e(B, H, a), sigma=e(B, H, a), actions=e(B, H, a), states=e(B, H, s))
     if keep:
         out.update(carry=e(B, keep, H, a), carry_returns=e(B, keep))

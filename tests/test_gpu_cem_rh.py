@@ -40,9 +40,10 @@ def _params(p, N, H, K, I, keep):
 
 
 def c_plan_rh(prob, p, N, H, K, I, keep=0, init_mu_rows=None, init_sigma_rows=None, carry_in=None, record=True,
-              expect=0, ws_bytes=None):
+              expect=0, ws_bytes=None, make_ws=None, alloc=None):
     """mbrl_cem_plan_rh through ctypes. Returns the outputs and records as device tensors; with `expect`
-    nonzero, asserts that return code instead (the argument checks)."""
+    nonzero, asserts that return code instead (the argument checks). make_ws(nbytes) -> the uint8 workspace and
+    alloc(*shape, dt=) -> an output tensor replace the private allocations (tests/workspace_cases.py)."""
     from mbrl_amd import _lib
     lib = _lib.load()
     md = prob.mdesc
@@ -50,8 +51,9 @@ def c_plan_rh(prob, p, N, H, K, I, keep=0, init_mu_rows=None, init_sigma_rows=No
     params = _params(p, N, H, K, I, keep)
     need = lib.mbrl_cem_rh_workspace_bytes(ctypes.byref(prob.shape), ctypes.byref(params))
     dev = torch.device(DEV)
-    ws = torch.empty(max(need if ws_bytes is None else ws_bytes, 256), dtype=torch.uint8, device=dev)
-    e = lambda *sh, dt=torch.float32: torch.full(sh, -7, dtype=dt, device=dev)  # noqa: E731
+    ws = make_ws(need) if make_ws else torch.empty(max(need if ws_bytes is None else ws_bytes, 256), dtype=torch.uint8,
+                                                   device=dev)
+    e = alloc or (lambda *sh, dt=torch.float32: torch.full(sh, -7, dtype=dt, device=dev))  # noqa: E731
     out = dict(mu=e(H, a), sigma=e(H, a), actions=e(H, a), states=e(H, s))
     Kc = max(keep, 0)
     if Kc:

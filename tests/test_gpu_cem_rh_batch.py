@@ -33,11 +33,12 @@ RECORDS = ("costs", "returns", "elites", "kept_hist")
 
 
 def c_plan_rh_batch(prob, p, s0s, N, H, K, I, keep=0, ins=None, flags="given", record=True, expect=0, ws_bytes=None,
-                    B=None, null=(), ws_size=None):
+                    B=None, null=(), ws_size=None, make_ws=None, alloc=None):
     """mbrl_cem_plan_rh_batch through ctypes. ins: br.stack_inputs' dict (its flags are passed unless
     flags=None). Returns the outputs and records as device tensors; with `expect` nonzero, asserts that return
     code and that nothing was written. null: names among packed / s0 / actions / states / workspace passed as
-    NULL; ws_size: the bytes to allocate when the query cannot size the call."""
+    NULL; ws_size: the bytes to allocate when the query cannot size the call. make_ws(nbytes) -> the uint8 workspace and
+    alloc(*shape, dt=) -> an output tensor replace the private allocations (tests/workspace_cases.py)."""
     from mbrl_amd import _lib
     lib = _lib.load()
     md = prob.mdesc
@@ -47,8 +48,9 @@ def c_plan_rh_batch(prob, p, s0s, N, H, K, I, keep=0, ins=None, flags="given", r
     params = _params(p, N, H, K, I, keep)
     need = lib.mbrl_cem_rh_batch_workspace_bytes(ctypes.byref(prob.shape), ctypes.byref(params), B)
     dev = torch.device(DEV)
-    ws = torch.empty(max(ws_size or (need if ws_bytes is None else ws_bytes), 256), dtype=torch.uint8, device=dev)
-    e = lambda *sh, dt=torch.float32: torch.full(sh, -7, dtype=dt, device=dev)  # noqa: E731
+    ws = make_ws(need) if make_ws else torch.empty(max(ws_size or (need if ws_bytes is None else ws_bytes), 256),
+                                                   dtype=torch.uint8, device=dev)
+    e = alloc or (lambda *sh, dt=torch.float32: torch.full(sh, -7, dtype=dt, device=dev))  # noqa: E731
     out = dict(mu=e(Bo, H, a), sigma=e(Bo, H, a), actions=e(Bo, H, a), states=e(Bo, H, s))
     Kc = max(keep, 0)
     if Kc:

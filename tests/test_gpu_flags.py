@@ -190,27 +190,30 @@ def test_pair_rollout_in_a_plan(family, variant):
 
 
 # ------------------------------------------------------------------------------------------------ b. trajectory
-def trajectory(prob, p, acts, opts=()):
+def trajectory(prob, p, acts, opts=(), make_ws=None, alloc=None):
     """fused.trajectory (the wrapper the planners' shard path uses), or for norm == NULL, which has no
-    Python spelling, mbrl_trajectory through ctypes: (member-mean states [H, s], member states [E, H, s])."""
+    Python spelling, mbrl_trajectory through ctypes: (member-mean states [H, s], member states [E, H, s]).
+    make_ws(nbytes) -> the uint8 workspace and alloc(*shape, dt=) -> an output tensor: the ctypes call on
+    them, whatever the norm (tests/workspace_cases.py)."""
     from mbrl_amd import _lib, fused
     H = acts.shape[0]
     E, s = p["cfg"]["E"], p["cfg"]["s"]
     s0 = torch.from_numpy(p["s0"]).to(DEV)
     a_d = torch.from_numpy(np.array(acts)).to(DEV)
-    members = torch.full((E, H, s), float("nan"), dtype=torch.float32, device=DEV)
+    e = alloc or (lambda *sh, dt=torch.float32: torch.full(sh, float("nan"), dtype=dt, device=DEV))  # noqa: E731
+    members = e(E, H, s)
     with ExitStack() as stack:
         for name, value in dict(opts).items():
             stack.enter_context(_lib.option(name, value))
-        if p["norm"] is not None:
+        if p["norm"] is not None and make_ws is None:
             states = fused.trajectory(prob, s0, a_d, H, member_states=members)
         else:
             lib = _lib.load()
             shape, packed, norm_ref, _ = prob.refs
-            assert norm_ref is None
-            states = torch.full((H, s), float("nan"), dtype=torch.float32, device=DEV)
+            assert (norm_ref is None) == (p["norm"] is None)
+            states = e(H, s)
             need = lib.mbrl_trajectory_workspace_bytes(shape, H)
-            ws = torch.empty(need, dtype=torch.uint8, device=DEV)
+            ws = make_ws(need) if make_ws else torch.empty(need, dtype=torch.uint8, device=DEV)
             _lib.check(lib.mbrl_trajectory(shape, packed, norm_ref, _lib.ptr(s0), _lib.ptr(a_d), H, _lib.ptr(states),
                                            _lib.ptr(members), _lib.ptr(ws), ws.numel(),
                                            _lib.stream_handle(torch.device(DEV))), "mbrl_trajectory")

@@ -40,19 +40,24 @@ def device_problem(name):
 def run_grad(name, opts=(), plans=None):
     """mbrl_gd_grad on the case's plans (all, or the listed ones in one call) under the options:
     (states [B, H + 1, s], grad [B, H, a]) as NumPy. The given actions must come back untouched."""
-    from mbrl_amd import _lib
-    lib = _lib.load()
-    prob = device_problem(name)
     S0, A = gc.inputs(name)
     if plans is not None:
         S0, A = S0[list(plans)], A[list(plans)]
+    return grad_call(device_problem(name), S0, A, opts)
+
+
+def grad_call(prob, S0, A, opts=(), make_ws=None, alloc=None):
+    """mbrl_gd_grad on start states S0 [B, s] and sequences A [B, H, a]. make_ws(nbytes) -> the uint8 workspace
+    and alloc(*shape, dt=) -> an output tensor replace the private allocations (tests/workspace_cases.py)."""
+    from mbrl_amd import _lib
+    lib = _lib.load()
     B, H, a = A.shape
     s0 = torch.from_numpy(np.array(S0)).to(DEV)
     acts = torch.from_numpy(np.array(A)).to(DEV)
-    grad = torch.full((B, H, a), float("nan"), dtype=torch.float32, device=DEV)
-    states = torch.full((B, H + 1, S0.shape[1]), float("nan"), dtype=torch.float32, device=DEV)
+    e = alloc or (lambda *sh, dt=torch.float32: torch.full(sh, float("nan"), dtype=dt, device=DEV))  # noqa: E731
+    grad, states = e(B, H, a), e(B, H + 1, S0.shape[1])
     need = lib.mbrl_gd_batch_workspace_bytes(prob.refs[0], H, B)
-    ws = torch.empty(need, dtype=torch.uint8, device=DEV)
+    ws = make_ws(need) if make_ws else torch.empty(need, dtype=torch.uint8, device=DEV)
     with ExitStack() as stack:
         for opt, value in opts:
             stack.enter_context(_lib.option(opt, value))

@@ -102,8 +102,10 @@ def _orders(E, T, epochs, seed=0):
     return o
 
 
-def _single_epochs(mem, data, orders, batch, wd=0.0, lr=LR, step0=0):
-    """mbrl_train_epoch on one member, one call per epoch; returns the losses [epochs][batches][3]."""
+def _single_epochs(mem, data, orders, batch, wd=0.0, lr=LR, step0=0, make_ws=None, alloc=None):
+    """mbrl_train_epoch on one member, one call per epoch; returns the losses [epochs][batches][3].
+    make_ws(nbytes) -> the uint8 workspace (zeroed by its maker: the single-model contract) and
+    alloc(*shape) -> an output tensor replace the private allocations (tests/workspace_cases.py)."""
     from mbrl_amd import _lib
     lib = _lib.load()
     tm = _lib.TrainModel()
@@ -111,14 +113,15 @@ def _single_epochs(mem, data, orders, batch, wd=0.0, lr=LR, step0=0):
     n = len(mem.params)
     table = (_lib.AdamTensor * n)()
     mem.adam(table, 0)
-    ws = torch.zeros(lib.mbrl_train_workspace_bytes(ctypes.byref(tm), batch), dtype=torch.uint8, device=DEV)
+    need = lib.mbrl_train_workspace_bytes(ctypes.byref(tm), batch)
+    ws = make_ws(need) if make_ws else torch.zeros(need, dtype=torch.uint8, device=DEV)
     rows = orders.shape[1]
     steps = (rows + batch - 1) // batch
     hp = _hp(wd)
     out = []
     for k in range(orders.shape[0]):
         order = torch.from_numpy(orders[k]).to(DEV)
-        losses = torch.zeros((steps, 3), device=DEV)
+        losses = alloc(steps, 3) if alloc else torch.zeros((steps, 3), device=DEV)
         ss, bc = _scalars([step0 + k * steps], steps, n, [lr])
         _lib.check(lib.mbrl_train_epoch(ctypes.byref(tm), ctypes.byref(data.c), _P(order), rows, batch, table, n,
                                         ctypes.byref(hp), ss, bc, _P(losses), _P(ws), ws.numel(),
@@ -128,9 +131,9 @@ def _single_epochs(mem, data, orders, batch, wd=0.0, lr=LR, step0=0):
     return torch.stack(out)
 
 
-def _ensemble_epochs(mems, data, orders, batch, wd=0.0, lrs=None, step0s=None):
+def _ensemble_epochs(mems, data, orders, batch, wd=0.0, lrs=None, step0s=None, make_ws=None, alloc=None):
     """mbrl_train_epoch_ensemble on the members, one call per epoch; losses [epochs][batches][E][3].
-    orders: [epochs][E][rows]."""
+    orders: [epochs][E][rows]. make_ws / alloc: as _single_epochs' (this workspace needs no zeroing)."""
     from mbrl_amd import _lib
     lib = _lib.load()
     E = len(mems)
@@ -142,14 +145,15 @@ def _ensemble_epochs(mems, data, orders, batch, wd=0.0, lrs=None, step0s=None):
         mem.adam(table, e * n)
     need = lib.mbrl_train_ensemble_workspace_bytes(tms, E, batch)
     assert need > 0
-    ws = torch.empty(need, dtype=torch.uint8, device=DEV).fill_(0xA5)   # the workspace needs no zeroing
+    # the workspace needs no zeroing
+    ws = make_ws(need) if make_ws else torch.empty(need, dtype=torch.uint8, device=DEV).fill_(0xA5)
     rows = orders.shape[2]
     steps = (rows + batch - 1) // batch
     hp = _hp(wd)
     out = []
     for k in range(orders.shape[0]):
         order = torch.from_numpy(np.ascontiguousarray(orders[k])).to(DEV)
-        losses = torch.zeros((steps, E, 3), device=DEV)
+        losses = alloc(steps, E, 3) if alloc else torch.zeros((steps, E, 3), device=DEV)
         ss, bc = _scalars([s0 + k * steps for s0 in (step0s or [0] * E)], steps, n, lrs)
         _lib.check(lib.mbrl_train_epoch_ensemble(tms, E, ctypes.byref(data.c), _P(order), rows, batch, table, n,
                                                  ctypes.byref(hp), ss, bc, _P(losses), _P(ws), ws.numel(),
@@ -216,33 +220,47 @@ def test_single_model_layouts_agree_with_the_ensemble(T_, batch):
                 assert torch.equal(losses[:, :, e], want), (split, e)
 
 
-def _grads_calls(mems, data, idx):
-    """mbrl_train_grads_ensemble on rows idx [E][batch]; then mbrl_train_grads per member on clones.
-    Returns (ensemble losses [E][3], [(clone, its loss [3])])."""
+def _grads_ensemble(mems, data, didx, make_ws=None, alloc=None):
+    """mbrl_train_grads_ensemble on device rows didx [E][batch]: the losses [E][3] (make_ws / alloc: as
+    _single_epochs')."""
     from mbrl_amd import _lib
     lib = _lib.load()
-    E, batch = idx.shape
-    clones = [m.clone() for m in mems]
+    E, batch = didx.shape
     tms = (_lib.TrainModel * E)()
     for e, mem in enumerate(mems):
         mem.fill(tms[e])
-    ws = torch.empty(lib.mbrl_train_ensemble_workspace_bytes(tms, E, batch), dtype=torch.uint8, device=DEV).fill_(0x5A)
-    loss = torch.zeros((E, 3), device=DEV)
-    didx = torch.from_numpy(np.ascontiguousarray(idx)).to(DEV)
+    need = lib.mbrl_train_ensemble_workspace_bytes(tms, E, batch)
+    ws = make_ws(need) if make_ws else torch.empty(need, dtype=torch.uint8, device=DEV).fill_(0x5A)
+    loss = alloc(E, 3) if alloc else torch.zeros((E, 3), device=DEV)
     _lib.check(lib.mbrl_train_grads_ensemble(tms, E, ctypes.byref(data.c), _P(didx), batch, _P(loss), _P(ws), ws.numel(),
                                              _lib.stream_handle(DEV)), "mbrl_train_grads_ensemble")
     torch.cuda.synchronize()
-    singles = []
-    for e, c in enumerate(clones):
-        tm = _lib.TrainModel()
-        c.fill(tm)
-        ws1 = torch.zeros(lib.mbrl_train_workspace_bytes(ctypes.byref(tm), batch), dtype=torch.uint8, device=DEV)
-        l1 = torch.zeros(3, device=DEV)
-        _lib.check(lib.mbrl_train_grads(ctypes.byref(tm), ctypes.byref(data.c), _P(didx[e]), batch, _P(l1), _P(ws1),
-                                        ws1.numel(), _lib.stream_handle(DEV)), "mbrl_train_grads")
-        torch.cuda.synchronize()
-        singles.append((c, l1))
-    return loss, singles
+    return loss
+
+
+def _grads_single(mem, data, rows, make_ws=None, alloc=None):
+    """mbrl_train_grads on one member and device rows [batch]: its loss [3]."""
+    from mbrl_amd import _lib
+    lib = _lib.load()
+    batch = rows.numel()
+    tm = _lib.TrainModel()
+    mem.fill(tm)
+    need = lib.mbrl_train_workspace_bytes(ctypes.byref(tm), batch)
+    ws1 = make_ws(need) if make_ws else torch.zeros(need, dtype=torch.uint8, device=DEV)
+    l1 = alloc(3) if alloc else torch.zeros(3, device=DEV)
+    _lib.check(lib.mbrl_train_grads(ctypes.byref(tm), ctypes.byref(data.c), _P(rows), batch, _P(l1), _P(ws1),
+                                    ws1.numel(), _lib.stream_handle(DEV)), "mbrl_train_grads")
+    torch.cuda.synchronize()
+    return l1
+
+
+def _grads_calls(mems, data, idx):
+    """mbrl_train_grads_ensemble on rows idx [E][batch]; then mbrl_train_grads per member on clones.
+    Returns (ensemble losses [E][3], [(clone, its loss [3])])."""
+    clones = [m.clone() for m in mems]
+    didx = torch.from_numpy(np.ascontiguousarray(idx)).to(DEV)
+    loss = _grads_ensemble(mems, data, didx)
+    return loss, [(c, _grads_single(c, data, didx[e])) for e, c in enumerate(clones)]
 
 
 @pytest.mark.parametrize("s,a,W,L,H,reward,batch", [(5, 2, 50, 2, 2, 1, 37), (4, 1, 64, 1, 1, 0, 32),
