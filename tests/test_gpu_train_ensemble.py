@@ -24,24 +24,47 @@ def _P(t):
 class _Data:
     """Stacked transitions [T][H][.] as the C entries read them."""
 
-    def __init__(self, s, a, H, T, seed):
+    def __init__(self, s, a, H, T, seed, arrays=None):
+        """arrays: the transitions themselves (states / actions / next_states [T][H][.], rewards [T][H] as
+        NumPy) instead of the seeded draw. a = 0: the C struct's actions pointer is NULL."""
         from mbrl_amd import _lib
         g = torch.Generator().manual_seed(seed)
-        self.states = torch.randn((T, H, s), generator=g).to(DEV)
-        self.actions = torch.rand((T, H, a), generator=g).mul(2).sub(1).to(DEV)
-        self.next_states = torch.randn((T, H, s), generator=g).to(DEV)
-        self.rewards = torch.randn((T, H), generator=g).to(DEV)
+        if arrays is None:
+            self.states = torch.randn((T, H, s), generator=g).to(DEV)
+            self.actions = torch.rand((T, H, a), generator=g).mul(2).sub(1).to(DEV)
+            self.next_states = torch.randn((T, H, s), generator=g).to(DEV)
+            self.rewards = torch.randn((T, H), generator=g).to(DEV)
+        else:
+            self.states, self.actions, self.next_states, self.rewards = [
+                torch.from_numpy(np.array(arrays[k], np.float32)).to(DEV)
+                for k in ("states", "actions", "next_states", "rewards")]
+            assert self.states.shape == (T, H, s) and self.actions.shape == (T, H, a)
+            assert self.next_states.shape == (T, H, s) and self.rewards.shape == (T, H)
         self.T = T
         d = self.c = _lib.TrainData()
         d.states, d.actions, d.next_states, d.rewards = [x.data_ptr() for x in (self.states, self.actions,
                                                                                  self.next_states, self.rewards)]
+        if a == 0:
+            d.actions = None
         d.transitions = T
+
+
+def _offset_like(t):
+    """A copy of t as a view 4 bytes into a larger buffer: data_ptr() % 16 == 4."""
+    buf = torch.empty(t.numel() + 8, dtype=t.dtype, device=t.device)
+    v = buf[1:1 + t.numel()].view(t.shape)
+    v.copy_(t)
+    assert v.data_ptr() % 16 == 4
+    return v
 
 
 class _Member:
     """One member's tensors: every Linear's weight and bias, their gradients and Adam state."""
 
-    def __init__(self, s, a, W, L, reward, H, seed):
+    def __init__(self, s, a, W, L, reward, H, seed, values=None, offset_params=(), offset_grads=()):
+        """values: the parameters (NumPy, in params' order) instead of the seeded draw. offset_params /
+        offset_grads: indices into params / grads of the tensors allocated as views 4 bytes into a larger
+        buffer (_offset_like), so that their pointers are not 16-byte aligned."""
         g = torch.Generator().manual_seed(seed)
         dims = [(W, s + a)] + [(W, W)] * (L - 1) + [(s, W)] + ([(1, W)] if reward else [])
         self.shape = (s, a, W, L, int(reward), H)
@@ -50,14 +73,21 @@ class _Member:
             bound = 1.0 / fi ** 0.5
             self.params.append(torch.rand((fo, fi), generator=g).mul(2 * bound).sub(bound).to(DEV))
             self.params.append(torch.rand((fo,), generator=g).mul(2 * bound).sub(bound).to(DEV))
+        if values is not None:
+            assert [tuple(v.shape) for v in values] == [tuple(p.shape) for p in self.params]
+            self.params = [torch.from_numpy(np.array(v, np.float32)).to(DEV) for v in values]
         self.grads = [torch.zeros_like(p) for p in self.params]
         self.m = [torch.zeros_like(p) for p in self.params]
         self.v = [torch.zeros_like(p) for p in self.params]
+        for i in offset_params:
+            self.params[i] = _offset_like(self.params[i])
+        for i in offset_grads:
+            self.grads[i] = _offset_like(self.grads[i])
 
     def clone(self):
         c = copy.copy(self)
         for k in ("params", "grads", "m", "v"):
-            setattr(c, k, [t.clone() for t in getattr(self, k)])
+            setattr(c, k, [_offset_like(t) if t.data_ptr() % 16 else t.clone() for t in getattr(self, k)])
         return c
 
     def fill(self, tm):
