@@ -854,6 +854,58 @@ int mbrl_train_epoch_ensemble(const mbrl_train_model* members, int32_t E, const 
                               const float* bc2_sqrt, float* losses, void* workspace, size_t ws_bytes,
                               mbrl_stream_t stream);
 
+/* ---- held-out evaluation of ensemble members (added within ABI v13): E members of one shape, forward
+ * only, on the dataset rows rows[0..R) (device int64; indices may repeat and need no order; each
+ * < transitions, not checked on the device; R may exceed transitions). With i = rows[r],
+ * x = (states[i][h], actions[i][h]) and (s^, r^) the member's forward pass as mbrl_train_grads defines it
+ * (n_hidden Linear-ReLU layers, the state head and, with reward_head, the reward head; the weights are
+ * read from the live buffers of the struct, whose weight_grad / bias_grad are ignored and may be NULL; a
+ * member may be listed twice):
+ *   row_err[e][r][h]     = sum_j (s^_j - next_states[i][h][j])^2      fp32, j ascending, no contraction
+ *   row_rew_err[e][r][h] = (r^ - rewards[i][h])^2                     required iff reward_head, else NULL
+ *   loss_out[e]          = (state + reward, state, reward) or NULL, with
+ *                          state  = sum_h (sum_r row_err[e][r][h]) / (R s),
+ *                          reward = sum_h (sum_r row_rew_err[e][r][h]) / R
+ * -- mbrl_train_grads' loss of a batch made of these rows. The sum over r is taken in one order that
+ * depends on R alone: lane t of 1024 adds r = t, t + 1024, ... ascending, and the 1024 partials meet in a
+ * pairwise tree (partial[t] += partial[t + d], d = 512, 256, .. 1); the steps are added h ascending.
+ * row_err[e][r][h] depends, byte for byte, on member e's parameters and dataset row rows[r] at step h
+ * alone: not on E, the other members, R, r or the neighbouring rows. Every output element is written and
+ * what the outputs held on entry never matters. No workspace, no allocation, no synchronisation: stream-
+ * ordered and capturable. Two launches whatever E and R are (one with loss_out == NULL): the row errors
+ * with the members on a grid axis, 16 (r, h) positions per workgroup, then one workgroup per member for
+ * the losses; neither waits on another workgroup.
+ * Envelope: state_dim, state_dim + action_dim and hidden <= MBRL_EVAL_MAX_DIM, n_hidden <=
+ * MBRL_TRAIN_MAX_LAYERS - 2, action_dim = 0 with NULL actions, parameters at any 4-byte alignment;
+ * beyond it MBRL_EUNSUPPORTED. Before any launch: MBRL_EINVAL for NULL members, data, rows or row_err, a
+ * missing or superfluous row_rew_err, a NULL weight or bias, E < 1, R < 1, a bad shape or member shapes
+ * that differ; MBRL_EUNSUPPORTED for E > MBRL_TRAIN_MAX_MEMBERS or E * R * horizon >= 2^31. */
+#define MBRL_EVAL_MAX_DIM 1024
+int mbrl_eval_members(const mbrl_train_model* members, int32_t E, const mbrl_train_data* data,
+                      const int64_t* rows, int64_t R, float* row_err, float* row_rew_err, float* loss_out,
+                      mbrl_stream_t stream);
+
+/* Keep-best snapshots: per member e, v = loss[e * loss_stride] (device) against best_loss[e] AS IT WAS ON
+ * ENTRY. If v < best_loss[e] (a NaN is never better): best_loss[e] = v, best_epoch[e] = epoch,
+ * stale[e] = 0, and each of the member's `count` tensors tensors[e * count + i] (host table [E][count]) is
+ * copied src -> dst bit for bit. Otherwise stale[e] += 1 and no byte of any dst is written. The caller
+ * starts with best_loss = +inf, best_epoch = -1, stale = 0 (device arrays [E], in/out).
+ * Ordering: the copy launches come first and only read loss and best_loss; the one launch that updates
+ * best_loss, best_epoch and stale follows them on the stream, so no copy acts on an updated best_loss.
+ * The table travels in the launch arguments (64 tensors per launch; more take further launches). A dst
+ * must not overlap loss, best_loss or any src. No workspace, no allocation, no synchronisation.
+ * Before any launch: MBRL_EINVAL for a NULL loss, best_loss, best_epoch or stale, E < 1, loss_stride < 1,
+ * epoch < 0, count < 0, a NULL table with count > 0, or a tensor with numel < 0 or with numel > 0 and a
+ * NULL src or dst. */
+typedef struct {
+    const float* src;
+    float* dst;
+    int64_t numel;
+} mbrl_copy_tensor;
+int mbrl_keep_best(const float* loss, int32_t loss_stride, int32_t E, int32_t epoch, float* best_loss,
+                   int32_t* best_epoch, int32_t* stale, const mbrl_copy_tensor* tensors, int32_t count,
+                   mbrl_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

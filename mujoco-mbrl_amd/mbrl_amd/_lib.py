@@ -76,6 +76,7 @@ EXPORTED = (
     "mbrl_mppi_plan_elite", "mbrl_mppi_plan_elite_batch",
     "mbrl_gd_grad",
     "mbrl_train_ensemble_workspace_bytes", "mbrl_train_grads_ensemble", "mbrl_train_epoch_ensemble",
+    "mbrl_eval_members", "mbrl_keep_best",
 )
 
 
@@ -153,6 +154,11 @@ class TrainData(ctypes.Structure):
                 ("transitions", c_int64)]
 
 
+class CopyTensor(ctypes.Structure):
+    """mbrl_copy_tensor (include/mbrl_cem.h; added within ABI v13): one tensor of mbrl_keep_best's table."""
+    _fields_ = [("src", c_void_p), ("dst", c_void_p), ("numel", c_int64)]
+
+
 _lib = None
 
 
@@ -218,6 +224,8 @@ def load():
         "mbrl_train_epoch_ensemble": (c_int32, [POINTER(TrainModel), c_int32, POINTER(TrainData), P, c_int64, c_int32,
                                                 POINTER(AdamTensor), c_int32, POINTER(AdamHparams), P, P, P, P,
                                                 c_size_t, P]),
+        "mbrl_eval_members": (c_int32, [POINTER(TrainModel), c_int32, POINTER(TrainData), P, c_int64, P, P, P, P]),
+        "mbrl_keep_best": (c_int32, [P, c_int32, c_int32, c_int32, P, P, P, POINTER(CopyTensor), c_int32, P]),
         "mbrl_cem_plan": (c_int32, [POINTER(MlpShape), P, POINTER(Norm), POINTER(Cost), P, POINTER(CemParams),
                                     P, P, P, P, P, P, P, P, P, c_size_t, P]),
         "mbrl_mppi_update": (c_int32, [P, c_int32, c_int32, P, POINTER(Sampler), c_int32, c_int32, c_float, c_float,
@@ -438,4 +446,4 @@ __all__ = ["load", "check", "ptr", "stream_handle", "MlpShape", "Norm", "Cost", 
            "EXPORTED", "MBRL_NAN_LAST", "MBRL_NAN_FIRST", "MBRL_COST_GOAL_STATE", "MBRL_COST_MODEL_REWARD",
            "ABI_VERSION", "c_int64", "MBRL_PRECISION_F32", "MBRL_PRECISION_F16X3", "MBRL_PRECISION_F16X6",
            "precision_code", "load_other", "option", "OPTIONS", "AdamTensor", "AdamHparams",
-           "TrainModel", "TrainData", "TRAIN_MAX_LAYERS", "TRAIN_MAX_MEMBERS", "HostStaging"]
+           "TrainModel", "TrainData", "TRAIN_MAX_LAYERS", "TRAIN_MAX_MEMBERS", "HostStaging", "CopyTensor"]

@@ -648,6 +648,125 @@ class EnsembleModel(DynamicsModel):
         self.train_iterations += 1
         return first
 
+    def evaluate_members(self, dataset, rows=None):
+        """Every member's error on rows `rows` of dataset.stacked() (default: all of them; indices may repeat):
+        dict(loss [E], per_step [E, horizon], row_err [E, R, horizon]) on the ensemble's device, with
+            row_err[e, r, h] = sum_j (member e's predicted next state - next_states[rows[r], h])_j ** 2,
+            per_step[e, h]   = sum_r row_err[e, r, h] / (R * state_dim)    (MSELoss of step h),
+            loss[e]          = sum_h per_step[e, h]: train_members' loss of a batch made of these rows.
+        On a GPU, when train_members' support test passes for every member, one mbrl_eval_members call
+        (csrc/eval.hip) with no host synchronisation -- pass `rows` as a device tensor to keep its upload out
+        as well; otherwise (CPU, `noise`, more than 8 members) the same definitions in torch."""
+        members = list(self.members)
+        dev = _device_of(self)
+        _, ins, outs = dataset.stacked(dev)
+        rows = _holdout_rows(dataset, dev, rows)
+        R, H = int(rows.shape[0]), dataset.horizon
+        if R < 1:
+            raise ValueError("evaluate_members needs at least one row")
+        if _NativeEval.supported(members, dataset, ins, outs):
+            with torch.cuda.device(dev):
+                row_err = torch.empty((len(members), R, H), dtype=torch.float32, device=dev)
+                loss3 = torch.empty((len(members), 3), dtype=torch.float32, device=dev)
+                _NativeEval(members, ins, outs, H).run(rows, row_err, loss3)
+            loss = loss3[:, 0]
+        else:
+            row_err = _eval_members_torch(members, ins, outs, rows)
+            loss = None
+        per_step = row_err.sum(1) / (R * self.state_dim)
+        return dict(loss=per_step.sum(1) if loss is None else loss, per_step=per_step, row_err=row_err)
+
+    def fit_members(self, dataset, holdout, optimizers, batch_size=512, max_epochs=50, patience=None, check_every=1,
+                    restore_best=True, bootstrap=True, seed=0, criterion=None, writer=None):
+        """train_members with a held-out set: the same epochs (orders, shared launches and fallback rules
+        are train_members'), and after each epoch every member's loss on all rows of `holdout` (a
+        TransitionsDataset of the same spec; evaluate_members' loss) and a snapshot of each member's
+        parameters whenever its loss is below all its earlier ones (a NaN never is). On the native path the
+        evaluation and the snapshots are two C calls enqueued on the training stream (mbrl_eval_members,
+        mbrl_keep_best); with patience=None the host never waits between epochs.
+
+        patience: after each epoch k with (k + 1) % check_every == 0 the host reads the members' `stale`
+        counts (epochs since the member's best) and stops when every member's is >= patience
+        (tests/holdout_reference.py restates the rule in NumPy). restore_best: at the end each member's parameters become its
+        snapshot, by an in-place copy (the planners' cached weight packs are refreshed as after
+        train_members); a member whose loss was never finite has no snapshot and keeps its last weights. The optimizers' state stays at the last epoch's: it is not snapshotted, so training
+        on from restored weights starts with moments that belong to later weights.
+
+        Returns, and keeps as self.holdout_report, dict(val_loss [epochs_run, E], best_loss [E],
+        best_epoch [E] (CPU tensors), epochs_run, native_epochs: the epochs that trained in the shared
+        launches, native_eval: whether the held-out losses came from mbrl_eval_members). Writer tags: train_members', and loss/holdout/member{e}/{iteration} per epoch."""
+        members = list(self.members)
+        opts = [optimizers(m) for m in members] if callable(optimizers) else list(optimizers)
+        if len(opts) != len(members):
+            raise ValueError(f"fit_members needs one optimizer per member ({len(members)}), got {len(opts)}")
+        if patience is not None and (patience < 1 or check_every < 1):
+            raise ValueError("fit_members needs patience >= 1 and check_every >= 1")
+        criterion = criterion or torch.nn.MSELoss()
+        n, dev = dataset.num_transitions(), _device_of(self)
+        max_epochs = max(int(max_epochs), 0) if n > 0 else 0
+        iteration = [m.train_iterations for m in members]
+        with torch.cuda.device(dev) if dev.type == "cuda" else contextlib.nullcontext():
+            tracker = _Holdout(members, holdout, max_epochs)
+            stopped = []
+
+            def after_epoch(k):
+                tracker.record(k)
+                if tracker.stop(k, patience, check_every):
+                    stopped.append(k)
+                return bool(stopped)
+            first = 0
+            if max_epochs > 0 and dev.type == "cuda":
+                first = _train_members_native(self, members, opts, dataset, batch_size, max_epochs, bootstrap, seed,
+                                              criterion, writer, after_epoch=after_epoch)
+            batches = (n + batch_size - 1) // max(batch_size, 1)
+            for k in range(tracker.epochs, 0 if stopped else max_epochs):
+                for e, (m, opt) in enumerate(zip(members, opts)):
+                    def step_loss(inp, out, m=m):
+                        (states, actions), (_, next_states) = inp, out
+                        return [criterion(m.forward(states, actions, normalize_action=None, normalize_state=None,
+                                                    unnormalize_state=None), next_states)]
+                    m.train_iterations = iteration[e]         # (one call's worth of epochs: one iteration)
+                    _train_loop(m, dataset, opt, batch_size, 1, step_loss, writer, [f"loss/state/member{e}/{{}}"],
+                                criterion, order_fn=lambda _, e=e, k=k: member_order(seed, e, k, n, bootstrap),
+                                iter0=k * batches)
+                if after_epoch(k):
+                    break
+            ran = tracker.epochs
+            best_epoch = tracker.best_epoch.detach().cpu().to(torch.int64)      # (the call's first host read)
+            if restore_best:
+                with torch.no_grad():
+                    for params, snaps, at in zip(tracker.params, tracker.snaps, best_epoch.tolist()):
+                        if at >= 0:                   # (a member whose loss was never finite stays where it is)
+                            torch._foreach_copy_(params, snaps)
+            val = tracker.val[:ran, :, 0].detach().cpu()
+            report = dict(val_loss=val, best_loss=tracker.best_loss.detach().cpu(), best_epoch=best_epoch,
+                          epochs_run=ran, native_epochs=first, native_eval=tracker.native is not None)
+        if writer is not None:
+            for k, row in enumerate(val.tolist()):
+                for e, v in enumerate(row):
+                    writer.add_scalar(f"loss/holdout/member{e}/{iteration[e]}", v, k + 1)
+        for m, it in zip(members, iteration):
+            m.train_iterations = it + 1
+        self.train_iterations += 1
+        self.holdout_report = report
+        return report
+
+    def elite(self, k, report=None):
+        """An EnsembleModel over the k members with the lowest best_loss of `report` (default: the last
+        fit_members'), ties to the lower index, in member order (elite_indices). The members are shared, not
+        copied: the planners then roll out k members, and training either ensemble trains the same weights."""
+        report = report if report is not None else getattr(self, "holdout_report", None)
+        if report is None:
+            raise ValueError("elite needs a report: call fit_members first or pass one")
+        best = np.asarray(torch.as_tensor(report["best_loss"]).cpu().numpy(), np.float64)
+        E = len(self.members)
+        if best.shape != (E,) or not 1 <= k <= E:
+            raise ValueError(f"elite needs 1 <= k <= {E} and one best_loss per member")
+        keep = sorted(np.argsort(best, kind="stable")[:k].tolist())     # (NaNs sort last)
+        out = EnsembleModel([self.members[i] for i in keep])
+        out.elite_indices = keep
+        return out
+
 
 def member_order(seed, e, k, n, bootstrap=True):
     """The rows member e visits in epoch k of EnsembleModel.train_members (int64 [n]): n draws with
@@ -750,11 +869,13 @@ class _NativeEnsemble:
         return losses
 
 
-def _train_members_native(owner, members, opts, dataset, batch_size, num_epochs, bootstrap, seed, criterion, writer):
+def _train_members_native(owner, members, opts, dataset, batch_size, num_epochs, bootstrap, seed, criterion, writer,
+                          after_epoch=None):
     """The epochs of train_members the shared launches can take, from the first: returns how many ran
     (0: not supported here; the caller trains the rest member by member). Orders are staged as
     _train_loop_on stages them: epoch k + 1's rows are drawn into a pinned ring row while epoch k
-    runs and copied on the side stream, with no host round trip between epochs."""
+    runs and copied on the side stream, with no host round trip between epochs.
+    after_epoch (fit_members): called with k once epoch k is enqueued; a true result ends the epochs."""
     from . import _lib
     dev = _device_of(members[0])
     E = len(members)
@@ -792,6 +913,8 @@ def _train_members_native(owner, members, opts, dataset, batch_size, num_epochs,
         ring.consumed[ep % ring.K].record(main)       # the ring row is free once this epoch has run
         epoch_losses.append(losses)
         done += 1
+        if after_epoch is not None and after_epoch(ep):
+            break
     if writer is not None:
         it = 0
         for losses in epoch_losses:
@@ -803,6 +926,134 @@ def _train_members_native(owner, members, opts, dataset, batch_size, num_epochs,
         for m in members:
             m.train_iterations += 1
     return done
+
+
+def _eval_members_torch(members, ins, outs, rows):
+    """mbrl_eval_members' definitions in torch (CPU, or members the native call does not take): the squared
+    error of every member's own _forward per row and horizon step, row_err [E, R, horizon]."""
+    (states, actions), (_, next_states) = ins, outs
+    with torch.no_grad():
+        st, ac, ns = (x.index_select(0, rows) for x in (states, actions, next_states))
+        R, H = st.shape[0], st.shape[1]
+        x = torch.cat([st.reshape(R * H, -1), ac.reshape(R * H, -1)], dim=1)
+        target = ns.reshape(R * H, -1)
+        return torch.stack([((m._forward(x) - target) ** 2).sum(1).reshape(R, H) for m in members])
+
+
+class _NativeEval:
+    """mbrl_eval_members for E supported members on one dataset: the members' live weights and biases (no
+    gradients), the stacked transitions, no workspace."""
+
+    def __init__(self, members, ins, outs, horizon):
+        from . import _lib
+        self._lib, self.lib = _lib, _native_lib()
+        self.dev = _device_of(members[0])
+        self.E, self.horizon = len(members), int(horizon)
+        self.params = [[t for lin in m.linears() for t in (lin.weight, lin.bias)] for m in members]
+        self.models = (_lib.TrainModel * self.E)()
+        for m, model, params in zip(self.models, members, self.params):
+            m.state_dim, m.action_dim, m.hidden = model.state_dim, model.action_dim, model.hidden_units
+            m.n_hidden, m.reward_head, m.horizon = model.n_hidden, 0, self.horizon
+            for i in range(len(params) // 2):
+                m.weight[i], m.bias[i] = params[2 * i].data_ptr(), params[2 * i + 1].data_ptr()
+        (states, actions), (rewards, next_states) = ins, outs
+        self.keep = [x.contiguous() for x in (states, actions, next_states, rewards)]
+        d = self.data = _lib.TrainData()
+        d.states, d.actions, d.next_states, d.rewards = [x.data_ptr() for x in self.keep]
+        if members[0].action_dim == 0:
+            d.actions = None
+        d.transitions = states.shape[0]
+        self.ptrs = [t.data_ptr() for params in self.params for t in params]
+
+    @staticmethod
+    def supported(members, dataset, ins, outs):
+        """train_members' own test, member by member (a member may be listed twice here)."""
+        from . import _lib
+        if _device_of(members[0]).type != "cuda" or len(members) > _lib.TRAIN_MAX_MEMBERS:
+            return False
+        mse = torch.nn.MSELoss()
+        return all(_NativeGrads.supported(m, dataset, ins, outs, mse) is False for m in members)
+
+    def run(self, rows, row_err, loss):
+        """Enqueue the evaluation of the device rows `rows` into row_err [E, R, horizon] and loss [E, 3]."""
+        if [t.data_ptr() for params in self.params for t in params] != self.ptrs:
+            raise RuntimeError("model parameters moved during evaluation")
+        P = ctypes.c_void_p
+        self._lib.check(self.lib.mbrl_eval_members(self.models, self.E, ctypes.byref(self.data), P(rows.data_ptr()),
+                                                   int(rows.shape[0]), P(row_err.data_ptr()), None, P(loss.data_ptr()),
+                                                   self._lib.stream_handle(self.dev)), "mbrl_eval_members")
+
+
+def _holdout_rows(dataset, dev, rows):
+    if rows is None:
+        return torch.arange(dataset.num_transitions(), dtype=torch.int64, device=dev)
+    return torch.as_tensor(rows, dtype=torch.int64).to(dev).contiguous().reshape(-1)
+
+
+class _Holdout:
+    """fit_members' per-epoch work: the members' losses on the held-out rows, the best loss so far and the
+    snapshot of each member's parameters at its best epoch. On the native path (mbrl_eval_members and
+    mbrl_keep_best on the training stream) the host reads nothing unless a patience asks for `stale`."""
+
+    def __init__(self, members, holdout, max_epochs):
+        self.members = members
+        dev = self.dev = _device_of(members[0])
+        _, self.ins, self.outs = holdout.stacked(dev)
+        self.rows = _holdout_rows(holdout, dev, None)
+        E, R, H = len(members), int(self.rows.shape[0]), holdout.horizon
+        if R < 1:
+            raise ValueError("fit_members needs a holdout with at least one transition")
+        self.state_dim = members[0].state_dim
+        self.params = [list(m.parameters()) for m in members]
+        # (written by a member's first finite loss; a member that never has one is not restored)
+        self.snaps = [[torch.empty_like(p) for p in params] for params in self.params]
+        self.val = torch.full((max(max_epochs, 1), E, 3), float("nan"), dtype=torch.float32, device=dev)
+        self.best_loss = torch.full((E,), float("inf"), dtype=torch.float32, device=dev)
+        self.best_epoch = torch.full((E,), -1, dtype=torch.int32, device=dev)
+        self.stale = torch.zeros(E, dtype=torch.int32, device=dev)
+        self.epochs = 0
+        self.native = None
+        if _NativeEval.supported(members, holdout, self.ins, self.outs):
+            from . import _lib
+            self.native = _NativeEval(members, self.ins, self.outs, H)
+            self.row_err = torch.empty((E, R, H), dtype=torch.float32, device=dev)
+            count = len(self.params[0])
+            self.table = (_lib.CopyTensor * (E * count))()
+            for e in range(E):
+                for i, (p, snap) in enumerate(zip(self.params[e], self.snaps[e])):
+                    t = self.table[e * count + i]
+                    t.src, t.dst, t.numel = p.data_ptr(), snap.data_ptr(), p.numel()
+            self.count = count
+
+    def record(self, k):
+        """Epoch k has been enqueued (or has run): evaluate, keep the best."""
+        E = len(self.members)
+        if self.native is not None:
+            nat, P = self.native, ctypes.c_void_p
+            nat.run(self.rows, self.row_err, self.val[k])
+            nat._lib.check(nat.lib.mbrl_keep_best(P(self.val[k].data_ptr()), 3, E, int(k), P(self.best_loss.data_ptr()),
+                                                  P(self.best_epoch.data_ptr()), P(self.stale.data_ptr()), self.table,
+                                                  self.count, nat._lib.stream_handle(self.dev)), "mbrl_keep_best")
+        else:
+            row_err = _eval_members_torch(self.members, self.ins, self.outs, self.rows)
+            state = (row_err.sum(1) / (row_err.shape[1] * self.state_dim)).sum(1)
+            self.val[k, :, 0] = state
+            self.val[k, :, 1] = state
+            self.val[k, :, 2] = 0
+            better = state < self.best_loss
+            self.best_loss = torch.where(better, state, self.best_loss)
+            self.best_epoch = torch.where(better, torch.full_like(self.best_epoch, k), self.best_epoch)
+            self.stale = torch.where(better, torch.zeros_like(self.stale), self.stale + 1)
+            with torch.no_grad():
+                for e in np.flatnonzero(better.cpu().numpy()):
+                    for p, snap in zip(self.params[e], self.snaps[e]):
+                        snap.copy_(p)
+        self.epochs = k + 1
+
+    def stop(self, k, patience, check_every):
+        if patience is None or (k + 1) % check_every != 0:
+            return False
+        return int(self.stale.min().item()) >= patience      # (the one host read a patience costs)
 
 
 class ModelWithReward(nn.Module):
