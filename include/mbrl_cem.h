@@ -885,6 +885,32 @@ int mbrl_eval_members(const mbrl_train_model* members, int32_t E, const mbrl_tra
                       const int64_t* rows, int64_t R, float* row_err, float* row_rew_err, float* loss_out,
                       mbrl_stream_t stream);
 
+/* ---- open-loop evaluation of ensemble members (added within ABI v13): the k-step error a planner's rollout
+ * meets. Members, data, rows and R as for mbrl_eval_members; the member's own prediction is fed back as the
+ * next state for horizon steps. With i = rows[r] and x_0 = states[i][0], for h = 0 .. horizon - 1:
+ *   (s^_{h+1}, r^_h) = the member's forward pass on (x_h, actions[i][h])   as mbrl_eval_members defines it
+ *   x_{h+1}          = s^_{h+1}       the state head's fp32 values, not renormalised and not clamped: the
+ *                                     stacked dataset holds next_states[i][h] and states[i][h + 1] as one
+ *                                     sample under one normalisation, so this is the identity in the space
+ *                                     the member is trained in. NaN and inf propagate down the row's chain.
+ *   row_err[e][r][h]     = sum_j (s^_{h+1,j} - next_states[i][h][j])^2     fp32, j ascending, no contraction
+ *   row_rew_err[e][r][h] = (r^_h - rewards[i][h])^2                        required iff reward_head, else NULL
+ *   pred_out[e][r][h][j] = s^_{h+1,j}                                      or NULL; every element is written
+ *   loss_out[e]          = mbrl_eval_members' loss_out over these row_err / row_rew_err, in its summation
+ *                          order, or NULL: open-loop and one-step losses share a scale, and mbrl_keep_best
+ *                          takes either.
+ * states[i][h] for h >= 1 is never read. At horizon 1 every output equals mbrl_eval_members', byte for byte,
+ * and step h of a longer call equals mbrl_eval_members on a horizon-1 dataset whose states are
+ * pred_out[e][r][h - 1]. The bytes of (e, r, h) depend on member e's parameters and dataset row rows[r]
+ * alone: not on E, the other members, R, r, the neighbouring rows (a non-finite neighbour included) or what
+ * the outputs held on entry. No workspace, no allocation, no synchronisation: stream-ordered and capturable.
+ * Two launches whatever E, R and horizon are (one with loss_out == NULL): 16 rows of one member per
+ * workgroup, which runs the horizon loop with the activations in LDS; no workgroup waits on another.
+ * Envelope, argument checks and error codes are mbrl_eval_members', all before any launch. */
+int mbrl_eval_members_open_loop(const mbrl_train_model* members, int32_t E, const mbrl_train_data* data,
+                                const int64_t* rows, int64_t R, float* row_err, float* row_rew_err,
+                                float* pred_out, float* loss_out, mbrl_stream_t stream);
+
 /* Keep-best snapshots: per member e, v = loss[e * loss_stride] (device) against best_loss[e] AS IT WAS ON
  * ENTRY. If v < best_loss[e] (a NaN is never better): best_loss[e] = v, best_epoch[e] = epoch,
  * stale[e] = 0, and each of the member's `count` tensors tensors[e * count + i] (host table [E][count]) is

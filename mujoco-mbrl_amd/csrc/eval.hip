@@ -19,6 +19,19 @@
 // Launch 2 (eval_loss_kernel, skipped without loss_out): one workgroup per member, the order documented
 // in the header.
 //
+// mbrl_eval_members_open_loop, launch 1 (eval_open_loop_kernel): grid (row tiles, members). A workgroup owns
+// EVAL_TM = 16 rows r of one member and runs the horizon loop itself: the same layer chain per step, in the
+// same two LDS buffers, and between two steps the seam, built in place in the buffer that holds the outputs
+// (it alternates with the parity of L): the predicted state stays where the output layer put it, columns
+// 0 .. s - 1, and every column from s to the end of layer 0's last 16-deep chunk is rewritten -- the next
+// step's actions, then zeros -- so that neither the reward head's output in column s nor an earlier layer's
+// hidden activations further right reach layer 0. The error lanes and the pred_out stores read the outputs
+// before a barrier, the rewrite follows it, and a second barrier stands before layer 0. The next actions are
+// loaded from global memory at the seam, not ahead of it: their latency is covered by the other workgroups
+// of the compute unit, not by this one's layers. Every output element is still one k-ordered fma chain over
+// its own row's inputs, so the bytes of a (member, row, step) depend on nothing else.
+// Launch 2: eval_loss_kernel on the open-loop row errors.
+//
 // mbrl_keep_best: copy launches that read loss and best_loss only, then the launch that updates
 // best_loss, best_epoch and stale; the stream orders them, so no copy sees an updated best_loss.
 #include <hip/hip_runtime.h>
@@ -117,6 +130,22 @@ __device__ __forceinline__ void eval_layer(const float* __restrict__ in, float* 
     }
 }
 
+// The member's forward pass on the 16 inputs in buf[cur] (s + a columns, zeros up to the next multiple of
+// 16): returns the buffer that holds (s^, r^) in columns 0 .. s (+ 1), zeros up to the next multiple of 16,
+// behind a barrier.
+__device__ __forceinline__ int eval_forward(const EvalLaunch& A, const EvalMember& M, float* const* buf, int cur) {
+    for (int l = 0; l < A.L; ++l) {
+        eval_layer<true>(buf[cur], buf[cur ^ 1], A.ld, M.w[l], M.b[l], A.W, nullptr, nullptr, 0,
+                         l == 0 ? A.s + A.a : A.W);
+        cur ^= 1;
+        __syncthreads();
+    }
+    eval_layer<false>(buf[cur], buf[cur ^ 1], A.ld, M.w[A.L], M.b[A.L], A.s, A.reward ? M.w[A.L + 1] : nullptr,
+                      A.reward ? M.b[A.L + 1] : nullptr, A.reward ? 1 : 0, A.W);
+    __syncthreads();
+    return cur ^ 1;
+}
+
 __global__ __launch_bounds__(64 * EVAL_WAVES) void eval_rows_kernel(const EvalLaunch A) {
     extern __shared__ __attribute__((aligned(16))) float eval_lds[];
     const int ld = A.ld, tid = threadIdx.x, e = blockIdx.y;
@@ -163,6 +192,58 @@ __global__ __launch_bounds__(64 * EVAL_WAVES) void eval_rows_kernel(const EvalLa
             const float d = y[A.s] - A.rewards[at];
             A.row_rew_err[(int64_t)e * A.P + p] = d * d;
         }
+    }
+}
+
+// Open loop: the tile's 16 rows of one member through all H steps, x_{h+1} = s^_{h+1} (see the top of the file).
+// A.P is R here, and row_err / row_rew_err / pred_out are [E][R][H](, [s]).
+__global__ __launch_bounds__(64 * EVAL_WAVES) void eval_open_loop_kernel(const EvalLaunch A, float* __restrict__ pred_out) {
+    extern __shared__ __attribute__((aligned(16))) float eval_lds[];
+    const int ld = A.ld, tid = threadIdx.x, e = blockIdx.y;
+    float* buf[2] = {eval_lds, eval_lds + EVAL_TM * ld};
+    const int64_t r0 = (int64_t)blockIdx.x * EVAL_TM, R = A.P;
+    const EvalMember& M = A.m[e];
+    const int K0 = A.s + A.a, K0p = (K0 + 15) & ~15, tail = K0p - A.s;
+    // x_0 = states[i][0]; rows past R run on zeros and store nothing
+    for (int idx = tid; idx < EVAL_TM * A.s; idx += 64 * EVAL_WAVES) {
+        const int row = idx / A.s, k = idx - row * A.s;
+        buf[0][row * ld + k] = r0 + row < R ? A.states[A.rows[r0 + row] * A.H * A.s + k] : 0.0f;
+    }
+    int cur = 0;
+    for (int h = 0; h < A.H; ++h) {
+        // columns s .. K0p - 1 of the input: step h's actions, then zeros (over the reward head's output and
+        // whatever an earlier layer left there)
+        for (int idx = tid; idx < EVAL_TM * tail; idx += 64 * EVAL_WAVES) {
+            const int row = idx / tail, k = idx - row * tail;
+            float v = 0.0f;
+            if (k < A.a && r0 + row < R) v = A.actions[(A.rows[r0 + row] * A.H + h) * A.a + k];
+            buf[cur][row * ld + A.s + k] = v;
+        }
+        __syncthreads();
+        cur = eval_forward(A, M, buf, cur);
+        if (tid < EVAL_TM && r0 + tid < R) {
+            const int64_t at = A.rows[r0 + tid] * A.H + h;
+            const int64_t o = ((int64_t)e * R + r0 + tid) * A.H + h;
+            const float* y = buf[cur] + tid * ld;
+            const float* target = A.next_states + at * A.s;
+            float sum = 0.0f;
+            for (int j = 0; j < A.s; ++j) {
+                const float d = y[j] - target[j];
+                sum = sum + d * d;                        // (-ffp-contract=off: a product, then a sum)
+            }
+            A.row_err[o] = sum;
+            if (A.reward) {
+                const float d = y[A.s] - A.rewards[at];
+                A.row_rew_err[o] = d * d;
+            }
+        }
+        if (pred_out) {
+            for (int idx = tid; idx < EVAL_TM * A.s; idx += 64 * EVAL_WAVES) {
+                const int row = idx / A.s, j = idx - row * A.s;
+                if (r0 + row < R) pred_out[(((int64_t)e * R + r0 + row) * A.H + h) * A.s + j] = buf[cur][row * ld + j];
+            }
+        }
+        __syncthreads();                                  // the outputs are read: the next step may overwrite column s
     }
 }
 
@@ -279,17 +360,10 @@ static hipError_t launch_keep_best_copies(const float* loss, int loss_stride, co
     return hipSuccess;
 }
 
-}  // namespace mbrl
-
-using namespace mbrl;
-
-// ---- ABI entries (include/mbrl_cem.h)
-extern "C" {
-
-int mbrl_eval_members(const mbrl_train_model* members, int32_t E, const mbrl_train_data* data,
-                      const int64_t* rows, int64_t R, float* row_err, float* row_rew_err, float* loss_out,
-                      mbrl_stream_t stream) {
-    const char* what = "eval_members";
+// The argument checks of mbrl_eval_members and mbrl_eval_members_open_loop (all before any launch) and the
+// launch arguments both share; A.P is left to the caller.
+static int eval_prepare(const char* what, const mbrl_train_model* members, int32_t E, const mbrl_train_data* data,
+                        const int64_t* rows, int64_t R, float* row_err, float* row_rew_err, EvalLaunch& A) {
     if (!members || !data || !rows || !row_err) return fail(MBRL_EINVAL, "%s: NULL members, data, rows or row_err", what);
     if (E < 1 || R < 1) return fail(MBRL_EINVAL, "%s: E = %d members, R = %lld rows", what, E, (long long)R);
     if (E > MBRL_TRAIN_MAX_MEMBERS)
@@ -325,7 +399,6 @@ int mbrl_eval_members(const mbrl_train_model* members, int32_t E, const mbrl_tra
         return fail(MBRL_EUNSUPPORTED, "%s: E * R * horizon = %d * %lld * %d is not below 2^31", what, E, (long long)R,
                     m0.horizon);
 
-    EvalLaunch A{};
     for (int e = 0; e < E; ++e)
         for (int l = 0; l < layers; ++l) {
             A.m[e].w[l] = members[e].weight[l];
@@ -338,21 +411,53 @@ int mbrl_eval_members(const mbrl_train_model* members, int32_t E, const mbrl_tra
     A.rows = rows;
     A.row_err = row_err;
     A.row_rew_err = row_rew_err;
-    A.P = R * m0.horizon;
     A.s = m0.state_dim; A.a = m0.action_dim; A.W = m0.hidden; A.L = m0.n_hidden; A.reward = m0.reward_head;
     A.H = m0.horizon;
     A.ld = eval_ld(A.s, A.a, A.W, A.reward);
+    return MBRL_OK;
+}
+
+// the row errors' launch (grid: row tiles x members, the two activation buffers in dynamic LDS), then the losses
+template <typename... Extra>
+static int eval_launch(const char* what, void (*kernel)(EvalLaunch, Extra...), const EvalLaunch& A, int32_t E,
+                       int64_t tile_items, int64_t R, float* loss_out, mbrl_stream_t stream, Extra... extra) {
     const size_t lds = (size_t)2 * EVAL_TM * A.ld * sizeof(float);
     const hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (int rc = hip_check(ensure_dynamic_lds(reinterpret_cast<const void*>(&eval_rows_kernel), 160 * 1024), what))
-        return rc;
-    const unsigned tiles = (unsigned)((A.P + EVAL_TM - 1) / EVAL_TM);
-    hipLaunchKernelGGL(eval_rows_kernel, dim3(tiles, E), dim3(64 * EVAL_WAVES), lds, st, A);
+    if (int rc = hip_check(ensure_dynamic_lds(reinterpret_cast<const void*>(kernel), 160 * 1024), what)) return rc;
+    const unsigned tiles = (unsigned)((tile_items + EVAL_TM - 1) / EVAL_TM);
+    hipLaunchKernelGGL(kernel, dim3(tiles, E), dim3(64 * EVAL_WAVES), lds, st, A, extra...);
     if (int rc = hip_check(hipGetLastError(), what)) return rc;
     if (!loss_out) return MBRL_OK;
-    hipLaunchKernelGGL(eval_loss_kernel, dim3(E), dim3(EVAL_LOSS_THREADS), 0, st, row_err, row_rew_err, loss_out, R,
+    hipLaunchKernelGGL(eval_loss_kernel, dim3(E), dim3(EVAL_LOSS_THREADS), 0, st, A.row_err, A.row_rew_err, loss_out, R,
                        A.H, A.s);
     return hip_check(hipGetLastError(), what);
+}
+
+}  // namespace mbrl
+
+using namespace mbrl;
+
+// ---- ABI entries (include/mbrl_cem.h)
+extern "C" {
+
+int mbrl_eval_members(const mbrl_train_model* members, int32_t E, const mbrl_train_data* data,
+                      const int64_t* rows, int64_t R, float* row_err, float* row_rew_err, float* loss_out,
+                      mbrl_stream_t stream) {
+    const char* what = "eval_members";
+    EvalLaunch A{};
+    if (int rc = eval_prepare(what, members, E, data, rows, R, row_err, row_rew_err, A)) return rc;
+    A.P = R * A.H;
+    return eval_launch(what, eval_rows_kernel, A, E, A.P, R, loss_out, stream);
+}
+
+int mbrl_eval_members_open_loop(const mbrl_train_model* members, int32_t E, const mbrl_train_data* data,
+                                const int64_t* rows, int64_t R, float* row_err, float* row_rew_err,
+                                float* pred_out, float* loss_out, mbrl_stream_t stream) {
+    const char* what = "eval_members_open_loop";
+    EvalLaunch A{};
+    if (int rc = eval_prepare(what, members, E, data, rows, R, row_err, row_rew_err, A)) return rc;
+    A.P = R;
+    return eval_launch(what, eval_open_loop_kernel, A, E, R, R, loss_out, stream, pred_out);
 }
 
 int mbrl_keep_best(const float* loss, int32_t loss_stride, int32_t E, int32_t epoch, float* best_loss,

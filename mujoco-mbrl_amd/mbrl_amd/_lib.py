@@ -76,7 +76,7 @@ EXPORTED = (
     "mbrl_mppi_plan_elite", "mbrl_mppi_plan_elite_batch",
     "mbrl_gd_grad",
     "mbrl_train_ensemble_workspace_bytes", "mbrl_train_grads_ensemble", "mbrl_train_epoch_ensemble",
-    "mbrl_eval_members", "mbrl_keep_best",
+    "mbrl_eval_members", "mbrl_keep_best", "mbrl_eval_members_open_loop",
 )
 
 
@@ -225,6 +225,8 @@ def load():
                                                 POINTER(AdamTensor), c_int32, POINTER(AdamHparams), P, P, P, P,
                                                 c_size_t, P]),
         "mbrl_eval_members": (c_int32, [POINTER(TrainModel), c_int32, POINTER(TrainData), P, c_int64, P, P, P, P]),
+        "mbrl_eval_members_open_loop": (c_int32, [POINTER(TrainModel), c_int32, POINTER(TrainData), P, c_int64, P, P, P, P,
+                                                  P]),
         "mbrl_keep_best": (c_int32, [P, c_int32, c_int32, c_int32, P, P, P, POINTER(CopyTensor), c_int32, P]),
         "mbrl_cem_plan": (c_int32, [POINTER(MlpShape), P, POINTER(Norm), POINTER(Cost), P, POINTER(CemParams),
                                     P, P, P, P, P, P, P, P, P, c_size_t, P]),

@@ -648,15 +648,23 @@ class EnsembleModel(DynamicsModel):
         self.train_iterations += 1
         return first
 
-    def evaluate_members(self, dataset, rows=None):
+    def evaluate_members(self, dataset, rows=None, open_loop=False, predictions=False):
         """Every member's error on rows `rows` of dataset.stacked() (default: all of them; indices may repeat):
         dict(loss [E], per_step [E, horizon], row_err [E, R, horizon]) on the ensemble's device, with
             row_err[e, r, h] = sum_j (member e's predicted next state - next_states[rows[r], h])_j ** 2,
             per_step[e, h]   = sum_r row_err[e, r, h] / (R * state_dim)    (MSELoss of step h),
             loss[e]          = sum_h per_step[e, h]: train_members' loss of a batch made of these rows.
-        On a GPU, when train_members' support test passes for every member, one mbrl_eval_members call
-        (csrc/eval.hip) with no host synchronisation -- pass `rows` as a device tensor to keep its upload out
-        as well; otherwise (CPU, `noise`, more than 8 members) the same definitions in torch."""
+        open_loop=False: the member predicts from the dataset's true states[rows[r], h] at every step (teacher
+        forcing). open_loop=True: from states[rows[r], 0] only, its own prediction being fed back as the
+        next state for the dataset's `horizon` steps, as a planner's rollout does (the stacked next_states[i, h]
+        and states[i, h + 1] are one sample under one normalisation, so the prediction is fed back as it
+        is); predictions=True (open loop only) adds pred [E, R, horizon, state_dim], the fed-back states.
+        On a GPU, when train_members' support test passes for every member, one mbrl_eval_members /
+        mbrl_eval_members_open_loop call (csrc/eval.hip) with no host synchronisation -- pass `rows` as a
+        device tensor to keep its upload out as well; otherwise (CPU, `noise`, more than 8 members) the same
+        definitions in torch."""
+        if predictions and not open_loop:
+            raise ValueError("evaluate_members returns predictions of an open-loop evaluation only (open_loop=True)")
         members = list(self.members)
         dev = _device_of(self)
         _, ins, outs = dataset.stacked(dev)
@@ -664,26 +672,45 @@ class EnsembleModel(DynamicsModel):
         R, H = int(rows.shape[0]), dataset.horizon
         if R < 1:
             raise ValueError("evaluate_members needs at least one row")
+        pred = None
         if _NativeEval.supported(members, dataset, ins, outs):
             with torch.cuda.device(dev):
                 row_err = torch.empty((len(members), R, H), dtype=torch.float32, device=dev)
                 loss3 = torch.empty((len(members), 3), dtype=torch.float32, device=dev)
-                _NativeEval(members, ins, outs, H).run(rows, row_err, loss3)
+                if open_loop:
+                    if predictions:
+                        pred = torch.empty((len(members), R, H, self.state_dim), dtype=torch.float32, device=dev)
+                    _NativeEval(members, ins, outs, H).run_open_loop(rows, row_err, loss3, pred)
+                else:
+                    _NativeEval(members, ins, outs, H).run(rows, row_err, loss3)
             loss = loss3[:, 0]
         else:
-            row_err = _eval_members_torch(members, ins, outs, rows)
+            if open_loop:
+                row_err, pred = _eval_members_open_loop_torch(members, ins, outs, rows)
+            else:
+                row_err = _eval_members_torch(members, ins, outs, rows)
             loss = None
         per_step = row_err.sum(1) / (R * self.state_dim)
-        return dict(loss=per_step.sum(1) if loss is None else loss, per_step=per_step, row_err=row_err)
+        out = dict(loss=per_step.sum(1) if loss is None else loss, per_step=per_step, row_err=row_err)
+        if predictions:
+            out["pred"] = pred
+        return out
 
     def fit_members(self, dataset, holdout, optimizers, batch_size=512, max_epochs=50, patience=None, check_every=1,
-                    restore_best=True, bootstrap=True, seed=0, criterion=None, writer=None):
+                    restore_best=True, bootstrap=True, seed=0, criterion=None, writer=None, holdout_loss="one_step"):
         """train_members with a held-out set: the same epochs (orders, shared launches and fallback rules
         are train_members'), and after each epoch every member's loss on all rows of `holdout` (a
-        TransitionsDataset of the same spec; evaluate_members' loss) and a snapshot of each member's
-        parameters whenever its loss is below all its earlier ones (a NaN never is). On the native path the
-        evaluation and the snapshots are two C calls enqueued on the training stream (mbrl_eval_members,
-        mbrl_keep_best); with patience=None the host never waits between epochs.
+        TransitionsDataset of the same dimensions and normalisation; evaluate_members' loss) and a snapshot
+        of each member's parameters whenever its loss is below all its earlier ones (a NaN never is). On the
+        native path the evaluation and the snapshots are two C calls enqueued on the training stream
+        (mbrl_eval_members or mbrl_eval_members_open_loop, mbrl_keep_best); with patience=None the host never
+        waits between epochs.
+
+        holdout_loss: "one_step" scores a member by evaluate_members(holdout), "open_loop" by
+        evaluate_members(holdout, open_loop=True): its own predictions fed back over the holdout's horizon,
+        which may be longer than the training dataset's (30 against 1, say: the planning horizon). Keep-best,
+        patience, restore_best, the report and elite(k) then act on that loss. Any other string is a
+        ValueError before any work.
 
         patience: after each epoch k with (k + 1) % check_every == 0 the host reads the members' `stale`
         counts (epochs since the member's best) and stops when every member's is >= patience
@@ -694,7 +721,9 @@ class EnsembleModel(DynamicsModel):
 
         Returns, and keeps as self.holdout_report, dict(val_loss [epochs_run, E], best_loss [E],
         best_epoch [E] (CPU tensors), epochs_run, native_epochs: the epochs that trained in the shared
-        launches, native_eval: whether the held-out losses came from mbrl_eval_members). Writer tags: train_members', and loss/holdout/member{e}/{iteration} per epoch."""
+        launches, native_eval: whether the held-out losses came from the C entry, holdout_loss). Writer tags: train_members', and loss/holdout/member{e}/{iteration} per epoch."""
+        if holdout_loss not in ("one_step", "open_loop"):
+            raise ValueError(f'fit_members: holdout_loss must be "one_step" or "open_loop", got {holdout_loss!r}')
         members = list(self.members)
         opts = [optimizers(m) for m in members] if callable(optimizers) else list(optimizers)
         if len(opts) != len(members):
@@ -706,7 +735,7 @@ class EnsembleModel(DynamicsModel):
         max_epochs = max(int(max_epochs), 0) if n > 0 else 0
         iteration = [m.train_iterations for m in members]
         with torch.cuda.device(dev) if dev.type == "cuda" else contextlib.nullcontext():
-            tracker = _Holdout(members, holdout, max_epochs)
+            tracker = _Holdout(members, holdout, max_epochs, open_loop=holdout_loss == "open_loop")
             stopped = []
 
             def after_epoch(k):
@@ -740,7 +769,8 @@ class EnsembleModel(DynamicsModel):
                             torch._foreach_copy_(params, snaps)
             val = tracker.val[:ran, :, 0].detach().cpu()
             report = dict(val_loss=val, best_loss=tracker.best_loss.detach().cpu(), best_epoch=best_epoch,
-                          epochs_run=ran, native_epochs=first, native_eval=tracker.native is not None)
+                          epochs_run=ran, native_epochs=first, native_eval=tracker.native is not None,
+                          holdout_loss=holdout_loss)
         if writer is not None:
             for k, row in enumerate(val.tolist()):
                 for e, v in enumerate(row):
@@ -940,8 +970,26 @@ def _eval_members_torch(members, ins, outs, rows):
         return torch.stack([((m._forward(x) - target) ** 2).sum(1).reshape(R, H) for m in members])
 
 
+def _eval_members_open_loop_torch(members, ins, outs, rows):
+    """mbrl_eval_members_open_loop's definitions in torch: from states[rows, 0] every member's own _forward is
+    fed back as the next state, horizon times. Returns (row_err [E, R, horizon], pred [E, R, horizon, s])."""
+    (states, actions), (_, next_states) = ins, outs
+    with torch.no_grad():
+        st, ac, ns = (x.index_select(0, rows) for x in (states, actions, next_states))
+        errs, preds = [], []
+        for m in members:
+            x, steps = st[:, 0], []
+            for h in range(st.shape[1]):
+                x = m._forward(torch.cat([x, ac[:, h]], dim=1))
+                steps.append(x)
+            pred = torch.stack(steps, dim=1)
+            preds.append(pred)
+            errs.append(((pred - ns) ** 2).sum(2))
+        return torch.stack(errs), torch.stack(preds)
+
+
 class _NativeEval:
-    """mbrl_eval_members for E supported members on one dataset: the members' live weights and biases (no
+    """mbrl_eval_members / mbrl_eval_members_open_loop for E supported members on one dataset: the members' live weights and biases (no
     gradients), the stacked transitions, no workspace."""
 
     def __init__(self, members, ins, outs, horizon):
@@ -983,6 +1031,17 @@ class _NativeEval:
                                                    int(rows.shape[0]), P(row_err.data_ptr()), None, P(loss.data_ptr()),
                                                    self._lib.stream_handle(self.dev)), "mbrl_eval_members")
 
+    def run_open_loop(self, rows, row_err, loss, pred=None):
+        """The same with the members' predictions fed back (mbrl_eval_members_open_loop); pred: [E, R, horizon, s]
+        or None."""
+        if [t.data_ptr() for params in self.params for t in params] != self.ptrs:
+            raise RuntimeError("model parameters moved during evaluation")
+        P = ctypes.c_void_p
+        self._lib.check(self.lib.mbrl_eval_members_open_loop(
+            self.models, self.E, ctypes.byref(self.data), P(rows.data_ptr()), int(rows.shape[0]), P(row_err.data_ptr()),
+            None, None if pred is None else P(pred.data_ptr()), P(loss.data_ptr()), self._lib.stream_handle(self.dev)),
+            "mbrl_eval_members_open_loop")
+
 
 def _holdout_rows(dataset, dev, rows):
     if rows is None:
@@ -995,8 +1054,8 @@ class _Holdout:
     snapshot of each member's parameters at its best epoch. On the native path (mbrl_eval_members and
     mbrl_keep_best on the training stream) the host reads nothing unless a patience asks for `stale`."""
 
-    def __init__(self, members, holdout, max_epochs):
-        self.members = members
+    def __init__(self, members, holdout, max_epochs, open_loop=False):
+        self.members, self.open_loop = members, open_loop
         dev = self.dev = _device_of(members[0])
         _, self.ins, self.outs = holdout.stacked(dev)
         self.rows = _holdout_rows(holdout, dev, None)
@@ -1030,12 +1089,18 @@ class _Holdout:
         E = len(self.members)
         if self.native is not None:
             nat, P = self.native, ctypes.c_void_p
-            nat.run(self.rows, self.row_err, self.val[k])
+            if self.open_loop:
+                nat.run_open_loop(self.rows, self.row_err, self.val[k])
+            else:
+                nat.run(self.rows, self.row_err, self.val[k])
             nat._lib.check(nat.lib.mbrl_keep_best(P(self.val[k].data_ptr()), 3, E, int(k), P(self.best_loss.data_ptr()),
                                                   P(self.best_epoch.data_ptr()), P(self.stale.data_ptr()), self.table,
                                                   self.count, nat._lib.stream_handle(self.dev)), "mbrl_keep_best")
         else:
-            row_err = _eval_members_torch(self.members, self.ins, self.outs, self.rows)
+            if self.open_loop:
+                row_err = _eval_members_open_loop_torch(self.members, self.ins, self.outs, self.rows)[0]
+            else:
+                row_err = _eval_members_torch(self.members, self.ins, self.outs, self.rows)
             state = (row_err.sum(1) / (row_err.shape[1] * self.state_dim)).sum(1)
             self.val[k, :, 0] = state
             self.val[k, :, 1] = state
