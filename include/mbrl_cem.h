@@ -44,7 +44,9 @@ extern "C" {
  * (mbrl_cem_rh_batch_workspace_bytes, mbrl_cem_plan_rh_batch) after it, then batched MPPI
  * (mbrl_mppi_update_batch, mbrl_mppi_batch_workspace_bytes, mbrl_mppi_plan_batch), then MPPI over the K best
  * (mbrl_mppi_elite_params, mbrl_mppi_update_elite, mbrl_mppi_update_elite_batch,
- * mbrl_mppi_elite_workspace_bytes, mbrl_mppi_plan_elite, mbrl_mppi_plan_elite_batch). */
+ * mbrl_mppi_elite_workspace_bytes, mbrl_mppi_plan_elite, mbrl_mppi_plan_elite_batch), and training on the
+ * open-loop loss (mbrl_train_open_loop_workspace_bytes, mbrl_train_grads_open_loop,
+ * mbrl_train_epoch_open_loop). */
 #define MBRL_ABI_VERSION 13
 
 typedef struct ihipStream_t* mbrl_stream_t; /* == hipStream_t */
@@ -910,6 +912,56 @@ int mbrl_eval_members(const mbrl_train_model* members, int32_t E, const mbrl_tra
 int mbrl_eval_members_open_loop(const mbrl_train_model* members, int32_t E, const mbrl_train_data* data,
                                 const int64_t* rows, int64_t R, float* row_err, float* row_rew_err,
                                 float* pred_out, float* loss_out, mbrl_stream_t stream);
+
+/* ---- training on the open-loop loss (added within ABI v13, additively: no existing entry, struct or option
+ * changes, no new option id): the training counterpart of mbrl_eval_members_open_loop, backpropagation through
+ * the fed-back predictions. Per member e, over the rows i = batch_idx[e][b], b < B = batch, with
+ * H = members[0].horizon and x_0 = states[i][0], for h = 0 .. H - 1:
+ *   (s^_{h+1}, r^_h) = the member's forward pass on (x_h, actions[i][h])    exactly mbrl_eval_members_open_loop's
+ *   x_{h+1}          = s^_{h+1}                                             not detached, clamped or renormalised
+ *   loss = sum_h [ sum_b sum_j (s^_{h+1,j} - next_states[i][h][j])^2 / (B s) + sum_b (r^_h - rewards[i][h])^2 / B ]
+ * -- the scale of mbrl_train_grads (2 / (B s) and 2 / B on the residuals) and of mbrl_eval_members' loss_out.
+ * states[i][h] for h >= 1 is never read. The gradient is the full derivative: the residual of step h reaches
+ * the parameters through every earlier step's prediction as well. At horizon 1 it is
+ * mbrl_train_grads_ensemble's gradient to rounding. The *_grad arrays are overwritten.
+ * Members, data, batch_idx [E][batch], orders [E][rows], tensors, step_sizes, bc2_sqrt, loss_out [E][3] and
+ * losses [batches][E][3] as for mbrl_train_grads_ensemble / mbrl_train_epoch_ensemble; E = 1 is the single
+ * model. loss_out[e] equals mbrl_eval_members_open_loop's loss_out[e] on rows = batch_idx[e], R = batch, byte
+ * for byte. Member e's gradients and losses depend, byte for byte, on member e's parameters and rows alone --
+ * not on E or the other members (a non-finite one included) -- and two calls on the same inputs return the same
+ * bytes: no floating-point atomics, every output element one ordered chain. Summation orders: a weight
+ * gradient sums the batch * H positions p = h * batch + b in the order of mbrl_train_grads' weight-gradient
+ * product over K = batch * H rows (contiguous K ranges per wave, the waves' partials added in wave order: a
+ * function of batch * H alone); a bias gradient adds, per 16-row tile of the batch, the steps h descending, each
+ * step's valid rows ascending, and then the tiles ascending.
+ * ws: the workspace, ws_bytes >= mbrl_train_open_loop_workspace_bytes(members, E, batch) (0 for a bad shape),
+ * 16-byte aligned; it may hold any bytes on entry and needs no zeroing (tests/test_gpu_train_open_loop.py fills it
+ * with NaN and with 0xFF bytes). Stream-ordered and capturable: no allocation, no
+ * synchronisation, and no workgroup waits on another -- every hand-off is a kernel boundary.
+ * Launches per batch, whatever E, batch and horizon are: n_hidden + 4 in mbrl_train_grads_open_loop (forward,
+ * backward through time, n_hidden + 1 weight-gradient launches, the loss; one fewer with loss_out == NULL) and
+ * n_hidden + 5 in mbrl_train_epoch_open_loop (the Adam launch over all E * count tensors, 64 tensors per launch;
+ * more take further launches).
+ * Envelope: mbrl_eval_members_open_loop's (state_dim, state_dim + action_dim and hidden <= MBRL_EVAL_MAX_DIM,
+ * n_hidden <= MBRL_TRAIN_MAX_LAYERS - 2, action_dim = 0 with NULL actions, parameters and gradients at any
+ * 4-byte alignment) less what the backward kernel's LDS (160 KiB) cannot hold: with up16(x) = x rounded up to a
+ * multiple of 16, J = state_dim + reward_head,
+ *   ld = up16(max(hidden, state_dim + action_dim, J)) + 4,   wacc = up16(max(hidden, J)),
+ *   32 ld + (n_hidden + 1) wacc <= 40960 floats
+ * (hidden = 1024 with state_dim + action_dim <= 1024: n_hidden <= 6; hidden <= 880: every n_hidden); beyond it
+ * MBRL_EUNSUPPORTED. Before any launch: the argument checks and error codes of mbrl_train_grads_ensemble /
+ * mbrl_train_epoch_ensemble (MBRL_EINVAL for E < 1, shapes that differ, NULL arguments, a pointer bound twice
+ * or a misaligned workspace; MBRL_EUNSUPPORTED for E > MBRL_TRAIN_MAX_MEMBERS or E * batch * horizon >= 2^31;
+ * MBRL_EWORKSPACE for a workspace that is too small). */
+size_t mbrl_train_open_loop_workspace_bytes(const mbrl_train_model* members, int32_t E, int32_t batch);
+int mbrl_train_grads_open_loop(const mbrl_train_model* members, int32_t E, const mbrl_train_data* data,
+                               const int64_t* batch_idx, int32_t batch, float* loss_out, void* ws,
+                               size_t ws_bytes, mbrl_stream_t stream);
+int mbrl_train_epoch_open_loop(const mbrl_train_model* members, int32_t E, const mbrl_train_data* data,
+                               const int64_t* orders, int64_t rows, int32_t batch_size, const mbrl_adam_tensor* tensors,
+                               int32_t count, const mbrl_adam_hparams* hparams, const float* step_sizes,
+                               const float* bc2_sqrt, float* losses, void* ws, size_t ws_bytes,
+                               mbrl_stream_t stream);
 
 /* Keep-best snapshots: per member e, v = loss[e * loss_stride] (device) against best_loss[e] AS IT WAS ON
  * ENTRY. If v < best_loss[e] (a NaN is never better): best_loss[e] = v, best_epoch[e] = epoch,

@@ -622,6 +622,13 @@ hipError_t launch_train_grads(const TrainShape& t, const TrainTensors& w, const 
                               const mbrl_adam_tensor* prior = nullptr, int prior_n = 0,
                               mbrl_adam_tensor* pending = nullptr, int* pending_n = nullptr,
                               const TrainGather* gather = nullptr, const TrainEnsemble* ens = nullptr);
+// train_open_loop.hip's weight-gradient launches (train.hip): layer `layer`'s dW = g^T x over K rows and db from
+// `colsum` [colsum_tiles][n_out], member e's g, x and colsum e * ens.ws_stride floats on, into members[e]'s
+// gradient buffers; and the ensemble epochs' Adam launch (64 tensors per launch).
+hipError_t launch_train_wgrads(const TrainShape& t, int layer, const float* g, const float* x, const float* colsum,
+                               int colsum_tiles, int K, const TrainEnsemble& ens, hipStream_t stream);
+hipError_t launch_adam_step_ensemble(const mbrl_adam_tensor* tensors, int count, const mbrl_adam_hparams& hp,
+                                     int arith, hipStream_t stream);
 
 // ---- cooperative single-candidate kernels (traj.hip, gd.hip): the dot of one 16-row slice, one row
 // per half-wave (32 lanes), and its reduction

@@ -2144,6 +2144,42 @@ hipError_t launch_train_grads(const TrainShape& t, const TrainTensors& w, const 
     return hipSuccess;
 }
 
+// One layer's weight and bias gradient for every member of an ensemble, from row-major deltas g [K][n_out] and
+// layer inputs x [K][n_in] in the members' workspaces (member e's lie e * ens.ws_stride floats on): the EPI_GRAD
+// product launch_train_grads runs for layer 0, dW = g^T x over K rows with the K split over the launch's waves
+// (launch_waves: a function of K alone), db[m] = the ordered sum of colsum[0 .. colsum_tiles)[m]. The output
+// layer (layer == t.L) with a reward head splits its rows between the two heads' gradient buffers.
+hipError_t launch_train_wgrads(const TrainShape& t, int layer, const float* g, const float* x, const float* colsum,
+                               int colsum_tiles, int K, const TrainEnsemble& ens, hipStream_t stream) {
+    const bool out_layer = layer == t.L;
+    const int J = t.s + (t.reward ? 1 : 0), n_out = out_layer ? J : t.W, n_in = layer == 0 ? t.s + t.a : t.W;
+    const mbrl_train_model& m0 = ens.members[0];
+    GemmLaunch G{};
+    G.H = t.H; G.s = t.s; G.a = t.a;
+    G.slot = -1;
+    G.nd = 1;
+    GemmDesc& D = G.d[0];
+    D.A = transposed(g, nullptr, 0, n_out, n_out, -1);
+    D.B = transposed(x, nullptr, 0, n_in, n_in, -1);
+    Output& O = D.out;
+    O.mode = EPI_GRAD; O.ldc = n_in; O.colsum_in = colsum; O.colsum_tiles = colsum_tiles;
+    if (out_layer) {
+        O.c0 = m0.weight_grad[t.L]; O.c1 = t.reward ? m0.weight_grad[t.L + 1] : m0.weight_grad[t.L];
+        O.split = t.reward ? t.s : J;
+        O.g0 = m0.bias_grad[t.L]; O.g1 = t.reward ? m0.bias_grad[t.L + 1] : m0.bias_grad[t.L];
+    } else {
+        O.c0 = O.c1 = m0.weight_grad[layer]; O.split = n_out;
+        O.g0 = O.g1 = m0.bias_grad[layer];
+    }
+    finish(D, n_out, n_in, K);
+    return launch_gemm_any<OP_TRANS, OP_TRANS>(G, false, stream, &ens, t, layer);
+}
+
+hipError_t launch_adam_step_ensemble(const mbrl_adam_tensor* tensors, int count, const mbrl_adam_hparams& hp,
+                                     int arith, hipStream_t stream) {
+    return launch_adam_step_cap<ADAM_ENS_TENSORS>(tensors, count, hp, arith, stream);
+}
+
 }  // namespace mbrl
 
 #ifdef MBRL_STAMPS

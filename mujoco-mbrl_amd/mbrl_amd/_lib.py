@@ -77,6 +77,7 @@ EXPORTED = (
     "mbrl_gd_grad",
     "mbrl_train_ensemble_workspace_bytes", "mbrl_train_grads_ensemble", "mbrl_train_epoch_ensemble",
     "mbrl_eval_members", "mbrl_keep_best", "mbrl_eval_members_open_loop",
+    "mbrl_train_open_loop_workspace_bytes", "mbrl_train_grads_open_loop", "mbrl_train_epoch_open_loop",
 )
 
 
@@ -224,6 +225,12 @@ def load():
         "mbrl_train_epoch_ensemble": (c_int32, [POINTER(TrainModel), c_int32, POINTER(TrainData), P, c_int64, c_int32,
                                                 POINTER(AdamTensor), c_int32, POINTER(AdamHparams), P, P, P, P,
                                                 c_size_t, P]),
+        "mbrl_train_open_loop_workspace_bytes": (c_size_t, [POINTER(TrainModel), c_int32, c_int32]),
+        "mbrl_train_grads_open_loop": (c_int32, [POINTER(TrainModel), c_int32, POINTER(TrainData), P, c_int32, P, P,
+                                                 c_size_t, P]),
+        "mbrl_train_epoch_open_loop": (c_int32, [POINTER(TrainModel), c_int32, POINTER(TrainData), P, c_int64, c_int32,
+                                                 POINTER(AdamTensor), c_int32, POINTER(AdamHparams), P, P, P, P,
+                                                 c_size_t, P]),
         "mbrl_eval_members": (c_int32, [POINTER(TrainModel), c_int32, POINTER(TrainData), P, c_int64, P, P, P, P]),
         "mbrl_eval_members_open_loop": (c_int32, [POINTER(TrainModel), c_int32, POINTER(TrainData), P, c_int64, P, P, P, P,
                                                   P]),

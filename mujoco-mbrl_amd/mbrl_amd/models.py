@@ -599,7 +599,7 @@ class EnsembleModel(DynamicsModel):
         return torch.stack([m._forward(x) for m in self.members]).mean(0)
 
     def train_members(self, dataset, optimizers, batch_size=512, num_epochs=50, bootstrap=True, seed=0,
-                      criterion=None, writer=None):
+                      criterion=None, writer=None, loss="one_step"):
         """Train every member on its own view of `dataset`: the bootstrap training a PETS-style
         ensemble's diversity comes from (train_model, inherited, fits the member MEAN with one optimizer
         and one data order, so every member sees the same signal).
@@ -621,7 +621,19 @@ class EnsembleModel(DynamicsModel):
         orders -- as do more than 8 members (MBRL_TRAIN_MAX_MEMBERS) or a member listed twice. Writer
         tags: loss/state/member{e}/{iteration}. train_iterations counts one per call on the ensemble and
         on each member. Returns the number of epochs that ran in the shared launches (0: member by
-        member)."""
+        member).
+
+        loss: "one_step" (the default) is the teacher-forced loss above. "open_loop" trains on the loss
+        evaluate_members(open_loop=True) measures: from states[i, 0] the member's own prediction is fed back
+        as the next state for the dataset's `horizon` steps, the criterion of every step's prediction against
+        next_states[i, h] is summed, and the gradient runs through the fed-back predictions (backpropagation
+        through time); states[i, h] for h >= 1 is not read. Orders, hook, writer tags and the return value are
+        the same; the shared launches are one mbrl_train_epoch_open_loop call per epoch
+        (csrc/train_open_loop.hip) under the same support test, and the fallback feeds m._forward its own
+        output in torch. Any other string is a ValueError before any work."""
+        if loss not in ("one_step", "open_loop"):
+            raise ValueError(f'train_members: loss must be "one_step" or "open_loop", got {loss!r}')
+        open_loop = loss == "open_loop"
         members = list(self.members)
         opts = [optimizers(m) for m in members] if callable(optimizers) else list(optimizers)
         if len(opts) != len(members):
@@ -632,8 +644,16 @@ class EnsembleModel(DynamicsModel):
         if n > 0 and num_epochs > 0 and _device_of(self).type == "cuda":
             with torch.cuda.device(_device_of(self)):
                 first = _train_members_native(self, members, opts, dataset, batch_size, num_epochs, bootstrap, seed,
-                                              criterion, writer)
-        if first < num_epochs or n == 0 or num_epochs <= 0:
+                                              criterion, writer, open_loop=open_loop)
+        if open_loop and n > 0 and first < num_epochs:
+            for e, (m, opt) in enumerate(zip(members, opts)):
+                if first > 0:
+                    m.train_iterations -= 1
+                _train_open_loop_torch(m, e, dataset, opt, batch_size, num_epochs - first, criterion, writer,
+                                       lambda k, e=e: member_order(seed, e, first + k, n, bootstrap),
+                                       first * ((n + batch_size - 1) // batch_size))
+                m.train_iterations += 1
+        elif first < num_epochs or n == 0 or num_epochs <= 0:
             for e, (m, opt) in enumerate(zip(members, opts)):
                 def step_loss(inp, out, m=m):
                     (states, actions), (_, next_states) = inp, out
@@ -697,7 +717,8 @@ class EnsembleModel(DynamicsModel):
         return out
 
     def fit_members(self, dataset, holdout, optimizers, batch_size=512, max_epochs=50, patience=None, check_every=1,
-                    restore_best=True, bootstrap=True, seed=0, criterion=None, writer=None, holdout_loss="one_step"):
+                    restore_best=True, bootstrap=True, seed=0, criterion=None, writer=None, holdout_loss="one_step",
+                    train_loss="one_step"):
         """train_members with a held-out set: the same epochs (orders, shared launches and fallback rules
         are train_members'), and after each epoch every member's loss on all rows of `holdout` (a
         TransitionsDataset of the same dimensions and normalisation; evaluate_members' loss) and a snapshot
@@ -712,6 +733,10 @@ class EnsembleModel(DynamicsModel):
         patience, restore_best, the report and elite(k) then act on that loss. Any other string is a
         ValueError before any work.
 
+        train_loss: train_members' `loss` for the epochs: "one_step" or "open_loop" (with
+        holdout_loss="open_loop" the members are trained on, and picked by, the loss a planner's rollout
+        meets). Any other string is a ValueError before any work.
+
         patience: after each epoch k with (k + 1) % check_every == 0 the host reads the members' `stale`
         counts (epochs since the member's best) and stops when every member's is >= patience
         (tests/holdout_reference.py restates the rule in NumPy). restore_best: at the end each member's parameters become its
@@ -724,6 +749,9 @@ class EnsembleModel(DynamicsModel):
         launches, native_eval: whether the held-out losses came from the C entry, holdout_loss). Writer tags: train_members', and loss/holdout/member{e}/{iteration} per epoch."""
         if holdout_loss not in ("one_step", "open_loop"):
             raise ValueError(f'fit_members: holdout_loss must be "one_step" or "open_loop", got {holdout_loss!r}')
+        if train_loss not in ("one_step", "open_loop"):
+            raise ValueError(f'fit_members: train_loss must be "one_step" or "open_loop", got {train_loss!r}')
+        open_loop = train_loss == "open_loop"
         members = list(self.members)
         opts = [optimizers(m) for m in members] if callable(optimizers) else list(optimizers)
         if len(opts) != len(members):
@@ -746,7 +774,7 @@ class EnsembleModel(DynamicsModel):
             first = 0
             if max_epochs > 0 and dev.type == "cuda":
                 first = _train_members_native(self, members, opts, dataset, batch_size, max_epochs, bootstrap, seed,
-                                              criterion, writer, after_epoch=after_epoch)
+                                              criterion, writer, after_epoch=after_epoch, open_loop=open_loop)
             batches = (n + batch_size - 1) // max(batch_size, 1)
             for k in range(tracker.epochs, 0 if stopped else max_epochs):
                 for e, (m, opt) in enumerate(zip(members, opts)):
@@ -755,6 +783,10 @@ class EnsembleModel(DynamicsModel):
                         return [criterion(m.forward(states, actions, normalize_action=None, normalize_state=None,
                                                     unnormalize_state=None), next_states)]
                     m.train_iterations = iteration[e]         # (one call's worth of epochs: one iteration)
+                    if open_loop:
+                        _train_open_loop_torch(m, e, dataset, opt, batch_size, 1, criterion, writer,
+                                               lambda _, e=e, k=k: member_order(seed, e, k, n, bootstrap), k * batches)
+                        continue
                     _train_loop(m, dataset, opt, batch_size, 1, step_loss, writer, [f"loss/state/member{e}/{{}}"],
                                 criterion, order_fn=lambda _, e=e, k=k: member_order(seed, e, k, n, bootstrap),
                                 iter0=k * batches)
@@ -811,6 +843,8 @@ class _NativeEnsemble:
     """mbrl_train_epoch_ensemble for E supported members: per member the gradient buffers and
     mbrl_train_model of _NativeGrads, one dataset, one workspace of E member slices."""
 
+    WORKSPACE, EPOCH = "mbrl_train_ensemble_workspace_bytes", "mbrl_train_epoch_ensemble"
+
     def __init__(self, members, ins, outs, horizon, batch_size):
         from . import _lib
         self._lib, self.lib = _lib, _native_lib()
@@ -836,9 +870,9 @@ class _NativeEnsemble:
         d = self.data
         d.states, d.actions, d.next_states, d.rewards = [x.data_ptr() for x in self.keep]
         d.transitions = states.shape[0]
-        need = self.lib.mbrl_train_ensemble_workspace_bytes(self.models, self.E, int(batch_size))
+        need = getattr(self.lib, self.WORKSPACE)(self.models, self.E, int(batch_size))
         if need == 0:
-            _lib.check(-1, "mbrl_train_ensemble_workspace_bytes")
+            _lib.check(-1, self.WORKSPACE)
         self.ws = torch.empty(need, dtype=torch.uint8, device=self.dev)
         self.ptrs = [t.data_ptr() for params in self.params for t in params]
 
@@ -846,7 +880,7 @@ class _NativeEnsemble:
     def cached(cls, owner, members, ins, outs, horizon, batch_size):
         """The object of the ensemble's previous train_members call while nothing it binds has changed
         (_NativeGrads.cached's rule): a call then allocates no gradients, workspace or tables."""
-        key = (str(_device_of(members[0])), int(horizon), int(batch_size), id(_LIB_OVERRIDE),
+        key = (cls.EPOCH, str(_device_of(members[0])), int(horizon), int(batch_size), id(_LIB_OVERRIDE),
                tuple(t.data_ptr() for m in members for lin in m.linears() for t in (lin.weight, lin.bias)),
                tuple((x.data_ptr(), tuple(x.shape), x.is_contiguous()) for x in (*ins, *outs)))
         hit = _NATIVE_ENS_CACHE.get(owner)
@@ -889,18 +923,52 @@ class _NativeEnsemble:
         bc = np.stack([np.ctypeslib.as_array(pl[3]).reshape(steps, count) for pl in plans], axis=1)
         ss, bc = np.ascontiguousarray(ss, np.float32), np.ascontiguousarray(bc, np.float32)
         losses = torch.empty((steps, self.E, 3), dtype=torch.float32, device=self.dev)
-        self._lib.check(self.lib.mbrl_train_epoch_ensemble(
+        self._lib.check(getattr(self.lib, self.EPOCH)(
             self.models, self.E, ctypes.byref(self.data), ctypes.c_void_p(orders.data_ptr()), int(rows),
             int(batch_size), table, count, ctypes.byref(hp), ctypes.c_void_p(ss.ctypes.data),
             ctypes.c_void_p(bc.ctypes.data), ctypes.c_void_p(losses.data_ptr()), ctypes.c_void_p(self.ws.data_ptr()),
-            self.ws.numel(), self._lib.stream_handle(self.dev)), "mbrl_train_epoch_ensemble")
+            self.ws.numel(), self._lib.stream_handle(self.dev)), self.EPOCH)
         for adam, params in zip(adams, self.params):
             adam.epoch_done(params)
         return losses
 
 
+class _NativeEnsembleOpenLoop(_NativeEnsemble):
+    """mbrl_train_epoch_open_loop: the same members, tables and orders, the open-loop loss (csrc/train_open_loop.hip)."""
+
+    WORKSPACE, EPOCH = "mbrl_train_open_loop_workspace_bytes", "mbrl_train_epoch_open_loop"
+
+
+def _train_open_loop_torch(m, e, dataset, opt, batch_size, num_epochs, criterion, writer, order_fn, iter0):
+    """train_members(loss="open_loop") for one member in torch: per batch the criterion of every step's prediction
+    against next_states[i, h], summed, with m._forward fed its own output from states[i, 0] on; autograd runs
+    through the fed-back predictions. A plain Adam steps through mbrl_adam_step on a GPU (optim.AdamStep)."""
+    dev = _device_of(m)
+    _, ins, outs = dataset.stacked(dev)
+    (states, actions), (_, next_states) = ins, outs
+    fast = AdamStep.maybe(opt) if dev.type == "cuda" else None
+    it = iter0
+    with torch.cuda.device(dev) if dev.type == "cuda" else contextlib.nullcontext():
+        for k in range(num_epochs):
+            order = torch.from_numpy(order_fn(k)).to(dev)
+            for i in range(0, int(order.shape[0]), batch_size):
+                idx = order[i:i + batch_size]
+                opt.zero_grad()
+                x, loss = states.index_select(0, idx)[:, 0], 0
+                ac, ns = actions.index_select(0, idx), next_states.index_select(0, idx)
+                for h in range(dataset.horizon):
+                    x = m._forward(torch.cat([x, ac[:, h]], dim=1))
+                    loss = loss + criterion(x, ns[:, h])
+                loss.backward()
+                if fast is None or not fast.step():
+                    opt.step()
+                it += 1
+                if writer is not None:
+                    writer.add_scalar(f"loss/state/member{e}/{m.train_iterations}", loss, it)
+
+
 def _train_members_native(owner, members, opts, dataset, batch_size, num_epochs, bootstrap, seed, criterion, writer,
-                          after_epoch=None):
+                          after_epoch=None, open_loop=False):
     """The epochs of train_members the shared launches can take, from the first: returns how many ran
     (0: not supported here; the caller trains the rest member by member). Orders are staged as
     _train_loop_on stages them: epoch k + 1's rows are drawn into a pinned ring row while epoch k
@@ -918,7 +986,8 @@ def _train_members_native(owner, members, opts, dataset, batch_size, num_epochs,
     if any(a is None for a in adams):
         return 0
     n = dataset.num_transitions()
-    native = _NativeEnsemble.cached(owner, members, ins, outs, dataset.horizon, batch_size)
+    native = (_NativeEnsembleOpenLoop if open_loop else _NativeEnsemble).cached(owner, members, ins, outs,
+                                                                                dataset.horizon, batch_size)
     ring = _order_ring(dev, E * n)
     main = torch.cuda.current_stream(dev)
 
