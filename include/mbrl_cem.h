@@ -46,7 +46,9 @@ extern "C" {
  * (mbrl_mppi_elite_params, mbrl_mppi_update_elite, mbrl_mppi_update_elite_batch,
  * mbrl_mppi_elite_workspace_bytes, mbrl_mppi_plan_elite, mbrl_mppi_plan_elite_batch), and training on the
  * open-loop loss (mbrl_train_open_loop_workspace_bytes, mbrl_train_grads_open_loop,
- * mbrl_train_epoch_open_loop). */
+ * mbrl_train_epoch_open_loop), and global-norm gradient clipping for the ensemble epochs (mbrl_grad_clip,
+ * mbrl_grad_clip_workspace_bytes, mbrl_grad_norm, mbrl_adam_step_clipped, mbrl_train_epoch_ensemble_clipped,
+ * mbrl_train_epoch_open_loop_clipped). */
 #define MBRL_ABI_VERSION 13
 
 typedef struct ihipStream_t* mbrl_stream_t; /* == hipStream_t */
@@ -962,6 +964,72 @@ int mbrl_train_epoch_open_loop(const mbrl_train_model* members, int32_t E, const
                                int32_t count, const mbrl_adam_hparams* hparams, const float* step_sizes,
                                const float* bc2_sqrt, float* losses, void* ws, size_t ws_bytes,
                                mbrl_stream_t stream);
+
+/* ---- global-norm gradient clipping for the ensemble epochs (added within ABI v13, additively: no existing entry,
+ * struct, option or version number changes): torch.nn.utils.clip_grad_norm_(member.parameters(), max_norm) (L2,
+ * error_if_nonfinite = False) between backward() and Adam.step(), per member e and per batch, and a record of the
+ * pre-clip norms. fp32, round to nearest, no contraction. tensors: [E][count] host, member e's `count` gradient
+ * tensors (E <= MBRL_TRAIN_MAX_MEMBERS).
+ * Sum of squares of member e, in one order that depends on its tensors' numels alone -- not on E, the member's
+ * position, the other members or pointer alignment:
+ *   - tensor i is cut into chunks of 1024 consecutive elements, the last one padded with zeros that take part as
+ *     zeros; a tensor with numel == 0 has no chunk;
+ *   - in a chunk, lane t of 256 forms ((g[4t]^2 + g[4t+1]^2) + g[4t+2]^2) + g[4t+3]^2, each square rounded before it
+ *     is added, and the 256 lane values meet in the pairwise tree v[t] += v[t + d], d = 128, 64, .. 1;
+ *   - the member's P chunk partials lie end to end, tensor ascending, chunk ascending, and are reduced by
+ *     mbrl_eval_members' rule: lane t of 1024 adds partials t, t + 1024, .. ascending, then the pairwise tree
+ *     d = 512, .. 1.
+ *   norm = sqrtf(sum) correctly rounded,  q = max_norm / (norm + 1e-6f),  coef = q > 1 ? 1 : q  (a NaN q stays NaN,
+ *   as under torch's clamp(max = 1)).
+ * So a norm within max_norm gives coef == 1.0f exactly, max_norm = +inf never clips, and a zero gradient gives
+ * coef = 1. A member with a NaN in its gradient gets norm = coef = NaN and NaN parameters from the clipped step; one
+ * with an inf gets norm = inf and coef = max_norm / inf = 0 (NaN under max_norm = +inf), so its step consumes
+ * inf * 0 = NaN where the inf was and 0 elsewhere -- both exactly as in torch -- while every other member's bytes
+ * are what they are without it.
+ * mbrl_grad_norm: norm_out[e] (device [E], or NULL) and coef_out[e] (device [E], required) for the E members; of
+ * each tensor only grad and numel are read. Two launches whatever E, count and the shapes are: the chunk partials
+ * of all E * count tensors (one workgroup per chunk; the table travels in the launch arguments, 64 tensors per
+ * launch, more take further launches; 16-byte loads where the gradient pointer allows and 4-byte loads otherwise,
+ * the same bytes either way), then one workgroup per member. No atomics; no workgroup waits on another.
+ * mbrl_adam_step_clipped: mbrl_adam_step over all E * count tensors (one launch per 64 tensors) in which member e's
+ * tensors consume g' = g * coef[e], one rounded fp32 product per element, in place of g; everything else, the
+ * MBRL_OPT_ADAM_ARITH handling included, is mbrl_adam_step's, and coef[e] == 1.0f is mbrl_adam_step bit for bit.
+ * The gradient buffers are only read: after the call they still hold the raw, unclipped gradient.
+ * mbrl_train_epoch_ensemble_clipped / mbrl_train_epoch_open_loop_clipped: the sibling epoch with, per batch, the
+ * two mbrl_grad_norm launches and the mbrl_adam_step_clipped launch in place of the Adam launch -- two launches
+ * more per batch than the sibling. clip->norms[b][e] (or NULL) receives batch b's pre-clip norm of member e.
+ * With max_norm = +inf the parameters, moments and losses are the sibling's byte for byte.
+ * Workspace (mbrl_grad_norm's ws, clip->workspace): >= mbrl_grad_clip_workspace_bytes(tensors, E, count) bytes (0
+ * for a bad table), 4-byte aligned; any bytes on entry, no zeroing (tests/test_gpu_grad_clip.py fills it, and the
+ * epoch entries' own ws, with NaN and with 0xFF bytes). It holds coef[E] and the chunk partials. The epoch entries'
+ * own ws is the siblings'.
+ * Stream-ordered and capturable: no allocation, no synchronisation. Before any launch: MBRL_EINVAL for a NULL
+ * clip, a max_norm that is NaN or <= 0, a NULL coef / coef_out / workspace, E < 1, count < 1, a NULL table or a
+ * tensor with numel < 0 or with numel > 0 and a NULL grad (the epoch entries and mbrl_adam_step_clipped: a NULL
+ * param or moment as well); MBRL_EUNSUPPORTED for E > MBRL_TRAIN_MAX_MEMBERS or a member of 2^28 chunks or more;
+ * MBRL_EWORKSPACE for a clip workspace that is too small; and every check and code of the sibling entry. */
+typedef struct {
+    float max_norm;      /* > 0, +inf allowed (records norms, never clips); NaN or <= 0: MBRL_EINVAL */
+    int32_t _pad;
+    float* norms;        /* device [batches][E], or NULL */
+    void* workspace;     /* >= mbrl_grad_clip_workspace_bytes; any bytes on entry, no zeroing */
+    size_t ws_bytes;
+} mbrl_grad_clip;
+size_t mbrl_grad_clip_workspace_bytes(const mbrl_adam_tensor* tensors, int32_t E, int32_t count);
+int mbrl_grad_norm(const mbrl_adam_tensor* tensors, int32_t E, int32_t count, float max_norm, float* norm_out,
+                   float* coef_out, void* ws, size_t ws_bytes, mbrl_stream_t stream);
+int mbrl_adam_step_clipped(const mbrl_adam_tensor* tensors, int32_t E, int32_t count,
+                           const mbrl_adam_hparams* hparams, const float* coef, mbrl_stream_t stream);
+int mbrl_train_epoch_ensemble_clipped(const mbrl_train_model* members, int32_t E, const mbrl_train_data* data,
+                                      const int64_t* orders, int64_t rows, int32_t batch_size,
+                                      const mbrl_adam_tensor* tensors, int32_t count, const mbrl_adam_hparams* hparams,
+                                      const float* step_sizes, const float* bc2_sqrt, float* losses, void* ws,
+                                      size_t ws_bytes, mbrl_stream_t stream, const mbrl_grad_clip* clip);
+int mbrl_train_epoch_open_loop_clipped(const mbrl_train_model* members, int32_t E, const mbrl_train_data* data,
+                                       const int64_t* orders, int64_t rows, int32_t batch_size,
+                                       const mbrl_adam_tensor* tensors, int32_t count, const mbrl_adam_hparams* hparams,
+                                       const float* step_sizes, const float* bc2_sqrt, float* losses, void* ws,
+                                       size_t ws_bytes, mbrl_stream_t stream, const mbrl_grad_clip* clip);
 
 /* Keep-best snapshots: per member e, v = loss[e * loss_stride] (device) against best_loss[e] AS IT WAS ON
  * ENTRY. If v < best_loss[e] (a NaN is never better): best_loss[e] = v, best_epoch[e] = epoch,

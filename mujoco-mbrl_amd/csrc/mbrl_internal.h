@@ -629,6 +629,16 @@ hipError_t launch_train_wgrads(const TrainShape& t, int layer, const float* g, c
                                int colsum_tiles, int K, const TrainEnsemble& ens, hipStream_t stream);
 hipError_t launch_adam_step_ensemble(const mbrl_adam_tensor* tensors, int count, const mbrl_adam_hparams& hp,
                                      int arith, hipStream_t stream);
+// Global-norm clipping for the ensemble epochs (grad_clip.hip; the clipped Adam launch is train.hip's). tensors
+// [E][count]. grad_clip_table_check: E, count and the table (adam: param and moments required as well), with the
+// entries' codes; grad_clip_check: the mbrl_grad_clip struct and its workspace on top. launch_grad_clip_step: one
+// batch's norm launches (norms row `batch`, coef in the clip workspace) and the clipped Adam launch.
+int grad_clip_table_check(const char* what, const mbrl_adam_tensor* tensors, int E, int count, bool adam);
+int grad_clip_check(const char* what, const mbrl_grad_clip* clip, const mbrl_adam_tensor* tensors, int E, int count);
+hipError_t launch_adam_step_clipped(const mbrl_adam_tensor* tensors, int E, int count, const mbrl_adam_hparams& hp,
+                                    int arith, const float* coef, hipStream_t stream);
+hipError_t launch_grad_clip_step(const mbrl_adam_tensor* tensors, int E, int count, const mbrl_adam_hparams& hp,
+                                 int arith, const mbrl_grad_clip& clip, int64_t batch, hipStream_t stream);
 
 // ---- cooperative single-candidate kernels (traj.hip, gd.hip): the dot of one 16-row slice, one row
 // per half-wave (32 lanes), and its reduction

@@ -69,8 +69,10 @@ __device__ __forceinline__ void adam_element(float& p, float g, float& m, float&
     p = (arith & ADAM_FMA_ADDCDIV) ? fmaf(step_size, q, p) : p + step_size * q;
 }
 
-template <int CAP>
-__global__ __launch_bounds__(ADAM_THREADS) void adam_step_kernel(const AdamLaunchT<CAP> L) {
+// One workgroup's chunk of one tensor. CLIP (mbrl_adam_step_clipped): the gradient is first scaled by its member's
+// clipping coefficient coef[member[slot]], one rounded product per element; without it neither pointer is read.
+template <int CAP, bool CLIP>
+__device__ __forceinline__ void adam_step_body(const AdamLaunchT<CAP>& L, const float* coef, const uint8_t* member) {
     const int blk = blockIdx.x;
     int ti = 0;
     while (ti + 1 < L.count && blk >= L.first_block[ti + 1]) ++ti;
@@ -79,14 +81,17 @@ __global__ __launch_bounds__(ADAM_THREADS) void adam_step_kernel(const AdamLaunc
     const int64_t i0 = base + 4 * (int64_t)threadIdx.x;
     if (i0 >= T.numel) return;
     const float ss = T.step_size, bc2 = T.bc2_sqrt;
+    float c = 1.0f;
+    if constexpr (CLIP) c = coef[member[ti]];
     const bool vec = i0 + 4 <= T.numel &&
                      ((reinterpret_cast<uintptr_t>(T.param) | reinterpret_cast<uintptr_t>(T.grad) |
                        reinterpret_cast<uintptr_t>(T.exp_avg) | reinterpret_cast<uintptr_t>(T.exp_avg_sq)) & 15) == 0;
     if (vec) {
         float4 p = *reinterpret_cast<const float4*>(T.param + i0);
-        const float4 g = *reinterpret_cast<const float4*>(T.grad + i0);
+        float4 g = *reinterpret_cast<const float4*>(T.grad + i0);
         float4 m = *reinterpret_cast<const float4*>(T.exp_avg + i0);
         float4 v = *reinterpret_cast<const float4*>(T.exp_avg_sq + i0);
+        if constexpr (CLIP) { g.x = g.x * c; g.y = g.y * c; g.z = g.z * c; g.w = g.w * c; }
         adam_element(p.x, g.x, m.x, v.x, ss, bc2, L.hp, L.arith);
         adam_element(p.y, g.y, m.y, v.y, ss, bc2, L.hp, L.arith);
         adam_element(p.z, g.z, m.z, v.z, ss, bc2, L.hp, L.arith);
@@ -98,11 +103,52 @@ __global__ __launch_bounds__(ADAM_THREADS) void adam_step_kernel(const AdamLaunc
     }
     for (int64_t i = i0; i < i0 + 4 && i < T.numel; ++i) {
         float p = T.param[i], m = T.exp_avg[i], v = T.exp_avg_sq[i];
-        adam_element(p, T.grad[i], m, v, ss, bc2, L.hp, L.arith);
+        float g = T.grad[i];
+        if constexpr (CLIP) g = g * c;
+        adam_element(p, g, m, v, ss, bc2, L.hp, L.arith);
         T.param[i] = p;
         T.exp_avg[i] = m;
         T.exp_avg_sq[i] = v;
     }
+}
+
+template <int CAP>
+__global__ __launch_bounds__(ADAM_THREADS) void adam_step_kernel(const AdamLaunchT<CAP> L) {
+    adam_step_body<CAP, false>(L, nullptr, nullptr);
+}
+
+// The ensemble launch with each tensor's member index and the members' device-side coefficients coef[E].
+struct AdamClipLaunch {
+    AdamLaunchT<ADAM_ENS_TENSORS> a;
+    const float* coef;
+    uint8_t member[ADAM_ENS_TENSORS];
+};
+__global__ __launch_bounds__(ADAM_THREADS) void adam_step_clipped_kernel(const AdamClipLaunch L) {
+    adam_step_body<ADAM_ENS_TENSORS, true>(L.a, L.coef, L.member);
+}
+
+// Fills A with up to CAP non-empty tensors at a time (first_block: the workgroup prefix over their chunks) and calls
+// fire(blocks) when the table is full or the tensors are exhausted; tag(slot, i) notes tensor i's slot in the table.
+template <int CAP, class Tag, class Fire>
+static hipError_t adam_table_walk(AdamLaunchT<CAP>& A, const mbrl_adam_tensor* tensors, int count, Tag tag, Fire fire) {
+    int blocks = 0;
+    for (int i = 0; i <= count; ++i) {
+        if (A.count == CAP || (i == count && A.count > 0)) {
+            A.first_block[A.count] = blocks;
+            fire(blocks);
+            const hipError_t e = hipGetLastError();
+            if (e != hipSuccess) return e;
+            A.count = 0;
+            blocks = 0;
+        }
+        if (i == count || tensors[i].numel <= 0) continue;
+        A.t[A.count] = tensors[i];
+        tag(A.count, i);
+        A.first_block[A.count] = blocks;
+        blocks += (int)((tensors[i].numel + ADAM_CHUNK - 1) / ADAM_CHUNK);
+        ++A.count;
+    }
+    return hipSuccess;
 }
 
 template <int CAP>
@@ -111,24 +157,23 @@ static hipError_t launch_adam_step_cap(const mbrl_adam_tensor* tensors, int coun
     AdamLaunchT<CAP> L{};
     L.hp = hp;
     L.arith = arith;
-    int blocks = 0;
-    for (int i = 0; i <= count; ++i) {
-        // launch when the table is full or the tensors are exhausted
-        if (L.count == CAP || (i == count && L.count > 0)) {
-            L.first_block[L.count] = blocks;
-            hipLaunchKernelGGL(adam_step_kernel<CAP>, dim3(blocks), dim3(ADAM_THREADS), 0, stream, L);
-            const hipError_t e = hipGetLastError();
-            if (e != hipSuccess) return e;
-            L.count = 0;
-            blocks = 0;
-        }
-        if (i == count || tensors[i].numel <= 0) continue;
-        L.t[L.count] = tensors[i];
-        L.first_block[L.count] = blocks;
-        blocks += (int)((tensors[i].numel + ADAM_CHUNK - 1) / ADAM_CHUNK);
-        ++L.count;
-    }
-    return hipSuccess;
+    return adam_table_walk<CAP>(L, tensors, count, [](int, int) {}, [&](int blocks) {
+        hipLaunchKernelGGL(adam_step_kernel<CAP>, dim3(blocks), dim3(ADAM_THREADS), 0, stream, L);
+    });
+}
+
+// tensors [E][count]: tensor i belongs to member i / count, whose coefficient scales its gradient.
+hipError_t launch_adam_step_clipped(const mbrl_adam_tensor* tensors, int E, int count, const mbrl_adam_hparams& hp,
+                                    int arith, const float* coef, hipStream_t stream) {
+    AdamClipLaunch L{};
+    L.a.hp = hp;
+    L.a.arith = arith;
+    L.coef = coef;
+    return adam_table_walk<ADAM_ENS_TENSORS>(
+        L.a, tensors, E * count, [&](int slot, int i) { L.member[slot] = (uint8_t)(i / count); },
+        [&](int blocks) {
+            hipLaunchKernelGGL(adam_step_clipped_kernel, dim3(blocks), dim3(ADAM_THREADS), 0, stream, L);
+        });
 }
 
 hipError_t launch_adam_step(const mbrl_adam_tensor* tensors, int count, const mbrl_adam_hparams& hp, int arith,
@@ -2206,6 +2251,16 @@ int mbrl_adam_step(const mbrl_adam_tensor* tensors, int32_t count, const mbrl_ad
                                       reinterpret_cast<hipStream_t>(stream)), "adam_step");
 }
 
+int mbrl_adam_step_clipped(const mbrl_adam_tensor* tensors, int32_t E, int32_t count, const mbrl_adam_hparams* hparams,
+                           const float* coef, mbrl_stream_t stream) {
+    const char* what = "adam_step_clipped";
+    if (!hparams || !coef) return fail(MBRL_EINVAL, "%s: NULL argument", what);
+    if (int rc = grad_clip_table_check(what, tensors, E, count, true)) return rc;
+    const int o = opt(MBRL_OPT_ADAM_ARITH);
+    return hip_check(launch_adam_step_clipped(tensors, E, count, *hparams, o ? o - 1 : ADAM_ARITH_TORCH, coef,
+                                              reinterpret_cast<hipStream_t>(stream)), what);
+}
+
 static int train_shape(const mbrl_train_model* m, TrainShape* t) {
     if (!m) return fail(MBRL_EINVAL, "train: NULL model");
     if (m->state_dim < 1 || m->action_dim < 0 || m->hidden < 1 || m->horizon < 1 || m->n_hidden < 1 ||
@@ -2404,12 +2459,13 @@ int mbrl_train_grads_ensemble(const mbrl_train_model* members, int32_t E, const 
                                         nullptr, nullptr, &ens), what);
 }
 
-int mbrl_train_epoch_ensemble(const mbrl_train_model* members, int32_t E, const mbrl_train_data* data,
-                              const int64_t* orders, int64_t rows, int32_t batch_size, const mbrl_adam_tensor* tensors,
-                              int32_t count, const mbrl_adam_hparams* hparams, const float* step_sizes,
-                              const float* bc2_sqrt, float* losses, void* workspace, size_t ws_bytes,
-                              mbrl_stream_t stream) {
-    const char* what = "train_epoch_ensemble";
+// mbrl_train_epoch_ensemble (clip == NULL) and mbrl_train_epoch_ensemble_clipped (clip checked by the caller's
+// grad_clip_check below): one body, the Adam launch or the norm launches and the clipped Adam launch per batch.
+static int train_epoch_ensemble(const char* what, bool clipped, const mbrl_train_model* members, int32_t E,
+                                const mbrl_train_data* data, const int64_t* orders, int64_t rows, int32_t batch_size,
+                                const mbrl_adam_tensor* tensors, int32_t count, const mbrl_adam_hparams* hparams,
+                                const float* step_sizes, const float* bc2_sqrt, float* losses, void* workspace,
+                                size_t ws_bytes, const mbrl_grad_clip* clip, mbrl_stream_t stream) {
     TrainShape t;
     if (int rc = ensemble_shape(what, members, E, &t)) return rc;
     if (!ensemble_data_ok(data, t) || !orders || !workspace || !tensors || count < 1 || !hparams || !step_sizes ||
@@ -2428,6 +2484,8 @@ int mbrl_train_epoch_ensemble(const mbrl_train_model* members, int32_t E, const 
     const int bs = (int)std::min<int64_t>(batch_size, rows);
     const size_t stride = train_ws_floats(t, bs), need = (size_t)E * stride * sizeof(float);
     if (ws_bytes < need) return fail(MBRL_EWORKSPACE, "%s: workspace %zu < %zu bytes", what, ws_bytes, need);
+    if (clipped)
+        if (int rc = grad_clip_check(what, clip, tensors, E, count)) return rc;
     const mbrl_train_model& m0 = members[0];
     TrainTensors w{m0.weight, m0.bias, m0.weight_grad, m0.bias_grad,
                    data->states, data->actions, data->next_states, data->rewards};
@@ -2448,10 +2506,30 @@ int mbrl_train_epoch_ensemble(const mbrl_train_model* members, int32_t E, const 
             table[i].bc2_sqrt = bc2_sqrt[b * total + i];
         }
         // every member's step in one launch (ADAM_ENS_TENSORS per launch: E x count beyond that takes more)
-        if (int rc = hip_check(launch_adam_step_cap<ADAM_ENS_TENSORS>(table.data(), total, *hparams, ar, st), what))
+        if (int rc = hip_check(clipped ? launch_grad_clip_step(table.data(), E, count, *hparams, ar, *clip, b, st)
+                                       : launch_adam_step_cap<ADAM_ENS_TENSORS>(table.data(), total, *hparams, ar, st),
+                               what))
             return rc;
     }
     return MBRL_OK;
+}
+
+int mbrl_train_epoch_ensemble(const mbrl_train_model* members, int32_t E, const mbrl_train_data* data,
+                              const int64_t* orders, int64_t rows, int32_t batch_size, const mbrl_adam_tensor* tensors,
+                              int32_t count, const mbrl_adam_hparams* hparams, const float* step_sizes,
+                              const float* bc2_sqrt, float* losses, void* workspace, size_t ws_bytes,
+                              mbrl_stream_t stream) {
+    return train_epoch_ensemble("train_epoch_ensemble", false, members, E, data, orders, rows, batch_size, tensors, count,
+                                hparams, step_sizes, bc2_sqrt, losses, workspace, ws_bytes, nullptr, stream);
+}
+
+int mbrl_train_epoch_ensemble_clipped(const mbrl_train_model* members, int32_t E, const mbrl_train_data* data,
+                                      const int64_t* orders, int64_t rows, int32_t batch_size,
+                                      const mbrl_adam_tensor* tensors, int32_t count, const mbrl_adam_hparams* hparams,
+                                      const float* step_sizes, const float* bc2_sqrt, float* losses, void* workspace,
+                                      size_t ws_bytes, mbrl_stream_t stream, const mbrl_grad_clip* clip) {
+    return train_epoch_ensemble("train_epoch_ensemble_clipped", true, members, E, data, orders, rows, batch_size, tensors,
+                                count, hparams, step_sizes, bc2_sqrt, losses, workspace, ws_bytes, clip, stream);
 }
 
 }  // extern "C"

@@ -465,12 +465,13 @@ int mbrl_train_grads_open_loop(const mbrl_train_model* members, int32_t E, const
                                reinterpret_cast<hipStream_t>(stream)), what);
 }
 
-int mbrl_train_epoch_open_loop(const mbrl_train_model* members, int32_t E, const mbrl_train_data* data,
-                               const int64_t* orders, int64_t rows, int32_t batch_size, const mbrl_adam_tensor* tensors,
-                               int32_t count, const mbrl_adam_hparams* hparams, const float* step_sizes,
-                               const float* bc2_sqrt, float* losses, void* workspace, size_t ws_bytes,
-                               mbrl_stream_t stream) {
-    const char* what = "train_epoch_open_loop";
+// mbrl_train_epoch_open_loop (clip == NULL) and mbrl_train_epoch_open_loop_clipped: one body, the Adam launch or the
+// norm launches and the clipped Adam launch per batch.
+static int train_epoch_open_loop(const char* what, bool clipped, const mbrl_train_model* members, int32_t E,
+                                 const mbrl_train_data* data, const int64_t* orders, int64_t rows, int32_t batch_size,
+                                 const mbrl_adam_tensor* tensors, int32_t count, const mbrl_adam_hparams* hparams,
+                                 const float* step_sizes, const float* bc2_sqrt, float* losses, void* workspace,
+                                 size_t ws_bytes, const mbrl_grad_clip* clip, mbrl_stream_t stream) {
     TrainShape t;
     if (int rc = ol_shape(what, members, E, &t)) return rc;
     if (!ol_data_ok(data, t) || !orders || !workspace || !tensors || count < 1 || !hparams || !step_sizes || !bc2_sqrt)
@@ -490,6 +491,8 @@ int mbrl_train_epoch_open_loop(const mbrl_train_model* members, int32_t E, const
     if (int rc = ol_batch_ok(what, E, bs, t)) return rc;
     const size_t need = ol_plan(t, E, bs).floats * sizeof(float);
     if (ws_bytes < need) return fail(MBRL_EWORKSPACE, "%s: workspace %zu < %zu bytes", what, ws_bytes, need);
+    if (clipped)
+        if (int rc = grad_clip_check(what, clip, tensors, E, count)) return rc;
     const int arith = opt(MBRL_OPT_ADAM_ARITH), ar = arith ? arith - 1 : ADAM_ARITH_TORCH;
     const hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     std::vector<mbrl_adam_tensor> table(tensors, tensors + total);
@@ -504,9 +507,29 @@ int mbrl_train_epoch_open_loop(const mbrl_train_model* members, int32_t E, const
             table[i].step_size = step_sizes[b * total + i];
             table[i].bc2_sqrt = bc2_sqrt[b * total + i];
         }
-        if (int rc = hip_check(launch_adam_step_ensemble(table.data(), total, *hparams, ar, st), what)) return rc;
+        if (int rc = hip_check(clipped ? launch_grad_clip_step(table.data(), E, count, *hparams, ar, *clip, b, st)
+                                       : launch_adam_step_ensemble(table.data(), total, *hparams, ar, st), what))
+            return rc;
     }
     return MBRL_OK;
+}
+
+int mbrl_train_epoch_open_loop(const mbrl_train_model* members, int32_t E, const mbrl_train_data* data,
+                               const int64_t* orders, int64_t rows, int32_t batch_size, const mbrl_adam_tensor* tensors,
+                               int32_t count, const mbrl_adam_hparams* hparams, const float* step_sizes,
+                               const float* bc2_sqrt, float* losses, void* workspace, size_t ws_bytes,
+                               mbrl_stream_t stream) {
+    return train_epoch_open_loop("train_epoch_open_loop", false, members, E, data, orders, rows, batch_size, tensors,
+                                 count, hparams, step_sizes, bc2_sqrt, losses, workspace, ws_bytes, nullptr, stream);
+}
+
+int mbrl_train_epoch_open_loop_clipped(const mbrl_train_model* members, int32_t E, const mbrl_train_data* data,
+                                       const int64_t* orders, int64_t rows, int32_t batch_size,
+                                       const mbrl_adam_tensor* tensors, int32_t count, const mbrl_adam_hparams* hparams,
+                                       const float* step_sizes, const float* bc2_sqrt, float* losses, void* workspace,
+                                       size_t ws_bytes, mbrl_stream_t stream, const mbrl_grad_clip* clip) {
+    return train_epoch_open_loop("train_epoch_open_loop_clipped", true, members, E, data, orders, rows, batch_size,
+                                 tensors, count, hparams, step_sizes, bc2_sqrt, losses, workspace, ws_bytes, clip, stream);
 }
 
 }  // extern "C"

@@ -78,6 +78,8 @@ EXPORTED = (
     "mbrl_train_ensemble_workspace_bytes", "mbrl_train_grads_ensemble", "mbrl_train_epoch_ensemble",
     "mbrl_eval_members", "mbrl_keep_best", "mbrl_eval_members_open_loop",
     "mbrl_train_open_loop_workspace_bytes", "mbrl_train_grads_open_loop", "mbrl_train_epoch_open_loop",
+    "mbrl_grad_clip_workspace_bytes", "mbrl_grad_norm", "mbrl_adam_step_clipped",
+    "mbrl_train_epoch_ensemble_clipped", "mbrl_train_epoch_open_loop_clipped",
 )
 
 
@@ -160,6 +162,12 @@ class CopyTensor(ctypes.Structure):
     _fields_ = [("src", c_void_p), ("dst", c_void_p), ("numel", c_int64)]
 
 
+class GradClip(ctypes.Structure):
+    """mbrl_grad_clip (include/mbrl_cem.h; added within ABI v13): the clipped epoch entries' extra argument."""
+    _fields_ = [("max_norm", c_float), ("_pad", c_int32), ("norms", c_void_p), ("workspace", c_void_p),
+                ("ws_bytes", c_size_t)]
+
+
 _lib = None
 
 
@@ -231,6 +239,16 @@ def load():
         "mbrl_train_epoch_open_loop": (c_int32, [POINTER(TrainModel), c_int32, POINTER(TrainData), P, c_int64, c_int32,
                                                  POINTER(AdamTensor), c_int32, POINTER(AdamHparams), P, P, P, P,
                                                  c_size_t, P]),
+        # global-norm clipping: the norm launches, the clipped Adam launch and the epoch entries that run them
+        "mbrl_grad_clip_workspace_bytes": (c_size_t, [POINTER(AdamTensor), c_int32, c_int32]),
+        "mbrl_grad_norm": (c_int32, [POINTER(AdamTensor), c_int32, c_int32, c_float, P, P, P, c_size_t, P]),
+        "mbrl_adam_step_clipped": (c_int32, [POINTER(AdamTensor), c_int32, c_int32, POINTER(AdamHparams), P, P]),
+        "mbrl_train_epoch_ensemble_clipped": (c_int32, [POINTER(TrainModel), c_int32, POINTER(TrainData), P, c_int64,
+                                                        c_int32, POINTER(AdamTensor), c_int32, POINTER(AdamHparams), P,
+                                                        P, P, P, c_size_t, P, POINTER(GradClip)]),
+        "mbrl_train_epoch_open_loop_clipped": (c_int32, [POINTER(TrainModel), c_int32, POINTER(TrainData), P, c_int64,
+                                                         c_int32, POINTER(AdamTensor), c_int32, POINTER(AdamHparams), P,
+                                                         P, P, P, c_size_t, P, POINTER(GradClip)]),
         "mbrl_eval_members": (c_int32, [POINTER(TrainModel), c_int32, POINTER(TrainData), P, c_int64, P, P, P, P]),
         "mbrl_eval_members_open_loop": (c_int32, [POINTER(TrainModel), c_int32, POINTER(TrainData), P, c_int64, P, P, P, P,
                                                   P]),

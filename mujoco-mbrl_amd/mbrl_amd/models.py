@@ -272,7 +272,7 @@ class _NativeGrads:
 
 
 def _train_loop(model, dataset, optimizer, batch_size, num_epochs, step_loss, writer, tags, criterion=None,
-                order_fn=None, iter0=0):
+                order_fn=None, iter0=0, max_grad_norm=None, norm_tag=None):
     """models.py:53-93 / 165-217 on the model's device: per batch, the loss summed over the horizon
     steps, zero_grad, backward, step -- the reference's order of operations. Batches are gathered
     from device-resident transitions (TransitionsDataset.stacked) instead of per-sample collation;
@@ -280,18 +280,20 @@ def _train_loop(model, dataset, optimizer, batch_size, num_epochs, step_loss, wr
     through mbrl_adam_step (optim.AdamStep: one launch, torch's arithmetic bit for bit).
     order_fn (EnsembleModel.train_members): epoch k visits the rows order_fn(k) instead of a shuffle
     drawn from the global RNG, batch by batch (no whole-epoch device call: its order ring draws), and
-    the writer's batch index goes on from iter0 (the batches a shared-launch part of the call ran)."""
+    the writer's batch index goes on from iter0 (the batches a shared-launch part of the call ran).
+    max_grad_norm (train_members): torch.nn.utils.clip_grad_norm_ over the model's parameters between the
+    gradient and the step, batch by batch; the writer gets the pre-clip norm under norm_tag."""
     dev = _device_of(model)
     if dev.type == "cuda":
         with torch.cuda.device(dev):       # launches and workspaces on the model's GPU
             return _train_loop_on(dev, model, dataset, optimizer, batch_size, num_epochs, step_loss, writer, tags,
-                                  criterion, order_fn, iter0)
+                                  criterion, order_fn, iter0, max_grad_norm, norm_tag)
     return _train_loop_on(dev, model, dataset, optimizer, batch_size, num_epochs, step_loss, writer, tags, criterion,
-                          order_fn, iter0)
+                          order_fn, iter0, max_grad_norm, norm_tag)
 
 
 def _train_loop_on(dev, model, dataset, optimizer, batch_size, num_epochs, step_loss, writer, tags, criterion,
-                   order_fn=None, iter0=0):
+                   order_fn=None, iter0=0, max_grad_norm=None, norm_tag=None):
     if dataset.num_transitions() == 0:    # the reference's DataLoader yields no batch
         model.train_iterations += 1
         return
@@ -314,7 +316,7 @@ def _train_loop_on(dev, model, dataset, optimizer, batch_size, num_epochs, step_
     own = set() if native is None else {id(p) for p in native.params}
     extra = [p for g in optimizer.param_groups for p in g["params"] if id(p) not in own] if native is not None else []
     num_iters = iter0
-    whole = native is not None and fast is not None and order_fn is None
+    whole = native is not None and fast is not None and order_fn is None and max_grad_norm is None
     if whole and num_epochs > 0:
         # The device path issues the epochs back to back with no host round trip between them (a
         # per-epoch copy of the row order from pageable memory waited for the previous epoch to drain).
@@ -358,9 +360,13 @@ def _train_loop_on(dev, model, dataset, optimizer, batch_size, num_epochs, step_
                 optimizer.zero_grad()
                 loss, parts = _batch_loss(dataset, ins, outs, idx, step_loss, n_parts)
                 loss.backward(retain_graph=True)
+            if max_grad_norm is not None:
+                norm = torch.nn.utils.clip_grad_norm_(model.parameters(), max_grad_norm)
             if fast is None or not fast.step():
                 optimizer.step()
             num_iters += 1
+            if writer is not None and max_grad_norm is not None and norm_tag is not None:
+                writer.add_scalar(norm_tag.format(model.train_iterations), norm, num_iters)
             if writer is not None:
                 for tag, val in zip(tags, parts if n_parts > 1 else [loss]):
                     writer.add_scalar(tag.format(model.train_iterations), val, num_iters)
@@ -599,7 +605,7 @@ class EnsembleModel(DynamicsModel):
         return torch.stack([m._forward(x) for m in self.members]).mean(0)
 
     def train_members(self, dataset, optimizers, batch_size=512, num_epochs=50, bootstrap=True, seed=0,
-                      criterion=None, writer=None, loss="one_step"):
+                      criterion=None, writer=None, loss="one_step", max_grad_norm=None):
         """Train every member on its own view of `dataset`: the bootstrap training a PETS-style
         ensemble's diversity comes from (train_model, inherited, fits the member MEAN with one optimizer
         and one data order, so every member sees the same signal).
@@ -630,9 +636,19 @@ class EnsembleModel(DynamicsModel):
         through time); states[i, h] for h >= 1 is not read. Orders, hook, writer tags and the return value are
         the same; the shared launches are one mbrl_train_epoch_open_loop call per epoch
         (csrc/train_open_loop.hip) under the same support test, and the fallback feeds m._forward its own
-        output in torch. Any other string is a ValueError before any work."""
+        output in torch. Any other string is a ValueError before any work.
+
+        max_grad_norm: None (the default: exactly the calls above), or a positive float -- each member's gradient
+        is clipped to that global L2 norm between the gradient and the Adam step of every batch, as
+        torch.nn.utils.clip_grad_norm_(m.parameters(), max_grad_norm) does (float("inf") clips nothing and only
+        records). The shared launches become mbrl_train_epoch_ensemble_clipped / mbrl_train_epoch_open_loop_clipped
+        (csrc/grad_clip.hip: two launches more per batch) under the same support test; the fallbacks call
+        clip_grad_norm_. With a writer each batch's pre-clip norm goes to grad_norm/member{e}/{iteration}; the
+        native path keeps the norms on the device through the epoch and copies them out with the losses. Anything
+        but None or a positive number is a ValueError before any work."""
         if loss not in ("one_step", "open_loop"):
             raise ValueError(f'train_members: loss must be "one_step" or "open_loop", got {loss!r}')
+        max_grad_norm = _check_max_grad_norm("train_members", max_grad_norm)
         open_loop = loss == "open_loop"
         members = list(self.members)
         opts = [optimizers(m) for m in members] if callable(optimizers) else list(optimizers)
@@ -644,14 +660,14 @@ class EnsembleModel(DynamicsModel):
         if n > 0 and num_epochs > 0 and _device_of(self).type == "cuda":
             with torch.cuda.device(_device_of(self)):
                 first = _train_members_native(self, members, opts, dataset, batch_size, num_epochs, bootstrap, seed,
-                                              criterion, writer, open_loop=open_loop)
+                                              criterion, writer, open_loop=open_loop, max_grad_norm=max_grad_norm)
         if open_loop and n > 0 and first < num_epochs:
             for e, (m, opt) in enumerate(zip(members, opts)):
                 if first > 0:
                     m.train_iterations -= 1
                 _train_open_loop_torch(m, e, dataset, opt, batch_size, num_epochs - first, criterion, writer,
                                        lambda k, e=e: member_order(seed, e, first + k, n, bootstrap),
-                                       first * ((n + batch_size - 1) // batch_size))
+                                       first * ((n + batch_size - 1) // batch_size), max_grad_norm)
                 m.train_iterations += 1
         elif first < num_epochs or n == 0 or num_epochs <= 0:
             for e, (m, opt) in enumerate(zip(members, opts)):
@@ -664,7 +680,8 @@ class EnsembleModel(DynamicsModel):
                 _train_loop(m, dataset, opt, batch_size, num_epochs - first, step_loss, writer,
                             [f"loss/state/member{e}/{{}}"], criterion,
                             order_fn=lambda k, e=e: member_order(seed, e, first + k, n, bootstrap),
-                            iter0=first * ((n + batch_size - 1) // batch_size))
+                            iter0=first * ((n + batch_size - 1) // batch_size), max_grad_norm=max_grad_norm,
+                            norm_tag=f"grad_norm/member{e}/{{}}")
         self.train_iterations += 1
         return first
 
@@ -718,7 +735,7 @@ class EnsembleModel(DynamicsModel):
 
     def fit_members(self, dataset, holdout, optimizers, batch_size=512, max_epochs=50, patience=None, check_every=1,
                     restore_best=True, bootstrap=True, seed=0, criterion=None, writer=None, holdout_loss="one_step",
-                    train_loss="one_step"):
+                    train_loss="one_step", max_grad_norm=None):
         """train_members with a held-out set: the same epochs (orders, shared launches and fallback rules
         are train_members'), and after each epoch every member's loss on all rows of `holdout` (a
         TransitionsDataset of the same dimensions and normalisation; evaluate_members' loss) and a snapshot
@@ -737,6 +754,8 @@ class EnsembleModel(DynamicsModel):
         holdout_loss="open_loop" the members are trained on, and picked by, the loss a planner's rollout
         meets). Any other string is a ValueError before any work.
 
+        max_grad_norm: train_members' per-member gradient clipping for the epochs (None: none).
+
         patience: after each epoch k with (k + 1) % check_every == 0 the host reads the members' `stale`
         counts (epochs since the member's best) and stops when every member's is >= patience
         (tests/holdout_reference.py restates the rule in NumPy). restore_best: at the end each member's parameters become its
@@ -751,6 +770,7 @@ class EnsembleModel(DynamicsModel):
             raise ValueError(f'fit_members: holdout_loss must be "one_step" or "open_loop", got {holdout_loss!r}')
         if train_loss not in ("one_step", "open_loop"):
             raise ValueError(f'fit_members: train_loss must be "one_step" or "open_loop", got {train_loss!r}')
+        max_grad_norm = _check_max_grad_norm("fit_members", max_grad_norm)
         open_loop = train_loss == "open_loop"
         members = list(self.members)
         opts = [optimizers(m) for m in members] if callable(optimizers) else list(optimizers)
@@ -774,7 +794,8 @@ class EnsembleModel(DynamicsModel):
             first = 0
             if max_epochs > 0 and dev.type == "cuda":
                 first = _train_members_native(self, members, opts, dataset, batch_size, max_epochs, bootstrap, seed,
-                                              criterion, writer, after_epoch=after_epoch, open_loop=open_loop)
+                                              criterion, writer, after_epoch=after_epoch, open_loop=open_loop,
+                                              max_grad_norm=max_grad_norm)
             batches = (n + batch_size - 1) // max(batch_size, 1)
             for k in range(tracker.epochs, 0 if stopped else max_epochs):
                 for e, (m, opt) in enumerate(zip(members, opts)):
@@ -785,11 +806,12 @@ class EnsembleModel(DynamicsModel):
                     m.train_iterations = iteration[e]         # (one call's worth of epochs: one iteration)
                     if open_loop:
                         _train_open_loop_torch(m, e, dataset, opt, batch_size, 1, criterion, writer,
-                                               lambda _, e=e, k=k: member_order(seed, e, k, n, bootstrap), k * batches)
+                                               lambda _, e=e, k=k: member_order(seed, e, k, n, bootstrap), k * batches,
+                                               max_grad_norm)
                         continue
                     _train_loop(m, dataset, opt, batch_size, 1, step_loss, writer, [f"loss/state/member{e}/{{}}"],
                                 criterion, order_fn=lambda _, e=e, k=k: member_order(seed, e, k, n, bootstrap),
-                                iter0=k * batches)
+                                iter0=k * batches, max_grad_norm=max_grad_norm, norm_tag=f"grad_norm/member{e}/{{}}")
                 if after_epoch(k):
                     break
             ran = tracker.epochs
@@ -830,6 +852,15 @@ class EnsembleModel(DynamicsModel):
         return out
 
 
+def _check_max_grad_norm(what, max_grad_norm):
+    """None, or the positive float train_members / fit_members clip to (inf allowed); anything else a ValueError."""
+    if max_grad_norm is None:
+        return None
+    if isinstance(max_grad_norm, bool) or not isinstance(max_grad_norm, (int, float)) or not max_grad_norm > 0:
+        raise ValueError(f"{what}: max_grad_norm must be None or a positive number, got {max_grad_norm!r}")
+    return float(max_grad_norm)
+
+
 def member_order(seed, e, k, n, bootstrap=True):
     """The rows member e visits in epoch k of EnsembleModel.train_members (int64 [n]): n draws with
     replacement (bootstrap) or a permutation, from np.random.default_rng([seed, e, k])."""
@@ -844,6 +875,7 @@ class _NativeEnsemble:
     mbrl_train_model of _NativeGrads, one dataset, one workspace of E member slices."""
 
     WORKSPACE, EPOCH = "mbrl_train_ensemble_workspace_bytes", "mbrl_train_epoch_ensemble"
+    CLIPPED = "mbrl_train_epoch_ensemble_clipped"
 
     def __init__(self, members, ins, outs, horizon, batch_size):
         from . import _lib
@@ -875,6 +907,7 @@ class _NativeEnsemble:
             _lib.check(-1, self.WORKSPACE)
         self.ws = torch.empty(need, dtype=torch.uint8, device=self.dev)
         self.ptrs = [t.data_ptr() for params in self.params for t in params]
+        self.clip_ws = None
 
     @classmethod
     def cached(cls, owner, members, ins, outs, horizon, batch_size):
@@ -897,6 +930,14 @@ class _NativeEnsemble:
         """One epoch of every member over the device orders [E * rows]. Returns the losses
         [batches, E, 3] (device), or None when an optimizer's state does not allow the whole-epoch
         call or the optimizers' hyper-parameters differ (nothing has been launched then)."""
+        return self._epoch(orders, rows, batch_size, adams, None)
+
+    def epoch_clipped(self, orders, rows, batch_size, adams, max_norm):
+        """epoch() through the clipped entry: returns (losses, norms [batches, E] (device): each batch's pre-clip
+        gradient norm per member), or None as epoch() does."""
+        return self._epoch(orders, rows, batch_size, adams, max_norm)
+
+    def _epoch(self, orders, rows, batch_size, adams, max_norm):
         for params, grads in zip(self.params, self.grads):
             for p, g in zip(params, grads):
                 if p.grad is not g:
@@ -923,26 +964,40 @@ class _NativeEnsemble:
         bc = np.stack([np.ctypeslib.as_array(pl[3]).reshape(steps, count) for pl in plans], axis=1)
         ss, bc = np.ascontiguousarray(ss, np.float32), np.ascontiguousarray(bc, np.float32)
         losses = torch.empty((steps, self.E, 3), dtype=torch.float32, device=self.dev)
-        self._lib.check(getattr(self.lib, self.EPOCH)(
-            self.models, self.E, ctypes.byref(self.data), ctypes.c_void_p(orders.data_ptr()), int(rows),
-            int(batch_size), table, count, ctypes.byref(hp), ctypes.c_void_p(ss.ctypes.data),
-            ctypes.c_void_p(bc.ctypes.data), ctypes.c_void_p(losses.data_ptr()), ctypes.c_void_p(self.ws.data_ptr()),
-            self.ws.numel(), self._lib.stream_handle(self.dev)), self.EPOCH)
+        args = (self.models, self.E, ctypes.byref(self.data), ctypes.c_void_p(orders.data_ptr()), int(rows),
+                int(batch_size), table, count, ctypes.byref(hp), ctypes.c_void_p(ss.ctypes.data),
+                ctypes.c_void_p(bc.ctypes.data), ctypes.c_void_p(losses.data_ptr()), ctypes.c_void_p(self.ws.data_ptr()),
+                self.ws.numel(), self._lib.stream_handle(self.dev))
+        if max_norm is None:
+            self._lib.check(getattr(self.lib, self.EPOCH)(*args), self.EPOCH)
+        else:
+            if self.clip_ws is None:
+                need = self.lib.mbrl_grad_clip_workspace_bytes(table, self.E, count)
+                if need == 0:
+                    self._lib.check(-1, "mbrl_grad_clip_workspace_bytes")
+                self.clip_ws = torch.empty(need, dtype=torch.uint8, device=self.dev)
+            norms = torch.empty((steps, self.E), dtype=torch.float32, device=self.dev)
+            clip = self._lib.GradClip(max_norm=max_norm, norms=norms.data_ptr(), workspace=self.clip_ws.data_ptr(),
+                                      ws_bytes=self.clip_ws.numel())
+            self._lib.check(getattr(self.lib, self.CLIPPED)(*args, ctypes.byref(clip)), self.CLIPPED)
         for adam, params in zip(adams, self.params):
             adam.epoch_done(params)
-        return losses
+        return losses if max_norm is None else (losses, norms)
 
 
 class _NativeEnsembleOpenLoop(_NativeEnsemble):
     """mbrl_train_epoch_open_loop: the same members, tables and orders, the open-loop loss (csrc/train_open_loop.hip)."""
 
     WORKSPACE, EPOCH = "mbrl_train_open_loop_workspace_bytes", "mbrl_train_epoch_open_loop"
+    CLIPPED = "mbrl_train_epoch_open_loop_clipped"
 
 
-def _train_open_loop_torch(m, e, dataset, opt, batch_size, num_epochs, criterion, writer, order_fn, iter0):
+def _train_open_loop_torch(m, e, dataset, opt, batch_size, num_epochs, criterion, writer, order_fn, iter0,
+                           max_grad_norm=None):
     """train_members(loss="open_loop") for one member in torch: per batch the criterion of every step's prediction
     against next_states[i, h], summed, with m._forward fed its own output from states[i, 0] on; autograd runs
-    through the fed-back predictions. A plain Adam steps through mbrl_adam_step on a GPU (optim.AdamStep)."""
+    through the fed-back predictions. A plain Adam steps through mbrl_adam_step on a GPU (optim.AdamStep).
+    max_grad_norm: clip_grad_norm_ between backward() and the step; the writer gets the pre-clip norm."""
     dev = _device_of(m)
     _, ins, outs = dataset.stacked(dev)
     (states, actions), (_, next_states) = ins, outs
@@ -960,20 +1015,26 @@ def _train_open_loop_torch(m, e, dataset, opt, batch_size, num_epochs, criterion
                     x = m._forward(torch.cat([x, ac[:, h]], dim=1))
                     loss = loss + criterion(x, ns[:, h])
                 loss.backward()
+                if max_grad_norm is not None:
+                    norm = torch.nn.utils.clip_grad_norm_(m.parameters(), max_grad_norm)
                 if fast is None or not fast.step():
                     opt.step()
                 it += 1
                 if writer is not None:
                     writer.add_scalar(f"loss/state/member{e}/{m.train_iterations}", loss, it)
+                    if max_grad_norm is not None:
+                        writer.add_scalar(f"grad_norm/member{e}/{m.train_iterations}", norm, it)
 
 
 def _train_members_native(owner, members, opts, dataset, batch_size, num_epochs, bootstrap, seed, criterion, writer,
-                          after_epoch=None, open_loop=False):
+                          after_epoch=None, open_loop=False, max_grad_norm=None):
     """The epochs of train_members the shared launches can take, from the first: returns how many ran
     (0: not supported here; the caller trains the rest member by member). Orders are staged as
     _train_loop_on stages them: epoch k + 1's rows are drawn into a pinned ring row while epoch k
     runs and copied on the side stream, with no host round trip between epochs.
-    after_epoch (fit_members): called with k once epoch k is enqueued; a true result ends the epochs."""
+    after_epoch (fit_members): called with k once epoch k is enqueued; a true result ends the epochs.
+    max_grad_norm: the epochs go through the clipped entry; the norms stay on the device beside the losses until
+    the writer reads both after the last epoch."""
     from . import _lib
     dev = _device_of(members[0])
     E = len(members)
@@ -998,14 +1059,20 @@ def _train_members_native(owner, members, opts, dataset, batch_size, num_epochs,
         return write
     ring.draw(0, fill(0))
     ring.copy(0, main)
-    epoch_losses, done = [], 0
+    epoch_losses, epoch_norms, done = [], [], 0
     for ep in range(num_epochs):
         _, order = ring.rows(ep)
         if ep >= 1:
             ring.copied[ep % ring.K].wait(main)       # epoch ep's orders have landed
-        losses = native.epoch(order, n, batch_size, adams)
+        if max_grad_norm is None:
+            losses = native.epoch(order, n, batch_size, adams)
+        else:
+            losses = native.epoch_clipped(order, n, batch_size, adams, max_grad_norm)
         if losses is None:
             break
+        if max_grad_norm is not None:
+            losses, norms = losses
+            epoch_norms.append(norms)
         if ep + 1 < num_epochs:
             ring.draw(ep + 1, fill(ep + 1))
             ring.copy(ep + 1, ring.side)
@@ -1021,6 +1088,12 @@ def _train_members_native(owner, members, opts, dataset, batch_size, num_epochs,
                 it += 1
                 for e, m in enumerate(members):
                     writer.add_scalar(f"loss/state/member{e}/{m.train_iterations}", row[e][0], it)
+        it = 0
+        for norms in epoch_norms:
+            for row in norms.cpu().tolist():
+                it += 1
+                for e, m in enumerate(members):
+                    writer.add_scalar(f"grad_norm/member{e}/{m.train_iterations}", row[e], it)
     if done:
         for m in members:
             m.train_iterations += 1
