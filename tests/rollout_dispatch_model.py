@@ -7,7 +7,12 @@ Four pieces of the HIP extension's host code, in plain Python:
   dispatch()          the fp32 part of rollout_impl (csrc/plan.hip) and launch_rollout (csrc/rollout.hip):
                       R, NW, part_alias, ring or generic, the half-group seam, the R = 2 -> 1 fallbacks, the
                       refusals, and the 8-candidate branch as a function of an explicit CU count
-  trajectory_kernel() traj_reg_supported and the static half of traj_coop_supported (csrc/traj.hip)
+  trajectory_instance() traj_impl (csrc/plan.hip) and the launchers of csrc/traj.hip: traj_reg_supported,
+                      launch_reg_w / launch_reg_k0, coop_k0r, the static half of traj_coop_supported,
+                      launch_coop_width and launch_coop_variant's grid choice -> the kernel with its template
+                      arguments (pinned by tests/test_traj_cases_host.py and, through the hand-off block each
+                      kernel leaves in the workspace, tests/test_gpu_traj_envelope.py)
+  trajectory_kernel() the kernel family alone: 'reg', 'coop' or 'plain'
 
 dispatch() returns an Instance (hashable: the template arguments of the kernel that runs, plus the labels a
 coverage test wants) or a Refusal (the MBRL_* code and a fragment of the message). It is a restatement, not
@@ -244,8 +249,25 @@ def split_kernel(s, a, W, L, E=1, reward=0, *, N, P, split_tile=0):
                  max(split_lds_need_bytes(g, R, P), LDS_FLOOR))
 
 
-# ---- the single-trajectory kernels (traj.hip)
+# ---- the single-trajectory kernels (traj.hip, dispatched by traj_impl in plan.hip)
 COOP_ROWS, COOP_MAX_W, COOP_LDS_LIMIT = 16, 512, 150 * 1024
+COOP_MAX_GRID = 1024           # traj_coop_supported: `P * E > 1024`
+COOP_BUDGETS = ((32, 32, 2), (96, 80, 5))    # coop_k0r / launch_traj_coop: (K0R, largest s, SM); 16 SM >= s
+XCD_MAX_E = 8                  # launch_coop_variant: the per-XCD grid needs `E <= 8`
+REG_MAX_W = 256                # traj_reg_supported: `A.Wpad > 256`
+REG_K0_SPLIT = 8               # launch_reg_k0: `K0 <= 8` runs the K0R = 8 instance, else K0R = 32
+REG_LDS_LIMIT = 64 * 1024      # traj_reg_supported
+REG_FIXED_FLOATS = 32 + 32 + 128     # traj_reg_kernel's x0, out and prm blocks (beside 2 Wpad and H a)
+TRAJ_HOP_DEFAULT = 2           # mbrl_host.h kTrajHopDefault: TrajArgs.hop_mode under MBRL_OPT_TRAJ_HOP = 0
+
+Reg = namedtuple("Reg", "kernel WP NHL K0R")
+Coop = namedtuple("Coop", "kernel K0R SM WI grid hop")     # grid "xcd" / "pe"; hop: TrajArgs.hop_mode as launched
+Plain = namedtuple("Plain", "kernel gated")
+
+# every instance launch_traj_reg / launch_traj_coop list
+REG_INSTANCES = frozenset((wp, nhl, k0r) for wp in (64, 128, 256) for nhl in range(4) for k0r in (8, 32)
+                          if wp <= 128 or nhl <= 1)
+COOP_INSTANCES = frozenset((k0r, sm, wi) for k0r, _, sm in COOP_BUDGETS for wi in (2, 4, 8, 16))
 
 
 def _reg_max_hidden(Wp):
@@ -253,10 +275,9 @@ def _reg_max_hidden(Wp):
 
 
 def _coop_k0r(s, a):
-    if s + a <= 32 and s <= 32:
-        return 32
-    if s + a <= 96 and s <= 80:
-        return 96
+    for k0r, max_s, _ in COOP_BUDGETS:
+        if s + a <= k0r and s <= max_s:
+            return k0r
     return 0
 
 
@@ -266,17 +287,53 @@ def _coop_lds_bytes(s, a, W, Wp, L, H, k0r):
     return 4 * o
 
 
-def trajectory_kernel(s, a, W, L, E=1, reward=0, *, H):
-    """'reg', 'coop' (where the workspace and the device's occupancy also allow it) or 'plain'."""
-    g = geometry(s, a, W, L, E, reward)
+def reg_max_steps(a, Wp):
+    """The longest H traj_reg_supported admits: H a <= 16384 - 192 - 2 Wpad floats of normalised actions."""
+    return (REG_LDS_LIMIT // 4 - REG_FIXED_FLOATS - 2 * Wp) // a
+
+
+def _reg_supported(s, a, Wp, L, H):
+    return Wp <= REG_MAX_W and L - 1 <= _reg_max_hidden(Wp) and s + a <= 32 and s <= 32 and \
+        4 * (REG_FIXED_FLOATS + 2 * Wp + H * a) <= REG_LDS_LIMIT
+
+
+def _coop_supported(s, a, W, Wp, L, E, H):
+    """The static half of traj_coop_supported (grid_fits, the device's occupancy, is left out)."""
+    k0r = _coop_k0r(s, a)
+    return bool(k0r) and L >= 2 and W == Wp and Wp <= COOP_MAX_W and (Wp // COOP_ROWS) * E <= COOP_MAX_GRID and \
+        _coop_lds_bytes(s, a, W, Wp, L, H, k0r) <= COOP_LDS_LIMIT
+
+
+def trajectory_instance(s, a, W, L, E=1, *, H, traj_hop=0, debug_abort=0):
+    """The kernel mbrl_trajectory / final_trajectory launches for one action sequence, with its template
+    arguments: Reg("reg", WP, NHL, K0R), Coop("coop", K0R, SM, WI, grid, hop) or Plain("plain", gated), None
+    where make_geometry refuses the shape. traj_hop / debug_abort: MBRL_OPT_TRAJ_HOP / MBRL_OPT_DEBUG_TRAJ_ABORT.
+
+    traj_reg_supported, launch_reg_w / launch_reg_k0, coop_k0r, traj_coop_supported, launch_coop_width and the
+    grid choice of launch_coop_variant, without their occupancy half (grid_fits: only the device knows; on a
+    device whose occupancy refuses the grid, Coop becomes Plain ungated, and "xcd" becomes "pe"). With
+    debug_abort the register kernel is skipped; a cooperative launch then sets the status word and returns,
+    and the answer is the gated plain kernel behind it, which computes the states."""
+    g = geometry(s, a, W, L, E)
     if g is None:
         return None
     Wp = g["Wpad"]
-    if Wp <= 256 and L - 1 <= _reg_max_hidden(Wp) and s + a <= 32 and s <= 32 and \
-            4 * (32 + 2 * Wp + 32 + 128 + H * a) <= 64 * 1024:
-        return "reg"
-    k0r = _coop_k0r(s, a)
-    if k0r and L >= 2 and W == Wp and Wp <= COOP_MAX_W and (Wp // COOP_ROWS) * E <= 1024 and \
-            _coop_lds_bytes(s, a, W, Wp, L, H, k0r) <= COOP_LDS_LIMIT:
-        return "coop"
-    return "plain"
+    if _reg_supported(s, a, Wp, L, H) and not debug_abort:
+        return Reg("reg", Wp, L - 1, 8 if s + a <= REG_K0_SPLIT else 32)
+    if _coop_supported(s, a, W, Wp, L, E, H):
+        if debug_abort:
+            return Plain("plain", True)
+        k0r = _coop_k0r(s, a)
+        sm = dict((k, m) for k, _, m in COOP_BUDGETS)[k0r]
+        hop = TRAJ_HOP_DEFAULT if traj_hop == 0 else traj_hop - 1
+        if hop >= 1 and E <= XCD_MAX_E:
+            return Coop("coop", k0r, sm, Wp // 32, "xcd", hop)
+        return Coop("coop", k0r, sm, Wp // 32, "pe", 0)
+    return Plain("plain", False)
+
+
+def trajectory_kernel(s, a, W, L, E=1, reward=0, *, H):
+    """'reg', 'coop' (where the workspace and the device's occupancy also allow it) or 'plain'."""
+    if geometry(s, a, W, L, E, reward) is None:
+        return None
+    return trajectory_instance(s, a, W, L, E, H=H).kernel

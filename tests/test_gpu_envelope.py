@@ -5,8 +5,10 @@ Accepted cases go through fused.rollout (mbrl_rollout_cost) against oracle.cem.r
 costs within test_gpu_parity.RTOL, states within rtol = atol = 1e-4. Cases with N >= 8192 must in addition
 equal, bit for bit, the same candidates rolled out as shards of at most 2048 (the README's promise that costs
 do not depend on the tile height), and are compared with the oracle on their first 64 candidates. Whole
-CEM plans, an MPPI plan and the single-trajectory kernels run at T = 16 and wide-input shapes at the fuzz
-test's bars. Refused cases must return MBRL_EUNSUPPORTED with the message the dispatch model predicts,
+CEM plans, an MPPI plan and the plain single-workgroup trajectory kernel (the shapes past both the register
+and the cooperative kernel's budgets) run at T = 16 and wide-input shapes at the fuzz test's bars; the
+single-trajectory kernels' own instance envelope -- every traj_reg_kernel and traj_coop_kernel instance,
+both cooperative grids, the hop modes -- is tests/test_gpu_traj_envelope.py. Refused cases must return MBRL_EUNSUPPORTED with the message the dispatch model predicts,
 launch nothing (sentinel-filled outputs untouched, a sampled call's actions_out included), and make the
 Python planners raise.
 
