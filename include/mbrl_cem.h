@@ -48,7 +48,8 @@ extern "C" {
  * open-loop loss (mbrl_train_open_loop_workspace_bytes, mbrl_train_grads_open_loop,
  * mbrl_train_epoch_open_loop), and global-norm gradient clipping for the ensemble epochs (mbrl_grad_clip,
  * mbrl_grad_clip_workspace_bytes, mbrl_grad_norm, mbrl_adam_step_clipped, mbrl_train_epoch_ensemble_clipped,
- * mbrl_train_epoch_open_loop_clipped). */
+ * mbrl_train_epoch_open_loop_clipped), and the device-resident transitions (mbrl_stack_field, mbrl_dataset_stack,
+ * mbrl_stats_field, mbrl_dataset_stats_workspace_bytes, mbrl_dataset_stats). */
 #define MBRL_ABI_VERSION 13
 
 typedef struct ihipStream_t* mbrl_stream_t; /* == hipStream_t */
@@ -1051,6 +1052,75 @@ typedef struct {
 int mbrl_keep_best(const float* loss, int32_t loss_stride, int32_t E, int32_t epoch, float* best_loss,
                    int32_t* best_epoch, int32_t* stale, const mbrl_copy_tensor* tensors, int32_t count,
                    mbrl_stream_t stream);
+
+/* ---- device-resident transitions (added within ABI v13, additively: no existing entry, struct, option or version
+ * number changes): the stacked training tensors and the normalisation statistics of a dataset whose steps live in
+ * device memory (mbrl_amd.device_data.DeviceTransitionsDataset), in place of the host's per-transition loops.
+ * Step store (the caller's device memory, fp32): one row-major array [S][dim] per field -- states, observations,
+ * actions, rewards. A rollout with K transitions occupies K + 1 consecutive rows; row k holds s_k, o_k, a_k, r_k. The
+ * action in a rollout's last row and the reward in its first row are padding and are never read.
+ *
+ * mbrl_dataset_stack: the stacked windows of up to 8 fields in ONE launch (the table travels in the launch
+ * arguments):
+ *   dst[t][h][j] = (src[win_row[t] + h + shift][j] - mean[j]) / std[j]      t < T, h < horizon, j < dim
+ * -- one fp32 subtraction and one correctly rounded fp32 division, the arithmetic of Rollout._norm -- or
+ * src[win_row[t] + h + shift][j] itself with NULL statistics. win_row: device int64 [T], the store row of each
+ * window's step 0 (not range-checked on the device: rows win_row[t] + shift .. win_row[t] + shift + horizon - 1 of
+ * every field must exist). Every element of every dst is written. src, dst, mean and std may sit at any 4-byte
+ * alignment: a workgroup walks 1024 consecutive dst elements, one dword per lane, so every load and store
+ * instruction of a wave covers 256 consecutive bytes on every alignment (there is no separate vector path). No
+ * workspace, no allocation, no synchronisation; stream-ordered and capturable.
+ * Before any launch: MBRL_EINVAL for a NULL table, win_row, src or dst, a mean without a std or the reverse, count
+ * outside 1 .. 8, T < 1, horizon < 1, dim < 1 or shift outside {0, 1}; MBRL_EUNSUPPORTED when T * horizon * dim >=
+ * 2^31 for any field. */
+typedef struct {
+    const float* src;   /* [S][dim] */
+    const float* mean;  /* [dim] or NULL */
+    const float* std;   /* [dim] or NULL (both or neither) */
+    float* dst;         /* [T][horizon][dim] */
+    int32_t dim;
+    int32_t shift;      /* 0: inputs (s, o, a); 1: outputs (r, s', o') */
+} mbrl_stack_field;
+int mbrl_dataset_stack(const mbrl_stack_field* fields, int32_t count, const int64_t* win_row, int64_t T,
+                       int32_t horizon, mbrl_stream_t stream);
+
+/* mbrl_dataset_stats: per field (up to 4 in a call) and per column j, over the store rows rows[0 .. R) of src (a
+ * device int64 list per field; rows may repeat and need no order): mean[j], the unbiased std[j], min[j] and max[j],
+ * four device arrays [dim]. x_i = src[rows[i]][j] is accumulated in float64 in one order that depends on R alone --
+ * the same for every column, whatever dim, the other fields and the pointers' alignment are:
+ *   - the list positions i are cut into chunks of 1024; absent positions of the last chunk contribute +0.0;
+ *   - in a chunk, lane t of 256 forms ((x[4t] + x[4t+1]) + x[4t+2]) + x[4t+3] and the 256 lane values meet in the
+ *     pairwise tree v[t] += v[t + d], d = 128, 64, .. 1;
+ *   - the chunk partials are reduced by mbrl_eval_members' rule: lane t of 1024 adds partials t, t + 1024, ..
+ *     ascending onto +0.0, then the pairwise tree d = 512, .. 1.
+ *   mean64 = sum / R stays in float64; a second pass sums (double(x_i) - mean64)^2 (each square rounded before it is
+ *   added) in the same order, absent positions again +0.0; std = sqrt(ss / (R - 1)). mean and std are rounded to fp32
+ *   once, at the end. R = 1 gives std = NaN, as torch.std does. min and max are exact. A NaN anywhere in a column
+ *   makes all four outputs NaN, as under torch; a column holding an inf has mean = +-inf (NaN with both signs) and
+ *   std = NaN.
+ * FOUR launches whatever count, R and dim are: the chunk sums with the chunk minima and maxima (one workgroup per
+ * chunk and four columns), one workgroup per column for mean64, mean, min and max, the chunk sums of squares, and one
+ * workgroup per column for std. No atomics; no workgroup waits on another. Stream-ordered and capturable: no
+ * allocation, no synchronisation.
+ * Workspace: >= mbrl_dataset_stats_workspace_bytes(fields, count) bytes (0 for a bad table; of each field it reads R
+ * and dim only), 8-byte aligned; any bytes on entry, no zeroing. It holds the chunk partials and mean64.
+ * Before any launch: MBRL_EINVAL for a NULL table, src, rows, output or workspace, a workspace that is not 8-byte
+ * aligned, count outside 1 .. 4 or R < 1; MBRL_EUNSUPPORTED for dim outside 1 .. MBRL_EVAL_MAX_DIM (or 2^29 or more
+ * chunks x column tiles in a field); MBRL_EWORKSPACE for a workspace that is too small. */
+typedef struct {
+    const float* src;     /* [S][dim] */
+    const int64_t* rows;  /* device [R] */
+    int64_t R;
+    float* mean;          /* [dim] each */
+    float* std;
+    float* min;
+    float* max;
+    int32_t dim;
+    int32_t _pad;
+} mbrl_stats_field;
+size_t mbrl_dataset_stats_workspace_bytes(const mbrl_stats_field* fields, int32_t count);
+int mbrl_dataset_stats(const mbrl_stats_field* fields, int32_t count, void* ws, size_t ws_bytes,
+                       mbrl_stream_t stream);
 
 #ifdef __cplusplus
 }

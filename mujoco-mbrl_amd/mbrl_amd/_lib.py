@@ -80,6 +80,7 @@ EXPORTED = (
     "mbrl_train_open_loop_workspace_bytes", "mbrl_train_grads_open_loop", "mbrl_train_epoch_open_loop",
     "mbrl_grad_clip_workspace_bytes", "mbrl_grad_norm", "mbrl_adam_step_clipped",
     "mbrl_train_epoch_ensemble_clipped", "mbrl_train_epoch_open_loop_clipped",
+    "mbrl_dataset_stack", "mbrl_dataset_stats_workspace_bytes", "mbrl_dataset_stats",
 )
 
 
@@ -168,6 +169,18 @@ class GradClip(ctypes.Structure):
                 ("ws_bytes", c_size_t)]
 
 
+class StackField(ctypes.Structure):
+    """mbrl_stack_field (include/mbrl_cem.h; added within ABI v13): one field of mbrl_dataset_stack's table."""
+    _fields_ = [("src", c_void_p), ("mean", c_void_p), ("std", c_void_p), ("dst", c_void_p), ("dim", c_int32),
+                ("shift", c_int32)]
+
+
+class StatsField(ctypes.Structure):
+    """mbrl_stats_field (include/mbrl_cem.h; added within ABI v13): one field of mbrl_dataset_stats' table."""
+    _fields_ = [("src", c_void_p), ("rows", c_void_p), ("R", c_int64), ("mean", c_void_p), ("std", c_void_p),
+                ("min", c_void_p), ("max", c_void_p), ("dim", c_int32), ("_pad", c_int32)]
+
+
 _lib = None
 
 
@@ -253,6 +266,10 @@ def load():
         "mbrl_eval_members_open_loop": (c_int32, [POINTER(TrainModel), c_int32, POINTER(TrainData), P, c_int64, P, P, P, P,
                                                   P]),
         "mbrl_keep_best": (c_int32, [P, c_int32, c_int32, c_int32, P, P, P, POINTER(CopyTensor), c_int32, P]),
+        # device-resident transitions: the stacked windows and the normalisation statistics
+        "mbrl_dataset_stack": (c_int32, [POINTER(StackField), c_int32, P, c_int64, c_int32, P]),
+        "mbrl_dataset_stats_workspace_bytes": (c_size_t, [POINTER(StatsField), c_int32]),
+        "mbrl_dataset_stats": (c_int32, [POINTER(StatsField), c_int32, P, c_size_t, P]),
         "mbrl_cem_plan": (c_int32, [POINTER(MlpShape), P, POINTER(Norm), POINTER(Cost), P, POINTER(CemParams),
                                     P, P, P, P, P, P, P, P, P, c_size_t, P]),
         "mbrl_mppi_update": (c_int32, [P, c_int32, c_int32, P, POINTER(Sampler), c_int32, c_int32, c_float, c_float,
@@ -473,4 +490,5 @@ __all__ = ["load", "check", "ptr", "stream_handle", "MlpShape", "Norm", "Cost", 
            "EXPORTED", "MBRL_NAN_LAST", "MBRL_NAN_FIRST", "MBRL_COST_GOAL_STATE", "MBRL_COST_MODEL_REWARD",
            "ABI_VERSION", "c_int64", "MBRL_PRECISION_F32", "MBRL_PRECISION_F16X3", "MBRL_PRECISION_F16X6",
            "precision_code", "load_other", "option", "OPTIONS", "AdamTensor", "AdamHparams",
-           "TrainModel", "TrainData", "TRAIN_MAX_LAYERS", "TRAIN_MAX_MEMBERS", "HostStaging", "CopyTensor"]
+           "TrainModel", "TrainData", "TRAIN_MAX_LAYERS", "TRAIN_MAX_MEMBERS", "HostStaging", "CopyTensor",
+           "StackField", "StatsField"]
