@@ -1,6 +1,6 @@
 // Per-member global-norm gradient clipping for the ensemble training epochs (include/mbrl_cem.h mbrl_grad_norm,
 // mbrl_grad_clip): torch.nn.utils.clip_grad_norm_(member.parameters(), max_norm) between backward() and
-// Adam.step(), as two launches whatever E, count and the shapes are, ahead of the clipped Adam launch (train.hip
+// Adam.step(), as two launches whatever E, count and the shapes are, ahead of the clipped Adam launch (adam.hip
 // adam_step_clipped_kernel).
 //
 // The sum of squares of member e's gradient tensors is taken in ONE order that depends on the tensors' numels alone

@@ -561,7 +561,7 @@ size_t traj_coop_xchg_bytes(const TrajArgs& A, int E);
 hipError_t launch_traj_coop(const TrajArgs& A, int E, unsigned long long* xchg, unsigned* status,
                             hipStream_t stream);
 
-// mbrl_adam_step (train.hip). AdamArith bits: which of torch's element-wise expressions its build
+// mbrl_adam_step (adam.hip). AdamArith bits: which of torch's element-wise expressions its build
 // contracts to a fused multiply-add; ADAM_ARITH_TORCH is the pattern pinned against torch.optim.Adam
 // on the MI355X (tests/test_gpu_train_adam.py).
 enum { ADAM_FMA_WD = 1, ADAM_FMA_LERP = 2, ADAM_FMA_ADDCMUL = 4, ADAM_FMA_ADDCDIV = 8 };
@@ -569,6 +569,12 @@ constexpr int ADAM_ARITH_TORCH = ADAM_FMA_WD | ADAM_FMA_LERP | ADAM_FMA_ADDCMUL 
 constexpr int ADAM_MAX_TENSORS = 32;   // tensors per launch (the table travels in the kernel arguments)
 hipError_t launch_adam_step(const mbrl_adam_tensor* tensors, int count, const mbrl_adam_hparams& hp, int arith,
                             hipStream_t stream);
+// The AdamArith bits MBRL_OPT_ADAM_ARITH selects (0: ADAM_ARITH_TORCH).
+int adam_arith();
+// An Adam table [E][count] whose every tensor a step can take (numel >= 0; with elements, all four pointers), or
+// MBRL_EINVAL naming the entry `what`, the member and the tensor. E == 0: one model's table of `count` tensors,
+// `what` naming the tensor as well ("adam_step: tensor").
+int adam_table_check(const char* what, const mbrl_adam_tensor* tensors, int E, int count);
 
 // mbrl_train_grads (train.hip): the MLP's loss gradient for one batch, n_hidden + 2 launches.
 struct TrainShape {
@@ -587,8 +593,8 @@ struct TrainTensors {
     const float *states, *actions, *next_states, *rewards;   // stacked transitions [T][H][.]
 };
 size_t train_ws_floats(const TrainShape& t, int batch);
-size_t train_status_offset(const TrainShape& t, int batch);   // bytes: the fused step's status word
-size_t train_counter_bytes(const TrainShape& t, int batch);   // the tickets and band counters (offset 0)
+// bytes: the fused step's status word; the tickets and band counters lie before it, from offset 0
+size_t train_status_offset(const TrainShape& t, int batch);
 // adam (optional): the step of every layer's weight and bias (linear1.weight, linear1.bias, ...)
 // folded into the backward launches, bit-identical to a separate mbrl_adam_step after the gradient.
 // With the layer-0 fold one layer's step cannot ride in this step's launches: it comes back in
@@ -616,20 +622,28 @@ struct TrainEnsemble {
     int64_t idx_stride;   // rows
     int loss_stride;      // floats
 };
+// What a step may add to the gradient launches; a caller names only what it sets.
+struct TrainStep {
+    const mbrl_adam_tensor* adam;   // with hp and arith
+    const mbrl_adam_hparams* hp;
+    int arith;
+    const mbrl_adam_tensor* prior;
+    int prior_n;
+    mbrl_adam_tensor* pending;
+    int* pending_n;
+    const TrainGather* gather;
+    const TrainEnsemble* ens;
+};
 hipError_t launch_train_grads(const TrainShape& t, const TrainTensors& w, const int64_t* idx, int batch,
-                              float* loss_out, float* ws, hipStream_t stream, const mbrl_adam_tensor* adam = nullptr,
-                              const mbrl_adam_hparams* hp = nullptr, int arith = 0,
-                              const mbrl_adam_tensor* prior = nullptr, int prior_n = 0,
-                              mbrl_adam_tensor* pending = nullptr, int* pending_n = nullptr,
-                              const TrainGather* gather = nullptr, const TrainEnsemble* ens = nullptr);
+                              float* loss_out, float* ws, hipStream_t stream, const TrainStep& step = TrainStep{});
 // train_open_loop.hip's weight-gradient launches (train.hip): layer `layer`'s dW = g^T x over K rows and db from
 // `colsum` [colsum_tiles][n_out], member e's g, x and colsum e * ens.ws_stride floats on, into members[e]'s
-// gradient buffers; and the ensemble epochs' Adam launch (64 tensors per launch).
+// gradient buffers; and the ensemble epochs' Adam launch (adam.hip; 64 tensors per launch).
 hipError_t launch_train_wgrads(const TrainShape& t, int layer, const float* g, const float* x, const float* colsum,
                                int colsum_tiles, int K, const TrainEnsemble& ens, hipStream_t stream);
 hipError_t launch_adam_step_ensemble(const mbrl_adam_tensor* tensors, int count, const mbrl_adam_hparams& hp,
                                      int arith, hipStream_t stream);
-// Global-norm clipping for the ensemble epochs (grad_clip.hip; the clipped Adam launch is train.hip's). tensors
+// Global-norm clipping for the ensemble epochs (grad_clip.hip; the clipped Adam launch is adam.hip's). tensors
 // [E][count]. grad_clip_table_check: E, count and the table (adam: param and moments required as well), with the
 // entries' codes; grad_clip_check: the mbrl_grad_clip struct and its workspace on top. launch_grad_clip_step: one
 // batch's norm launches (norms row `batch`, coef in the clip workspace) and the clipped Adam launch.

@@ -30,9 +30,9 @@
 #include <stdint.h>
 
 #include <algorithm>
-#include <vector>
 
 #include "eval_mlp.h"
+#include "mbrl_train.h"
 
 namespace mbrl {
 
@@ -318,73 +318,35 @@ static OlPlan ol_plan(const TrainShape& t, int E, int batch) {
     return p;
 }
 
-// The members' common shape inside the envelope (mbrl_eval_members_open_loop's, less what the backward
-// kernel's LDS cannot hold).
-static int ol_shape(const char* what, const mbrl_train_model* members, int32_t E, TrainShape* t) {
-    if (!members) return fail(MBRL_EINVAL, "%s: NULL members", what);
-    if (E < 1) return fail(MBRL_EINVAL, "%s: E = %d members", what, E);
-    if (E > MBRL_TRAIN_MAX_MEMBERS)
-        return fail(MBRL_EUNSUPPORTED, "%s: E = %d members exceeds MBRL_TRAIN_MAX_MEMBERS = %d", what, E,
-                    MBRL_TRAIN_MAX_MEMBERS);
-    const mbrl_train_model& m0 = members[0];
-    if (m0.state_dim < 1 || m0.action_dim < 0 || m0.hidden < 1 || m0.horizon < 1 || m0.n_hidden < 1 ||
-        (m0.reward_head != 0 && m0.reward_head != 1))
-        return fail(MBRL_EINVAL, "%s: bad shape (state %d, action %d, hidden %d x %d, horizon %d, reward %d)", what,
-                    m0.state_dim, m0.action_dim, m0.hidden, m0.n_hidden, m0.horizon, m0.reward_head);
-    for (int e = 1; e < E; ++e) {
-        const mbrl_train_model& b = members[e];
-        if (m0.state_dim != b.state_dim || m0.action_dim != b.action_dim || m0.hidden != b.hidden ||
-            m0.n_hidden != b.n_hidden || m0.reward_head != b.reward_head || m0.horizon != b.horizon)
-            return fail(MBRL_EINVAL, "%s: member %d's shape differs from member 0's", what, e);
-    }
-    if (m0.n_hidden + 2 > MBRL_TRAIN_MAX_LAYERS || m0.hidden > MBRL_EVAL_MAX_DIM || m0.state_dim > MBRL_EVAL_MAX_DIM ||
-        m0.action_dim > MBRL_EVAL_MAX_DIM || m0.state_dim + m0.action_dim > MBRL_EVAL_MAX_DIM)
+size_t ol_ws_floats(const TrainShape& t, int E, int batch) { return ol_plan(t, E, batch).floats; }
+
+// The members' common shape (ensemble_shape) inside the envelope: mbrl_eval_members_open_loop's, less what the
+// backward kernel's LDS cannot hold.
+int ol_envelope(const char* what, const TrainShape& t) {
+    if (t.L + 2 > MBRL_TRAIN_MAX_LAYERS || t.W > MBRL_EVAL_MAX_DIM || t.s > MBRL_EVAL_MAX_DIM ||
+        t.a > MBRL_EVAL_MAX_DIM || t.s + t.a > MBRL_EVAL_MAX_DIM)
         return fail(MBRL_EUNSUPPORTED, "%s: shape outside the envelope (state %d, action %d, hidden %d x %d; each of "
-                    "state, state + action and hidden <= %d, n_hidden <= %d)", what, m0.state_dim, m0.action_dim, m0.hidden,
-                    m0.n_hidden, MBRL_EVAL_MAX_DIM, MBRL_TRAIN_MAX_LAYERS - 2);
-    *t = TrainShape{};
-    t->s = m0.state_dim; t->a = m0.action_dim; t->W = m0.hidden; t->L = m0.n_hidden; t->reward = m0.reward_head;
-    t->H = m0.horizon;
-    t->split = 1;
-    const OlPlan p = ol_plan(*t, 1, 1);
+                    "state, state + action and hidden <= %d, n_hidden <= %d)", what, t.s, t.a, t.W, t.L,
+                    MBRL_EVAL_MAX_DIM, MBRL_TRAIN_MAX_LAYERS - 2);
+    const OlPlan p = ol_plan(t, 1, 1);
     if (p.lds_bwd > (size_t)OL_LDS_BYTES)
         return fail(MBRL_EUNSUPPORTED, "%s: the backward kernel needs %zu bytes of LDS for hidden %d x %d (32 rows of "
-                    "%d floats and %d column-sum rows of %d): more than %d", what, p.lds_bwd, m0.hidden, m0.n_hidden,
-                    p.ld, m0.n_hidden + 1, p.wacc, OL_LDS_BYTES);
+                    "%d floats and %d column-sum rows of %d): more than %d", what, p.lds_bwd, t.W, t.L, p.ld, t.L + 1,
+                    p.wacc, OL_LDS_BYTES);
     return MBRL_OK;
 }
 
-// NULL layers, and no parameter or gradient buffer bound twice (two members stepping one buffer would race)
-static int ol_members(const char* what, const mbrl_train_model* members, int32_t E, const TrainShape& t) {
-    const int layers = t.L + 1 + t.reward;
-    std::vector<const void*> seen;
-    for (int e = 0; e < E; ++e)
-        for (int l = 0; l < layers; ++l) {
-            const mbrl_train_model& m = members[e];
-            if (!m.weight[l] || !m.bias[l] || !m.weight_grad[l] || !m.bias_grad[l])
-                return fail(MBRL_EINVAL, "%s: member %d, layer %d: NULL weight, bias or gradient", what, e, l);
-            seen.insert(seen.end(), {m.weight[l], m.bias[l], m.weight_grad[l], m.bias_grad[l]});
-        }
-    std::sort(seen.begin(), seen.end());
-    if (std::adjacent_find(seen.begin(), seen.end()) != seen.end())
-        return fail(MBRL_EINVAL, "%s: a parameter or gradient pointer is bound twice", what);
-    return MBRL_OK;
-}
-
-static bool ol_data_ok(const mbrl_train_data* data, const TrainShape& t) {
-    return data && data->states && data->next_states && (t.a == 0 || data->actions) && (!t.reward || data->rewards);
-}
-
-static int ol_batch_ok(const char* what, int32_t E, int64_t batch, const TrainShape& t) {
+int ol_batch_ok(const char* what, int32_t E, int64_t batch, const TrainShape& t) {
     if ((int64_t)E * batch * t.H >= ((int64_t)1 << 31))
         return fail(MBRL_EUNSUPPORTED, "%s: E * batch * horizon = %d * %lld * %d is not below 2^31", what, E,
                     (long long)batch, t.H);
     return MBRL_OK;
 }
 
-// One batch's launches (checked arguments): forward, backward through time, L + 1 weight-gradient launches, loss.
+// One batch's launches (checked arguments; EnsembleBatch, the workspace laid out for `batch` itself): forward,
+// backward through time, L + 1 weight-gradient launches, loss.
 static hipError_t ol_launch(const TrainShape& t, const mbrl_train_model* members, int E, const mbrl_train_data* data,
-                            const int64_t* idx, int64_t idx_stride, int batch, float* loss_out, float* ws,
+                            const int64_t* idx, int64_t idx_stride, int /*bs*/, int batch, float* loss_out, float* ws,
                             hipStream_t stream) {
     const OlPlan p = ol_plan(t, E, batch);
     OlLaunch T{};
@@ -443,8 +405,9 @@ extern "C" {
 size_t mbrl_train_open_loop_workspace_bytes(const mbrl_train_model* members, int32_t E, int32_t batch) {
     TrainShape t;
     const char* what = "train_open_loop_workspace_bytes";
-    if (batch < 1 || ol_shape(what, members, E, &t) != MBRL_OK || ol_batch_ok(what, E, batch, t) != MBRL_OK) return 0;
-    return ol_plan(t, E, batch).floats * sizeof(float);
+    if (batch < 1 || ensemble_shape(what, members, E, true, &t) != MBRL_OK || ol_batch_ok(what, E, batch, t) != MBRL_OK)
+        return 0;
+    return ol_ws_floats(t, E, batch) * sizeof(float);
 }
 
 int mbrl_train_grads_open_loop(const mbrl_train_model* members, int32_t E, const mbrl_train_data* data,
@@ -452,66 +415,17 @@ int mbrl_train_grads_open_loop(const mbrl_train_model* members, int32_t E, const
                                size_t ws_bytes, mbrl_stream_t stream) {
     const char* what = "train_grads_open_loop";
     TrainShape t;
-    if (int rc = ol_shape(what, members, E, &t)) return rc;
-    if (!ol_data_ok(data, t) || !batch_idx || !workspace) return fail(MBRL_EINVAL, "%s: NULL argument", what);
+    if (int rc = ensemble_shape(what, members, E, true, &t)) return rc;
+    if (!train_data_ok(data, t) || !batch_idx || !workspace) return fail(MBRL_EINVAL, "%s: NULL argument", what);
     if (reinterpret_cast<uintptr_t>(workspace) & 15) return fail(MBRL_EINVAL, "%s: workspace not 16-byte aligned", what);
     if (batch < 1 || (int64_t)batch > data->transitions)
         return fail(MBRL_EINVAL, "%s: batch %d outside [1, %lld]", what, batch, (long long)data->transitions);
-    if (int rc = ol_members(what, members, E, t)) return rc;
+    if (int rc = ensemble_members(what, members, E, t)) return rc;
     if (int rc = ol_batch_ok(what, E, batch, t)) return rc;
-    const size_t need = ol_plan(t, E, batch).floats * sizeof(float);
+    const size_t need = ol_ws_floats(t, E, batch) * sizeof(float);
     if (ws_bytes < need) return fail(MBRL_EWORKSPACE, "%s: workspace %zu < %zu bytes", what, ws_bytes, need);
-    return hip_check(ol_launch(t, members, E, data, batch_idx, batch, batch, loss_out, static_cast<float*>(workspace),
-                               reinterpret_cast<hipStream_t>(stream)), what);
-}
-
-// mbrl_train_epoch_open_loop (clip == NULL) and mbrl_train_epoch_open_loop_clipped: one body, the Adam launch or the
-// norm launches and the clipped Adam launch per batch.
-static int train_epoch_open_loop(const char* what, bool clipped, const mbrl_train_model* members, int32_t E,
-                                 const mbrl_train_data* data, const int64_t* orders, int64_t rows, int32_t batch_size,
-                                 const mbrl_adam_tensor* tensors, int32_t count, const mbrl_adam_hparams* hparams,
-                                 const float* step_sizes, const float* bc2_sqrt, float* losses, void* workspace,
-                                 size_t ws_bytes, const mbrl_grad_clip* clip, mbrl_stream_t stream) {
-    TrainShape t;
-    if (int rc = ol_shape(what, members, E, &t)) return rc;
-    if (!ol_data_ok(data, t) || !orders || !workspace || !tensors || count < 1 || !hparams || !step_sizes || !bc2_sqrt)
-        return fail(MBRL_EINVAL, "%s: NULL argument", what);
-    if (reinterpret_cast<uintptr_t>(workspace) & 15) return fail(MBRL_EINVAL, "%s: workspace not 16-byte aligned", what);
-    if (batch_size < 1 || rows < 1 || rows > data->transitions)
-        return fail(MBRL_EINVAL, "%s: rows %lld / batch %d outside [1, %lld]", what, (long long)rows, batch_size,
-                    (long long)data->transitions);
-    if (int rc = ol_members(what, members, E, t)) return rc;
-    const int total = E * count;
-    for (int i = 0; i < total; ++i)
-        if (tensors[i].numel < 0 || (tensors[i].numel > 0 && (!tensors[i].param || !tensors[i].grad ||
-                                                              !tensors[i].exp_avg || !tensors[i].exp_avg_sq)))
-            return fail(MBRL_EINVAL, "%s: member %d, Adam tensor %d: NULL pointer or negative numel", what, i / count,
-                        i % count);
-    const int bs = (int)std::min<int64_t>(batch_size, rows);
-    if (int rc = ol_batch_ok(what, E, bs, t)) return rc;
-    const size_t need = ol_plan(t, E, bs).floats * sizeof(float);
-    if (ws_bytes < need) return fail(MBRL_EWORKSPACE, "%s: workspace %zu < %zu bytes", what, ws_bytes, need);
-    if (clipped)
-        if (int rc = grad_clip_check(what, clip, tensors, E, count)) return rc;
-    const int arith = opt(MBRL_OPT_ADAM_ARITH), ar = arith ? arith - 1 : ADAM_ARITH_TORCH;
-    const hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    std::vector<mbrl_adam_tensor> table(tensors, tensors + total);
-    const int64_t batches = (rows + batch_size - 1) / batch_size;
-    for (int64_t b = 0; b < batches; ++b) {
-        const int n = (int)std::min<int64_t>(batch_size, rows - b * batch_size);
-        if (int rc = hip_check(ol_launch(t, members, E, data, orders + b * batch_size, rows, n,
-                                         losses ? losses + 3 * (int64_t)E * b : nullptr, static_cast<float*>(workspace),
-                                         st), what))
-            return rc;
-        for (int i = 0; i < total; ++i) {
-            table[i].step_size = step_sizes[b * total + i];
-            table[i].bc2_sqrt = bc2_sqrt[b * total + i];
-        }
-        if (int rc = hip_check(clipped ? launch_grad_clip_step(table.data(), E, count, *hparams, ar, *clip, b, st)
-                                       : launch_adam_step_ensemble(table.data(), total, *hparams, ar, st), what))
-            return rc;
-    }
-    return MBRL_OK;
+    return hip_check(ol_launch(t, members, E, data, batch_idx, batch, batch, batch, loss_out,
+                               static_cast<float*>(workspace), reinterpret_cast<hipStream_t>(stream)), what);
 }
 
 int mbrl_train_epoch_open_loop(const mbrl_train_model* members, int32_t E, const mbrl_train_data* data,
@@ -519,8 +433,9 @@ int mbrl_train_epoch_open_loop(const mbrl_train_model* members, int32_t E, const
                                int32_t count, const mbrl_adam_hparams* hparams, const float* step_sizes,
                                const float* bc2_sqrt, float* losses, void* workspace, size_t ws_bytes,
                                mbrl_stream_t stream) {
-    return train_epoch_open_loop("train_epoch_open_loop", false, members, E, data, orders, rows, batch_size, tensors,
-                                 count, hparams, step_sizes, bc2_sqrt, losses, workspace, ws_bytes, nullptr, stream);
+    return train_epoch_members("train_epoch_open_loop", true, false, ol_launch, members, E, data, orders, rows,
+                               batch_size, tensors, count, hparams, step_sizes, bc2_sqrt, losses, workspace, ws_bytes,
+                               nullptr, stream);
 }
 
 int mbrl_train_epoch_open_loop_clipped(const mbrl_train_model* members, int32_t E, const mbrl_train_data* data,
@@ -528,8 +443,9 @@ int mbrl_train_epoch_open_loop_clipped(const mbrl_train_model* members, int32_t 
                                        const mbrl_adam_tensor* tensors, int32_t count, const mbrl_adam_hparams* hparams,
                                        const float* step_sizes, const float* bc2_sqrt, float* losses, void* workspace,
                                        size_t ws_bytes, mbrl_stream_t stream, const mbrl_grad_clip* clip) {
-    return train_epoch_open_loop("train_epoch_open_loop_clipped", true, members, E, data, orders, rows, batch_size,
-                                 tensors, count, hparams, step_sizes, bc2_sqrt, losses, workspace, ws_bytes, clip, stream);
+    return train_epoch_members("train_epoch_open_loop_clipped", true, true, ol_launch, members, E, data, orders, rows,
+                               batch_size, tensors, count, hparams, step_sizes, bc2_sqrt, losses, workspace, ws_bytes,
+                               clip, stream);
 }
 
 }  // extern "C"

@@ -1,4 +1,4 @@
-"""torch.optim.Adam.step() as one launch per parameter group (csrc/train.hip, mbrl_adam_step).
+"""torch.optim.Adam.step() as one launch per parameter group (csrc/adam.hip, mbrl_adam_step).
 
 The reference's training loop (models.py:53-93, 165-217) ends every batch with optimizer.step();
 the optimizer is torch.optim.Adam(model.parameters(), lr, weight_decay) or SGD (experiment.py:55-62).

@@ -1,4 +1,4 @@
-"""Model training on the GPU: mbrl_adam_step (csrc/train.hip) against
+"""Model training on the GPU: mbrl_adam_step (csrc/adam.hip) against
 torch.optim.Adam itself, and train_model's device paths against each other.
 
 mbrl_adam_step promises torch's Adam step bit for bit (parameters, exp_avg, exp_avg_sq, the CPU step

@@ -1,5 +1,5 @@
-"""Ensemble training on the GPU: mbrl_train_epoch_ensemble / mbrl_train_grads_ensemble (csrc/train.hip,
-the members on a grid axis of the multi-launch layout) against mbrl_train_epoch / mbrl_train_grads on each
+"""Ensemble training on the GPU: mbrl_train_epoch_ensemble / mbrl_train_grads_ensemble (csrc/train_api.hip;
+csrc/train.hip: the members on a grid axis of the multi-launch layout) against mbrl_train_epoch / mbrl_train_grads on each
 member alone with its own row order. The contract is equality bit for bit -- parameters, Adam state, the
 last gradients and every batch's losses -- so every comparison below is torch.equal on the raw tensors.
 Then EnsembleModel.train_members (the Python entry) against its member-by-member fallback, and the

@@ -365,7 +365,7 @@ def test_fused_step_random_shapes_bitwise(case):
     lo, hi = [(64, 128), (128, 255), (256, 512)][int(rng.integers(0, 3))]
     B = int(rng.integers(lo // H + 1, hi // H + 1))
     R = B * H
-    nw = 16 if R >= 256 else 8 if R > 128 else 4   # train.hip fold_waves: the fused step needs per == 2
+    nw = 16 if R >= 256 else 8 if R > 128 else 4   # fold_waves (csrc/train.hip): the fused step needs per == 2
     assert lo < R <= hi and (((R + 15) // 16 + nw - 1) // nw) == 2
     ds = _dataset(s, a, H, 3 * B + 5, seed=case)
     _, ins, outs = ds.stacked(DEV)

@@ -1,5 +1,5 @@
 """CPU: the float64 reference of tests/test_gpu_train_grad.py (train_grad_reference), its case table and
-the restatement of csrc/train.hip's dispatch (train_grad_cases). The hand-written backward pass is
+the restatement of the training sources' dispatch (train_grad_cases). The hand-written backward pass is
 autograd's; the table reaches every value of every dispatch dimension and both sides of every boundary,
 named; no ReLU of any case can change side between float32 and float64 (the rejection sampling held, and
 redrew at most a tenth of a case's transitions); and every case tells every applicable single mistake of
@@ -251,8 +251,10 @@ def test_table_covers_what_the_issue_names():
 
 def test_model_constants_are_the_sources():
     """A change of a threshold in launch_train_grads fails here, and sends its author to train_dispatch."""
-    with open(os.path.join(CSRC, "train.hip")) as f:
-        src = f.read()
+    src = ""
+    for name in ("mbrl_train.h", "train.hip", "train_fused.hip", "train_api.hip"):   # the training sources, together
+        with open(os.path.join(CSRC, name)) as f:
+            src += f.read()
 
     def one(pattern):
         assert len(re.findall(pattern, src)) == 1, pattern
@@ -274,5 +276,7 @@ def test_model_constants_are_the_sources():
     one(r"const bool xstage = !PLAIN && O\.mode == EPI_MASK && O\.fold && O\.fold_k0 <= FOLD_K0MAX;")
     one(r"K0 <= FOLD_K0MAX \? xs\[r - m0\]\[kk\] : O\.fold_x\[\(int64_t\)r \* K0 \+ kk\]")
     one(r"const int l_end = fold_nw \? 1 : 0;")
-    assert len(re.findall(r"if \(K0 <= 32\) hipLaunchKernelGGL", src)) == 4
-    assert len(re.findall(r"W >= 256\) \{", src)) == 2
+    one(r"const int kch = F\.K0 <= 32 \? 2 : 4;")
+    one(r"const int nw = F\.W >= 256 \? 16 : 4;")
+    one(r"K0 <= 32 \?")     # no second selection on either threshold
+    one(r"W >= 256 \?")

@@ -65,7 +65,7 @@ def test_shapes_reach_the_kernels_they_are_meant_to():
     # gd.hip gd_coop_supported's static half: the cooperative kernel takes W 64, L 2, s + a <= 32
     g = wc.GD["over"]
     assert g["W"] in (64, 128, 256, 512) and g["L"] >= 2 and g["s"] + g["a"] <= 32 and wc.GD["H"] == 3
-    # train.hip: the fused three-launch step at two hidden layers, batch x horizon rows
+    # fused_step (csrc/train.hip): the fused three-launch step at two hidden layers, batch x horizon rows
     assert wc.TRAIN["batch"] * wc.TRAIN["horizon"] == 260 and wc.TRAIN_ROWS % wc.TRAIN["batch"]
 
 

@@ -26,12 +26,13 @@ TAU_FACTOR = 32.0       # tau = TAU_FACTOR x max |z32 - z64| of the case: no |z6
 REDRAW_CAP = 0.10       # at most this share of a case's transitions was redrawn
 
 # ------------------------------------------------------------------------------------------------
-# Part one: csrc/train.hip's dispatch, restated (line numbers are train.hip's).
-TT = 32                 # :191  C tile edge
-FOLD_K0MAX = 64         # :193  the dW_0 fold stages its input rows in LDS up to this K0
-FUSED_WMAX = 512        # :1055
-FUSED_K0MAX = 64        # :1056
-FUSED_MAX_BANDS = 16    # :1835
+# Part one: the training sources' dispatch, restated (csrc/train.hip unless a comment names mbrl_train.h,
+# train_fused.hip or train_api.hip; functions are cited by name).
+TT = 32                 # mbrl_train.h  C tile edge
+FOLD_K0MAX = 64         # train.hip  the dW_0 fold stages its input rows in LDS up to this K0
+FUSED_WMAX = 512        # mbrl_train.h
+FUSED_K0MAX = 64        # mbrl_train.h
+FUSED_MAX_BANDS = 16    # mbrl_train.h
 OPTIONS = ("train_no_fold", "train_split", "train_fo", "train_xcd", "train_tile")
 
 # One GEMM launch: which layer's, the waves per workgroup (launch_waves), the C tile height in 32-row units
@@ -49,7 +50,7 @@ def _ceil(x, y):
 
 
 def fold_waves(R, L, fold):
-    """:1892-1896. The waves of the separate dW_0 launch when the fold reproduces it, else 0."""
+    """fold_waves. The waves of the separate dW_0 launch when the fold reproduces it, else 0."""
     if not fold or L < 1:
         return 0
     nw = 16 if R >= 256 else 8 if R > 128 else 4
@@ -58,14 +59,14 @@ def fold_waves(R, L, fold):
 
 
 def fused_step(s, a, W, L, reward, R, fold_nw, split):
-    """:1901-1907."""
+    """fused_step (both overloads)."""
     J, K0 = s + (1 if reward else 0), s + a
     return (not split and L == 2 and fold_nw > 0 and J <= TT and K0 <= FUSED_K0MAX and W <= FUSED_WMAX
             and _ceil(R, TT) <= FUSED_MAX_BANDS)
 
 
 def launch_waves(products):
-    """:1728-1734. products: [(K, is_weight_gradient)]."""
+    """launch_waves. products: [(K, is_weight_gradient)]."""
     kmax = max(k for k, _ in products)
     grad_rows = any(g and k == kmax for k, g in products)
     return 16 if kmax >= 256 else 8 if (kmax > 128 and grad_rows) else 4
@@ -75,21 +76,21 @@ def train_dispatch(s, a, W, L, reward, H, B, cu_count, opts=None, misaligned=(),
     """The dispatch key of one mbrl_train_grads call (ensemble: of mbrl_train_grads_ensemble's launches).
     opts: {option name: value} of OPTIONS; misaligned: the Linears (0 .. L, L + 1 = the reward head) whose
     weight is not 16-byte aligned -- for an ensemble member 0's, which direct() sees, with misaligned_any
-    those of any member (:1786; default: member 0's)."""
+    those of any member (launch_gemm_any; default: member 0's)."""
     opts = dict(opts or {})
     assert set(opts) <= set(OPTIONS), opts
     R, K0, J = B * H, s + a, s + (1 if reward else 0)
     tiles_r, tiles_w = _ceil(R, TT), _ceil(W, TT)
     tile = opts.get("train_tile", 0)
-    fold = not opts.get("train_no_fold", 0)                   # :2182
-    split = opts.get("train_split", 0) == 1                   # :2184
-    xcd_opt = opts.get("train_xcd", 0) == 1                   # :2183
-    fo = opts.get("train_fo", 0) != 1                         # :2185, :1983
-    if ensemble:                                              # :2317-2319
+    fold = not opts.get("train_no_fold", 0)                   # train_shape (train_api.hip)
+    split = opts.get("train_split", 0) == 1                   # train_shape
+    xcd_opt = opts.get("train_xcd", 0) == 1                   # train_shape
+    fo = opts.get("train_fo", 0) != 1                         # train_shape; launch_train_grads
+    if ensemble:                                              # ensemble_shape (train_api.hip)
         fold, split, xcd_opt = False, True, False
     bad0 = set(misaligned)                                    # what direct() sees
     bad = bad0 | set(misaligned_any or ())
-    wvec = lambda ld, seen, *layers: ld % 4 == 0 and not (set(layers) & seen)   # noqa: E731  :1707
+    wvec = lambda ld, seen, *layers: ld % 4 == 0 and not (set(layers) & seen)   # noqa: E731  direct()
     out_layers = (L, L + 1) if reward else (L,)
     fold_nw = fold_waves(R, L, fold)
     fused = fused_step(s, a, W, L, reward, R, fold_nw, split)
@@ -97,37 +98,37 @@ def train_dispatch(s, a, W, L, reward, H, B, cu_count, opts=None, misaligned=(),
     launches = []
 
     def add(name, nw, tmx, m0, vec_a, vec_b, kind0=False):
-        # :1754-1755: the XCD order needs whole groups of 8 64-row bands of product 0; :1795 never in an ensemble
+        # launch_gemm: the XCD order needs whole groups of 8 64-row bands of product 0; launch_gemm_any: never in an ensemble
         xcd = xcd_opt and _ceil(m0, TT * tmx) % (8 * (2 // tmx)) == 0
-        if kind0 and ensemble:                    # :1779-1793: one load path for all members
+        if kind0 and ensemble:                    # launch_gemm_any: one load path for all members
             vec_b = vec_b and not (set(kind0) & bad)
         launches.append(Launch(name, nw, tmx, xcd, vec_a, vec_b))
 
     if fused:
-        # :1990-2004: the wave count of the separate launches whose K is W; K0's chunks
+        # launch_train_fused (train_fused.hip): the wave count of the separate launches whose K is W; K0's chunks
         fused_key = Fused("fo" if fo else "split", 16 if W >= 256 else 4, 2 if K0 <= 32 else 4,
-                          wvec(K0, bad0, 0),              # :1217
-                          wvec(W, bad0, 1),               # :1191
-                          W % 4 == 0,                     # :1433 (act1 lies in the workspace: aligned)
-                          wvec(W, bad0, *out_layers))     # :1434
+                          wvec(K0, bad0, 0),              # fused_fwd vec0
+                          wvec(W, bad0, 1),               # fused_fwd vec1
+                          W % 4 == 0,                     # fused_out veca (act1 lies in the workspace: aligned)
+                          wvec(W, bad0, *out_layers))     # fused_out vecb
     else:
-        for l in range(L):                                    # :2008-2037
+        for l in range(L):                                    # launch_train_grads: the forward loop
             K = K0 if l == 0 else W
             add(f"fwd{l}", launch_waves([(K, False)]), 1, R, None if l == 0 else W % 4 == 0, wvec(K, bad0, l), kind0=(l,))
-        add("out", launch_waves([(W, False)]), 1, R, W % 4 == 0, wvec(W, bad0, *out_layers), kind0=out_layers)   # :2039-2054
-    l_end = 1 if fold_nw else 0                               # :2058
-    for l in range(L - 1 if fused else L, l_end - 1, -1):     # :2059
+        add("out", launch_waves([(W, False)]), 1, R, W % 4 == 0, wvec(W, bad0, *out_layers), kind0=out_layers)   # launch_train_grads: the output layer
+    l_end = 1 if fold_nw else 0                               # launch_train_grads
+    for l in range(L - 1 if fused else L, l_end - 1, -1):     # launch_train_grads: the backward loop
         n_out, n_in = (J if l == L else W), (K0 if l == 0 else W)
-        tiles32 = (tiles_r * tiles_w if l >= 1 else 0) + _ceil(n_out, TT) * _ceil(n_in, TT)          # :2066
+        tiles32 = (tiles_r * tiles_w if l >= 1 else 0) + _ceil(n_out, TT) * _ceil(n_in, TT)          # launch_train_grads
         big = l >= 1 and (n_out >= 256 or R >= 256)
-        tmx = 2 if (big and tiles32 > cu_count) else 1        # :2068
-        if tile == 32 or (tile == 64 and big):                # :2069
+        tmx = 2 if (big and tiles32 > cu_count) else 1        # launch_train_grads
+        if tile == 32 or (tile == 64 and big):                # launch_train_grads
             tmx = tile // 32
         products = ([(n_out, False)] if l >= 1 else []) + [(R, True)]
         nw = launch_waves(products)
-        assert tmx == 1 or nw == 16                           # :1756-1757
-        add(f"bwd{l}", nw, tmx, R if l >= 1 else n_out, (n_out % 4 == 0) if l >= 1 else None, None)   # :2074
-    fold_input = None if not fold_nw else "lds" if K0 <= FOLD_K0MAX else "global"      # :495, :723
+        assert tmx == 1 or nw == 16                           # launch_at_waves
+        add(f"bwd{l}", nw, tmx, R if l >= 1 else n_out, (n_out % 4 == 0) if l >= 1 else None, None)   # launch_train_grads
+    fold_input = None if not fold_nw else "lds" if K0 <= FOLD_K0MAX else "global"      # gemm_tile xstage, fold_dw0
     return Key(fold_nw, fold_input, fused_key, tuple(launches))
 
 
