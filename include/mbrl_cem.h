@@ -49,7 +49,9 @@ extern "C" {
  * mbrl_train_epoch_open_loop), and global-norm gradient clipping for the ensemble epochs (mbrl_grad_clip,
  * mbrl_grad_clip_workspace_bytes, mbrl_grad_norm, mbrl_adam_step_clipped, mbrl_train_epoch_ensemble_clipped,
  * mbrl_train_epoch_open_loop_clipped), and the device-resident transitions (mbrl_stack_field, mbrl_dataset_stack,
- * mbrl_stats_field, mbrl_dataset_stats_workspace_bytes, mbrl_dataset_stats). */
+ * mbrl_stats_field, mbrl_dataset_stats_workspace_bytes, mbrl_dataset_stats), and probabilistic members trained on
+ * the Gaussian negative log-likelihood (mbrl_nll_bounds, mbrl_train_nll_workspace_bytes, mbrl_train_grads_nll,
+ * mbrl_train_epoch_nll, mbrl_train_epoch_nll_clipped, mbrl_eval_members_nll). */
 #define MBRL_ABI_VERSION 13
 
 typedef struct ihipStream_t* mbrl_stream_t; /* == hipStream_t */
@@ -1031,6 +1033,82 @@ int mbrl_train_epoch_open_loop_clipped(const mbrl_train_model* members, int32_t 
                                        const mbrl_adam_tensor* tensors, int32_t count, const mbrl_adam_hparams* hparams,
                                        const float* step_sizes, const float* bc2_sqrt, float* losses, void* ws,
                                        size_t ws_bytes, mbrl_stream_t stream, const mbrl_grad_clip* clip);
+
+/* ---- probabilistic members: training on the Gaussian negative log-likelihood (added within ABI v13, additively: no
+ * existing entry, struct, option id or version number changes). A member is an mbrl_train_model with
+ * reward_head == 0 whose output layer weight[n_hidden] / bias[n_hidden] (and their gradients) is ONE head of
+ * 2 s rows, s = state_dim: [2 s][hidden] and [2 s]. Rows [0, s) are the predicted mean m, rows [s, 2 s) the raw
+ * log-variance r. The mean rows are the head's first s rows, so the same struct is a deterministic member for
+ * mbrl_eval_members, mbrl_mlp_pack and every planner: they read the mean and nothing else.
+ * Per member e, over the positions p = (b, h), b < B = batch, h < H = horizon, teacher forced as in mbrl_train_grads:
+ * with i = batch_idx[e][b] the input is (states[i][h], actions[i][h]) and the target y = next_states[i][h]. With
+ * softplus(x) = max(x, 0) + log1p(exp(-|x|)), sigmoid(x) = 1 / (1 + exp(-x)), fp32 throughout:
+ *   (m, r)  = the head's output on the trunk's last activation       mbrl_eval_members' fma chains, row by row
+ *   u_j     = max_lv_j - softplus(max_lv_j - r_j)
+ *   lv_j    = min_lv_j + softplus(u_j - min_lv_j)                    the bounded log-variance, in (min_lv, max_lv)
+ *   row_nll[e][b][h] = sum_j [ (m_j - y_j)^2 * exp(-lv_j) + lv_j ]   j ascending, no contraction
+ *   row_err[e][b][h] = sum_j (m_j - y_j)^2                           mbrl_eval_members' value, byte for byte
+ *   row_lv [e][b][h] = sum_j lv_j
+ *   loss_out[e] = (nll, mse, mean_lv), each sum_h (sum_b row_*[e][b][h]) / (B s) in mbrl_eval_members' summation
+ *                 order: the project's scale, so the NLL and the MSE curves sit beside each other (the constant
+ *                 s H log(2 pi) / 2 and the factor 1/2 of the textbook density are left out).
+ * The gradient of nll with respect to the head's outputs:
+ *   dm_j = 2 (m_j - y_j) exp(-lv_j) / (B s)
+ *   dr_j = (1 - (m_j - y_j)^2 exp(-lv_j)) / (B s) * sigmoid(u_j - min_lv_j) * sigmoid(max_lv_j - r_j)
+ * and the *_grad arrays receive d nll / d parameter (overwritten). The bounds are read only: they are not trained.
+ * The deltas of the hidden layers (delta_l = (delta_{l+1} W_{l+1}) masked by the activation) are n-ordered chains
+ * accumulated in fp64 from the fp32 deltas and weights and rounded to fp32 once: exp(-lv) makes their terms cancel.
+ * bounds: min_logvar and max_logvar, device [s] each, shared by the E members.
+ * mbrl_eval_members_nll: the same values forward only, on rows[0..R) for every member (mbrl_eval_members'
+ * arguments); row_nll, row_err and row_lv are [E][R][H] device outputs, all three required (there is no workspace
+ * for the third); loss_out [E][3] or NULL. It runs the gradient entry's forward kernel with its stores switched
+ * off, so the gradient entry's loss_out[e] and row values equal this entry's on rows = batch_idx[e], R = batch, byte
+ * for byte; row_err equals mbrl_eval_members' on the same struct.
+ * Members, data, batch_idx [E][batch], orders [E][rows], tensors, step_sizes, bc2_sqrt, loss_out [E][3], losses
+ * [batches][E][3] and clip as for mbrl_train_grads_open_loop / mbrl_train_epoch_open_loop(_clipped), and every
+ * contract of those entries holds: member e's gradients, losses and row values depend, byte for byte, on member
+ * e's parameters and rows alone -- not on E or the other members (a non-finite one included); two calls return
+ * the same bytes; no floating-point atomics; no workgroup waits on another; stream-ordered and capturable, no
+ * allocation. ws: >= mbrl_train_nll_workspace_bytes(members, E, batch) bytes (0 for a bad shape), 16-byte aligned,
+ * any bytes on entry, no zeroing, no status word. After the call it begins with the row values: row_nll, row_err
+ * and row_lv, each [E][batch][H] floats, each starting on a multiple of 64 floats (up64(E batch H) apart).
+ * Summation orders: a weight gradient sums the B * H positions
+ * p = b * H + h in the order of mbrl_train_grads' weight-gradient product over K = B * H rows; a bias gradient adds,
+ * per 16-position tile, the valid positions ascending and then the tiles ascending.
+ * Launches per batch, whatever E, batch and horizon are: n_hidden + 4 in mbrl_train_grads_nll (forward, backward,
+ * n_hidden + 1 weight-gradient launches, the loss; one fewer with loss_out == NULL), n_hidden + 5 in
+ * mbrl_train_epoch_nll (the Adam launch, 64 tensors per launch) and two more in mbrl_train_epoch_nll_clipped;
+ * two in mbrl_eval_members_nll (one with loss_out == NULL).
+ * Envelope: mbrl_eval_members' (state_dim, state_dim + action_dim and hidden <= MBRL_EVAL_MAX_DIM, n_hidden <=
+ * MBRL_TRAIN_MAX_LAYERS - 2, action_dim = 0 with NULL actions, parameters and gradients at any 4-byte alignment)
+ * less what the two 16-position activation buffers in LDS (160 KiB) cannot hold with a head of 2 s outputs: with
+ * up16(x) = x rounded up to a multiple of 16,
+ *   ld = up16(max(hidden, state_dim + action_dim, 2 state_dim)) + 4,   32 ld <= 40960 floats
+ * (state_dim <= 632; hidden = 1024 with every n_hidden); beyond it MBRL_EUNSUPPORTED. Before any launch: the
+ * argument checks and error codes of the open-loop entries (mbrl_eval_members' for mbrl_eval_members_nll), and
+ * MBRL_EINVAL for NULL bounds, a NULL bound array, reward_head != 0 or a NULL row_nll / row_lv. */
+typedef struct {
+    const float* min_logvar;   /* device [state_dim] */
+    const float* max_logvar;   /* device [state_dim] */
+} mbrl_nll_bounds;
+size_t mbrl_train_nll_workspace_bytes(const mbrl_train_model* members, int32_t E, int32_t batch);
+int mbrl_train_grads_nll(const mbrl_train_model* members, int32_t E, const mbrl_train_data* data,
+                         const int64_t* batch_idx, int32_t batch, const mbrl_nll_bounds* bounds, float* loss_out,
+                         void* ws, size_t ws_bytes, mbrl_stream_t stream);
+int mbrl_train_epoch_nll(const mbrl_train_model* members, int32_t E, const mbrl_train_data* data,
+                         const int64_t* orders, int64_t rows, int32_t batch_size, const mbrl_adam_tensor* tensors,
+                         int32_t count, const mbrl_adam_hparams* hparams, const float* step_sizes,
+                         const float* bc2_sqrt, float* losses, void* ws, size_t ws_bytes, mbrl_stream_t stream,
+                         const mbrl_nll_bounds* bounds);
+int mbrl_train_epoch_nll_clipped(const mbrl_train_model* members, int32_t E, const mbrl_train_data* data,
+                                 const int64_t* orders, int64_t rows, int32_t batch_size,
+                                 const mbrl_adam_tensor* tensors, int32_t count, const mbrl_adam_hparams* hparams,
+                                 const float* step_sizes, const float* bc2_sqrt, float* losses, void* ws,
+                                 size_t ws_bytes, mbrl_stream_t stream, const mbrl_nll_bounds* bounds,
+                                 const mbrl_grad_clip* clip);
+int mbrl_eval_members_nll(const mbrl_train_model* members, int32_t E, const mbrl_train_data* data,
+                          const int64_t* rows, int64_t R, const mbrl_nll_bounds* bounds, float* row_nll,
+                          float* row_err, float* row_lv, float* loss_out, mbrl_stream_t stream);
 
 /* Keep-best snapshots: per member e, v = loss[e * loss_stride] (device) against best_loss[e] AS IT WAS ON
  * ENTRY. If v < best_loss[e] (a NaN is never better): best_loss[e] = v, best_epoch[e] = epoch,

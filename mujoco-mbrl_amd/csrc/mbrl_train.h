@@ -102,31 +102,40 @@ struct FusedArgs {
 // F and O for a filled FusedArgs (train_fused.hip): one launch, or two with fo_split (MBRL_OPT_TRAIN_FO = 1).
 hipError_t launch_train_fused(const FusedArgs& F, bool fo_split, hipStream_t stream);
 
-// ---- the entries' checks (train_api.hip), one copy for one model, for ensembles and for both loss kinds
+// ---- the entries' checks (train_api.hip), one copy for one model, for ensembles and for every loss kind
+// The ensemble entries' loss: the teacher-forced MSE of mbrl_train_grads (the tiled launches of train.hip), the
+// open-loop MSE (train_open_loop.hip) and the Gaussian negative log-likelihood (train_nll.hip).
+enum TrainLoss { LOSS_ONE_STEP = 0, LOSS_OPEN_LOOP = 1, LOSS_NLL = 2 };
 // The transitions' pointers a model of shape t reads.
 bool train_data_ok(const mbrl_train_data* data, const TrainShape& t);
 // The members' common shape in the layout the ensemble launches run: the multi-launch one, the layer-0
-// weight gradient in its own launch (the only layout without a wait between workgroups). open_loop: the
-// open-loop loss's envelope (ol_envelope) after the member comparison, and no launch option read.
-int ensemble_shape(const char* what, const mbrl_train_model* members, int32_t E, bool open_loop, TrainShape* t);
+// weight gradient in its own launch (the only layout without a wait between workgroups). LOSS_OPEN_LOOP and
+// LOSS_NLL: the kind's envelope (ol_envelope, nll_envelope) after the member comparison, and no launch option
+// read; LOSS_NLL: a reward head is MBRL_EINVAL.
+int ensemble_shape(const char* what, const mbrl_train_model* members, int32_t E, TrainLoss kind, TrainShape* t);
 // NULL layers, and no parameter or gradient buffer bound twice (two members stepping one buffer would race)
 int ensemble_members(const char* what, const mbrl_train_model* members, int32_t E, const TrainShape& t);
 // One batch of an ensemble epoch: n transitions per member from rows idx (member e's idx_stride rows on), in a
-// workspace laid out for batches of up to bs.
+// workspace laid out for batches of up to bs. bounds: LOSS_NLL's log-variance bounds, NULL for the other kinds.
 typedef hipError_t (*EnsembleBatch)(const TrainShape& t, const mbrl_train_model* members, int E,
                                     const mbrl_train_data* data, const int64_t* idx, int64_t idx_stride, int bs, int n,
-                                    float* loss_out, float* ws, hipStream_t stream);
-// The four ensemble epoch entries (mbrl_cem.h's arguments): the checks, then per batch `launch`, the Adam table's
+                                    float* loss_out, float* ws, const mbrl_nll_bounds* bounds, hipStream_t stream);
+// The six ensemble epoch entries (mbrl_cem.h's arguments): the checks, then per batch `launch`, the Adam table's
 // refresh and the members' Adam launch -- or, clipped, the norm launches and the clipped Adam launch.
-int train_epoch_members(const char* what, bool open_loop, bool clipped, EnsembleBatch launch,
+int train_epoch_members(const char* what, TrainLoss kind, bool clipped, EnsembleBatch launch,
                         const mbrl_train_model* members, int32_t E, const mbrl_train_data* data, const int64_t* orders,
                         int64_t rows, int32_t batch_size, const mbrl_adam_tensor* tensors, int32_t count,
                         const mbrl_adam_hparams* hparams, const float* step_sizes, const float* bc2_sqrt, float* losses,
-                        void* workspace, size_t ws_bytes, const mbrl_grad_clip* clip, mbrl_stream_t stream);
+                        void* workspace, size_t ws_bytes, const mbrl_grad_clip* clip, const mbrl_nll_bounds* bounds,
+                        mbrl_stream_t stream);
 // The open-loop kind's own checks and workspace (train_open_loop.hip): the shape envelope, E * batch * horizon
 // below 2^31, the floats for E members of `batch` transitions.
 int ol_envelope(const char* what, const TrainShape& t);
 int ol_batch_ok(const char* what, int32_t E, int64_t batch, const TrainShape& t);
 size_t ol_ws_floats(const TrainShape& t, int E, int batch);
+// The same for the Gaussian NLL (train_nll.hip); nll_bounds_ok: the bounds struct and both of its arrays.
+int nll_envelope(const char* what, const TrainShape& t);
+size_t nll_ws_floats(const TrainShape& t, int E, int batch);
+bool nll_bounds_ok(const mbrl_nll_bounds* bounds);
 
 }  // namespace mbrl

@@ -1,6 +1,6 @@
 // Training ABI entries (include/mbrl_cem.h): argument checks around the launchers of train.hip and adam.hip, for
-// one model and for ensembles, and the ensemble epoch driver both loss kinds share (train_open_loop.hip's entries
-// call it too).
+// one model and for ensembles, and the ensemble epoch driver every loss kind shares (train_open_loop.hip's and
+// train_nll.hip's entries call it too).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -12,8 +12,8 @@
 
 namespace mbrl {
 
-// open_loop: the open-loop loss bounds n_hidden with its envelope (ol_envelope, MBRL_EUNSUPPORTED) and its
-// launches read no option.
+// open_loop (the open-loop and NLL kinds): the kind bounds n_hidden with its envelope (ol_envelope, nll_envelope:
+// MBRL_EUNSUPPORTED) and its launches read no option.
 static int train_shape(const char* what, const mbrl_train_model* m, bool open_loop, TrainShape* t) {
     if (!m) return fail(MBRL_EINVAL, "%s: NULL model", what);
     if (m->state_dim < 1 || m->action_dim < 0 || m->hidden < 1 || m->horizon < 1 || m->n_hidden < 1 ||
@@ -52,7 +52,8 @@ static TrainTensors train_tensors(const mbrl_train_model& m, const mbrl_train_da
 
 // ---- ensembles: E members in shared launches (train_gemm_ens_kernel)
 
-int ensemble_shape(const char* what, const mbrl_train_model* members, int32_t E, bool open_loop, TrainShape* t) {
+int ensemble_shape(const char* what, const mbrl_train_model* members, int32_t E, TrainLoss kind, TrainShape* t) {
+    const bool open_loop = kind != LOSS_ONE_STEP;
     if (!members) return fail(MBRL_EINVAL, "%s: NULL members", what);
     if (E < 1) return fail(MBRL_EINVAL, "%s: E = %d members", what, E);
     if (E > MBRL_TRAIN_MAX_MEMBERS)
@@ -68,7 +69,9 @@ int ensemble_shape(const char* what, const mbrl_train_model* members, int32_t E,
     t->fold = 0;
     t->split = 1;
     t->xcd = 0;
-    return open_loop ? ol_envelope(what, *t) : MBRL_OK;
+    if (kind == LOSS_NLL && t->reward)
+        return fail(MBRL_EINVAL, "%s: the NLL members have one head of 2 * state_dim rows: reward_head must be 0", what);
+    return kind == LOSS_OPEN_LOOP ? ol_envelope(what, *t) : kind == LOSS_NLL ? nll_envelope(what, *t) : MBRL_OK;
 }
 
 int ensemble_members(const char* what, const mbrl_train_model* members, int32_t E, const TrainShape& t) {
@@ -88,23 +91,26 @@ int ensemble_members(const char* what, const mbrl_train_model* members, int32_t 
 // The closed-loop kind's batch (EnsembleBatch): launch_train_grads with the members on a grid axis.
 static hipError_t ensemble_batch(const TrainShape& t, const mbrl_train_model* members, int E,
                                  const mbrl_train_data* data, const int64_t* idx, int64_t idx_stride, int bs, int n,
-                                 float* loss_out, float* ws, hipStream_t stream) {
+                                 float* loss_out, float* ws, const mbrl_nll_bounds* /*bounds*/, hipStream_t stream) {
     const TrainEnsemble ens{members, E, (int64_t)train_ws_floats(t, bs), idx_stride, 3};
     TrainStep step{};
     step.ens = &ens;
     return launch_train_grads(t, train_tensors(members[0], *data), idx, n, loss_out, ws, stream, step);
 }
 
-int train_epoch_members(const char* what, bool open_loop, bool clipped, EnsembleBatch launch,
+int train_epoch_members(const char* what, TrainLoss kind, bool clipped, EnsembleBatch launch,
                         const mbrl_train_model* members, int32_t E, const mbrl_train_data* data, const int64_t* orders,
                         int64_t rows, int32_t batch_size, const mbrl_adam_tensor* tensors, int32_t count,
                         const mbrl_adam_hparams* hparams, const float* step_sizes, const float* bc2_sqrt, float* losses,
-                        void* workspace, size_t ws_bytes, const mbrl_grad_clip* clip, mbrl_stream_t stream) {
+                        void* workspace, size_t ws_bytes, const mbrl_grad_clip* clip, const mbrl_nll_bounds* bounds,
+                        mbrl_stream_t stream) {
     TrainShape t;
-    if (int rc = ensemble_shape(what, members, E, open_loop, &t)) return rc;
+    const bool open_loop = kind != LOSS_ONE_STEP;   // (the kinds whose launches read 16 bytes at a time)
+    if (int rc = ensemble_shape(what, members, E, kind, &t)) return rc;
     if (!train_data_ok(data, t) || !orders || !workspace || !tensors || count < 1 || !hparams || !step_sizes ||
         !bc2_sqrt)
         return fail(MBRL_EINVAL, "%s: NULL argument", what);
+    if (kind == LOSS_NLL && !nll_bounds_ok(bounds)) return fail(MBRL_EINVAL, "%s: NULL log-variance bounds", what);
     if (open_loop && (reinterpret_cast<uintptr_t>(workspace) & 15))
         return fail(MBRL_EINVAL, "%s: workspace not 16-byte aligned", what);
     if (batch_size < 1 || rows < 1 || rows > data->transitions)
@@ -115,7 +121,9 @@ int train_epoch_members(const char* what, bool open_loop, bool clipped, Ensemble
     const int bs = (int)std::min<int64_t>(batch_size, rows);
     if (open_loop)
         if (int rc = ol_batch_ok(what, E, bs, t)) return rc;
-    const size_t need = (open_loop ? ol_ws_floats(t, E, bs) : (size_t)E * train_ws_floats(t, bs)) * sizeof(float);
+    const size_t need = (kind == LOSS_OPEN_LOOP ? ol_ws_floats(t, E, bs)
+                         : kind == LOSS_NLL     ? nll_ws_floats(t, E, bs)
+                                                : (size_t)E * train_ws_floats(t, bs)) * sizeof(float);
     if (ws_bytes < need) return fail(MBRL_EWORKSPACE, "%s: workspace %zu < %zu bytes", what, ws_bytes, need);
     if (clipped)
         if (int rc = grad_clip_check(what, clip, tensors, E, count)) return rc;
@@ -127,7 +135,7 @@ int train_epoch_members(const char* what, bool open_loop, bool clipped, Ensemble
         const int n = (int)std::min<int64_t>(batch_size, rows - b * batch_size);
         if (int rc = hip_check(launch(t, members, E, data, orders + b * batch_size, rows, bs, n,
                                       losses ? losses + 3 * (int64_t)E * b : nullptr, static_cast<float*>(workspace),
-                                      st), what))
+                                      bounds, st), what))
             return rc;
         for (int i = 0; i < total; ++i) {
             table[i].step_size = step_sizes[b * total + i];
@@ -260,7 +268,7 @@ int mbrl_train_epoch(const mbrl_train_model* model, const mbrl_train_data* data,
 
 size_t mbrl_train_ensemble_workspace_bytes(const mbrl_train_model* members, int32_t E, int32_t batch) {
     TrainShape t;
-    if (batch < 1 || ensemble_shape("train_ensemble_workspace_bytes", members, E, false, &t) != MBRL_OK) return 0;
+    if (batch < 1 || ensemble_shape("train_ensemble_workspace_bytes", members, E, LOSS_ONE_STEP, &t) != MBRL_OK) return 0;
     return (size_t)E * train_ws_floats(t, batch) * sizeof(float);
 }
 
@@ -269,7 +277,7 @@ int mbrl_train_grads_ensemble(const mbrl_train_model* members, int32_t E, const 
                               size_t ws_bytes, mbrl_stream_t stream) {
     const char* what = "train_grads_ensemble";
     TrainShape t;
-    if (int rc = ensemble_shape(what, members, E, false, &t)) return rc;
+    if (int rc = ensemble_shape(what, members, E, LOSS_ONE_STEP, &t)) return rc;
     if (!train_data_ok(data, t) || !batch_idx || !workspace) return fail(MBRL_EINVAL, "%s: NULL argument", what);
     if (batch < 1 || (int64_t)batch > data->transitions)
         return fail(MBRL_EINVAL, "%s: batch %d outside [1, %lld]", what, batch, (long long)data->transitions);
@@ -277,7 +285,7 @@ int mbrl_train_grads_ensemble(const mbrl_train_model* members, int32_t E, const 
     const size_t need = (size_t)E * train_ws_floats(t, batch) * sizeof(float);
     if (ws_bytes < need) return fail(MBRL_EWORKSPACE, "%s: workspace %zu < %zu bytes", what, ws_bytes, need);
     return hip_check(ensemble_batch(t, members, E, data, batch_idx, batch, batch, batch, loss_out,
-                                    static_cast<float*>(workspace), reinterpret_cast<hipStream_t>(stream)), what);
+                                    static_cast<float*>(workspace), nullptr, reinterpret_cast<hipStream_t>(stream)), what);
 }
 
 int mbrl_train_epoch_ensemble(const mbrl_train_model* members, int32_t E, const mbrl_train_data* data,
@@ -285,9 +293,9 @@ int mbrl_train_epoch_ensemble(const mbrl_train_model* members, int32_t E, const 
                               int32_t count, const mbrl_adam_hparams* hparams, const float* step_sizes,
                               const float* bc2_sqrt, float* losses, void* workspace, size_t ws_bytes,
                               mbrl_stream_t stream) {
-    return train_epoch_members("train_epoch_ensemble", false, false, ensemble_batch, members, E, data, orders, rows,
-                               batch_size, tensors, count, hparams, step_sizes, bc2_sqrt, losses, workspace, ws_bytes,
-                               nullptr, stream);
+    return train_epoch_members("train_epoch_ensemble", LOSS_ONE_STEP, false, ensemble_batch, members, E, data, orders,
+                               rows, batch_size, tensors, count, hparams, step_sizes, bc2_sqrt, losses, workspace,
+                               ws_bytes, nullptr, nullptr, stream);
 }
 
 int mbrl_train_epoch_ensemble_clipped(const mbrl_train_model* members, int32_t E, const mbrl_train_data* data,
@@ -295,9 +303,9 @@ int mbrl_train_epoch_ensemble_clipped(const mbrl_train_model* members, int32_t E
                                       const mbrl_adam_tensor* tensors, int32_t count, const mbrl_adam_hparams* hparams,
                                       const float* step_sizes, const float* bc2_sqrt, float* losses, void* workspace,
                                       size_t ws_bytes, mbrl_stream_t stream, const mbrl_grad_clip* clip) {
-    return train_epoch_members("train_epoch_ensemble_clipped", false, true, ensemble_batch, members, E, data, orders,
-                               rows, batch_size, tensors, count, hparams, step_sizes, bc2_sqrt, losses, workspace,
-                               ws_bytes, clip, stream);
+    return train_epoch_members("train_epoch_ensemble_clipped", LOSS_ONE_STEP, true, ensemble_batch, members, E, data,
+                               orders, rows, batch_size, tensors, count, hparams, step_sizes, bc2_sqrt, losses,
+                               workspace, ws_bytes, clip, nullptr, stream);
 }
 
 }  // extern "C"

@@ -33,12 +33,9 @@
 
 #include "eval_mlp.h"
 #include "mbrl_train.h"
+#include "train_bptt.h"
 
 namespace mbrl {
-
-constexpr int OL_TM = 16;            // rows of the batch per workgroup: the MFMA's 16 columns (eval.hip's EVAL_TM)
-constexpr int OL_THREADS = 64 * EVAL_WAVES;
-constexpr int OL_LDS_BYTES = 160 * 1024;
 
 struct OlLaunch {
     EvalLaunch A;                         // A.rows: member 0's batch rows; A.P = batch; row_err [E][B][H]
@@ -52,23 +49,6 @@ struct OlLaunch {
     float scale_s, scale_r;
     int wacc;                             // floats per LDS column-sum row: max(W, J) rounded up to 16
 };
-
-// rows [0, n) x columns [0, width) of an LDS buffer to dst[row * width + col]
-__device__ __forceinline__ void ol_store_rows(const float* buf, int ld, float* dst, int width, int n) {
-    if ((width & 3) == 0) {
-        const int w4 = width >> 2;
-        for (int idx = threadIdx.x; idx < n * w4; idx += OL_THREADS) {
-            const int row = idx / w4, k = (idx - row * w4) * 4;
-            *reinterpret_cast<eval_f32x4*>(dst + (int64_t)row * width + k) =
-                *reinterpret_cast<const eval_f32x4*>(buf + row * ld + k);
-        }
-    } else {
-        for (int idx = threadIdx.x; idx < n * width; idx += OL_THREADS) {
-            const int row = idx / width, k = idx - row * width;
-            dst[(int64_t)row * width + k] = buf[row * ld + k];
-        }
-    }
-}
 
 __global__ __launch_bounds__(OL_THREADS) void train_ol_fwd_kernel(const OlLaunch T) {
     extern __shared__ __attribute__((aligned(16))) float ol_lds[];
@@ -133,96 +113,6 @@ __global__ __launch_bounds__(OL_THREADS) void train_ol_fwd_kernel(const OlLaunch
             T.gout[by + (p0 + row) * J + j] = v;
         }
         __syncthreads();                                  // the outputs are read: the next step may overwrite column s
-    }
-}
-
-// out[p][m] = (sum_n in[p][n] w[n][m]) (* (mask[p][m] > 0)) for the tile's 16 positions and m < Kout, rows n < n0
-// of the weights from w0 and n0 <= n < n0 + n1 from w1, both with ldw floats per row; columns from Kout to the
-// next multiple of 16 are written as zeros. mask and store are the tile's rows of [.][ldo] arrays in global
-// memory (NULL: none); rows past nvalid mask to zero and are not stored.
-__device__ __forceinline__ void bptt_layer(const float* __restrict__ in, float* __restrict__ out, int ld,
-                                           const float* __restrict__ w0, int n0, const float* __restrict__ w1, int n1,
-                                           int ldw, int Kout, const float* __restrict__ mask, float* __restrict__ store,
-                                           int ldo, int nvalid) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c = lane & 15, q = lane >> 4;
-    const int N = n0 + n1, N16 = (N + 15) & ~15, MB = (Kout + 15) >> 4;
-    const bool vec = (ldo & 3) == 0;
-    for (int mb0 = wave * EVAL_JB; mb0 < MB; mb0 += EVAL_WAVES * EVAL_JB) {
-        eval_f32x4 acc[EVAL_JB], keep[EVAL_JB];
-        float w1v[EVAL_JB];
-#pragma unroll
-        for (int j = 0; j < EVAL_JB; ++j) {
-            acc[j] = eval_f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-            keep[j] = eval_f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-            w1v[j] = 0.0f;
-            if (n1 && (mb0 + j) * 16 + c < Kout) w1v[j] = w1[(mb0 + j) * 16 + c];
-            // the ReLU mask's activations, ahead of the products
-            const int mbase = (mb0 + j) * 16 + 4 * q;
-            if (mask && mb0 + j < MB && c < nvalid) {
-                if (vec && mbase + 3 < Kout) {
-                    keep[j] = *reinterpret_cast<const eval_f32x4*>(mask + (int64_t)c * ldo + mbase);
-                } else {
-#pragma unroll
-                    for (int v = 0; v < 4; ++v)
-                        if (mbase + v < Kout) keep[j][v] = mask[(int64_t)c * ldo + mbase + v];
-                }
-            }
-        }
-        for (int nb = 0; nb < N16; nb += 16) {
-            const int n = nb + 4 * q;
-            const eval_f32x4 x = *reinterpret_cast<const eval_f32x4*>(&in[c * ld + n]);
-            // every lane loads from a valid address (the last row where it has none, column 0 where it has no
-            // column) and the value is masked afterwards: no divergent branch around the loads. The second
-            // block of rows is the reward head's one row: it was loaded ahead of the loop.
-            size_t roff[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) roff[i] = (size_t)min(n + i, n0 - 1) * ldw;
-#pragma unroll
-            for (int j = 0; j < EVAL_JB; ++j) {
-                if (mb0 + j >= MB) continue;             // (wave-uniform)
-                const int m = (mb0 + j) * 16 + c;
-                const bool mok = m < Kout;
-                eval_f32x4 wv;
-#pragma unroll
-                for (int i = 0; i < 4; ++i) wv[i] = w0[roff[i] + (mok ? m : 0)];
-#pragma unroll
-                for (int i = 0; i < 4; ++i) wv[i] = !mok ? 0.0f : n + i < n0 ? wv[i] : n + i < N ? w1v[j] : 0.0f;
-                for (int i = 0; i < 4; ++i) acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(wv[i], x[i], acc[j], 0, 0, 0);
-            }
-        }
-        // lane l holds columns 16 mb + 4 q + v, v = 0 .. 3, of position c
-#pragma unroll
-        for (int j = 0; j < EVAL_JB; ++j) {
-            if (mb0 + j >= MB) continue;
-            const int mbase = (mb0 + j) * 16 + 4 * q;
-            eval_f32x4 y;
-#pragma unroll
-            for (int v = 0; v < 4; ++v) {
-                float t = acc[j][v];
-                if (mask && !(keep[j][v] > 0.0f)) t = 0.0f;
-                if (mbase + v >= Kout) t = 0.0f;          // (0 x a non-finite delta is a NaN: the padding stays zero)
-                y[v] = t;
-            }
-            *reinterpret_cast<eval_f32x4*>(&out[c * ld + mbase]) = y;
-            if (store && c < nvalid) {
-                if (vec && mbase + 3 < Kout) {
-                    *reinterpret_cast<eval_f32x4*>(store + (int64_t)c * ldo + mbase) = y;
-                } else {
-#pragma unroll
-                    for (int v = 0; v < 4; ++v)
-                        if (mbase + v < Kout) store[(int64_t)c * ldo + mbase + v] = y[v];
-                }
-            }
-        }
-    }
-}
-
-// acc[n] (+)= buf[0][n] + buf[1][n] + .. + buf[nvalid - 1][n], rows ascending; thread n % OL_THREADS owns column n
-__device__ __forceinline__ void ol_colsum(const float* buf, int ld, int N, int nvalid, float* acc, bool first) {
-    for (int n = threadIdx.x; n < N; n += OL_THREADS) {
-        float t = buf[n];
-        for (int r = 1; r < nvalid; ++r) t = t + buf[r * ld + n];
-        acc[n] = first ? t : acc[n] + t;
     }
 }
 
@@ -347,7 +237,7 @@ int ol_batch_ok(const char* what, int32_t E, int64_t batch, const TrainShape& t)
 // backward through time, L + 1 weight-gradient launches, loss.
 static hipError_t ol_launch(const TrainShape& t, const mbrl_train_model* members, int E, const mbrl_train_data* data,
                             const int64_t* idx, int64_t idx_stride, int /*bs*/, int batch, float* loss_out, float* ws,
-                            hipStream_t stream) {
+                            const mbrl_nll_bounds* /*bounds*/, hipStream_t stream) {
     const OlPlan p = ol_plan(t, E, batch);
     OlLaunch T{};
     EvalLaunch& A = T.A;
@@ -405,7 +295,7 @@ extern "C" {
 size_t mbrl_train_open_loop_workspace_bytes(const mbrl_train_model* members, int32_t E, int32_t batch) {
     TrainShape t;
     const char* what = "train_open_loop_workspace_bytes";
-    if (batch < 1 || ensemble_shape(what, members, E, true, &t) != MBRL_OK || ol_batch_ok(what, E, batch, t) != MBRL_OK)
+    if (batch < 1 || ensemble_shape(what, members, E, LOSS_OPEN_LOOP, &t) != MBRL_OK || ol_batch_ok(what, E, batch, t) != MBRL_OK)
         return 0;
     return ol_ws_floats(t, E, batch) * sizeof(float);
 }
@@ -415,7 +305,7 @@ int mbrl_train_grads_open_loop(const mbrl_train_model* members, int32_t E, const
                                size_t ws_bytes, mbrl_stream_t stream) {
     const char* what = "train_grads_open_loop";
     TrainShape t;
-    if (int rc = ensemble_shape(what, members, E, true, &t)) return rc;
+    if (int rc = ensemble_shape(what, members, E, LOSS_OPEN_LOOP, &t)) return rc;
     if (!train_data_ok(data, t) || !batch_idx || !workspace) return fail(MBRL_EINVAL, "%s: NULL argument", what);
     if (reinterpret_cast<uintptr_t>(workspace) & 15) return fail(MBRL_EINVAL, "%s: workspace not 16-byte aligned", what);
     if (batch < 1 || (int64_t)batch > data->transitions)
@@ -425,7 +315,7 @@ int mbrl_train_grads_open_loop(const mbrl_train_model* members, int32_t E, const
     const size_t need = ol_ws_floats(t, E, batch) * sizeof(float);
     if (ws_bytes < need) return fail(MBRL_EWORKSPACE, "%s: workspace %zu < %zu bytes", what, ws_bytes, need);
     return hip_check(ol_launch(t, members, E, data, batch_idx, batch, batch, batch, loss_out,
-                               static_cast<float*>(workspace), reinterpret_cast<hipStream_t>(stream)), what);
+                               static_cast<float*>(workspace), nullptr, reinterpret_cast<hipStream_t>(stream)), what);
 }
 
 int mbrl_train_epoch_open_loop(const mbrl_train_model* members, int32_t E, const mbrl_train_data* data,
@@ -433,9 +323,9 @@ int mbrl_train_epoch_open_loop(const mbrl_train_model* members, int32_t E, const
                                int32_t count, const mbrl_adam_hparams* hparams, const float* step_sizes,
                                const float* bc2_sqrt, float* losses, void* workspace, size_t ws_bytes,
                                mbrl_stream_t stream) {
-    return train_epoch_members("train_epoch_open_loop", true, false, ol_launch, members, E, data, orders, rows,
-                               batch_size, tensors, count, hparams, step_sizes, bc2_sqrt, losses, workspace, ws_bytes,
-                               nullptr, stream);
+    return train_epoch_members("train_epoch_open_loop", LOSS_OPEN_LOOP, false, ol_launch, members, E, data, orders,
+                               rows, batch_size, tensors, count, hparams, step_sizes, bc2_sqrt, losses, workspace,
+                               ws_bytes, nullptr, nullptr, stream);
 }
 
 int mbrl_train_epoch_open_loop_clipped(const mbrl_train_model* members, int32_t E, const mbrl_train_data* data,
@@ -443,9 +333,9 @@ int mbrl_train_epoch_open_loop_clipped(const mbrl_train_model* members, int32_t 
                                        const mbrl_adam_tensor* tensors, int32_t count, const mbrl_adam_hparams* hparams,
                                        const float* step_sizes, const float* bc2_sqrt, float* losses, void* workspace,
                                        size_t ws_bytes, mbrl_stream_t stream, const mbrl_grad_clip* clip) {
-    return train_epoch_members("train_epoch_open_loop_clipped", true, true, ol_launch, members, E, data, orders, rows,
-                               batch_size, tensors, count, hparams, step_sizes, bc2_sqrt, losses, workspace, ws_bytes,
-                               clip, stream);
+    return train_epoch_members("train_epoch_open_loop_clipped", LOSS_OPEN_LOOP, true, ol_launch, members, E, data,
+                               orders, rows, batch_size, tensors, count, hparams, step_sizes, bc2_sqrt, losses,
+                               workspace, ws_bytes, clip, nullptr, stream);
 }
 
 }  // extern "C"

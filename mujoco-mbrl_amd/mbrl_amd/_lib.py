@@ -81,6 +81,8 @@ EXPORTED = (
     "mbrl_grad_clip_workspace_bytes", "mbrl_grad_norm", "mbrl_adam_step_clipped",
     "mbrl_train_epoch_ensemble_clipped", "mbrl_train_epoch_open_loop_clipped",
     "mbrl_dataset_stack", "mbrl_dataset_stats_workspace_bytes", "mbrl_dataset_stats",
+    "mbrl_train_nll_workspace_bytes", "mbrl_train_grads_nll", "mbrl_train_epoch_nll", "mbrl_train_epoch_nll_clipped",
+    "mbrl_eval_members_nll",
 )
 
 
@@ -167,6 +169,11 @@ class GradClip(ctypes.Structure):
     """mbrl_grad_clip (include/mbrl_cem.h; added within ABI v13): the clipped epoch entries' extra argument."""
     _fields_ = [("max_norm", c_float), ("_pad", c_int32), ("norms", c_void_p), ("workspace", c_void_p),
                 ("ws_bytes", c_size_t)]
+
+
+class NllBounds(ctypes.Structure):
+    """mbrl_nll_bounds (include/mbrl_cem.h; added within ABI v13): the log-variance bounds of the NLL entries."""
+    _fields_ = [("min_logvar", c_void_p), ("max_logvar", c_void_p)]
 
 
 class StackField(ctypes.Structure):
@@ -262,6 +269,18 @@ def load():
         "mbrl_train_epoch_open_loop_clipped": (c_int32, [POINTER(TrainModel), c_int32, POINTER(TrainData), P, c_int64,
                                                          c_int32, POINTER(AdamTensor), c_int32, POINTER(AdamHparams), P,
                                                          P, P, P, c_size_t, P, POINTER(GradClip)]),
+        # probabilistic members: the Gaussian NLL's gradient, epochs and evaluation
+        "mbrl_train_nll_workspace_bytes": (c_size_t, [POINTER(TrainModel), c_int32, c_int32]),
+        "mbrl_train_grads_nll": (c_int32, [POINTER(TrainModel), c_int32, POINTER(TrainData), P, c_int32,
+                                           POINTER(NllBounds), P, P, c_size_t, P]),
+        "mbrl_train_epoch_nll": (c_int32, [POINTER(TrainModel), c_int32, POINTER(TrainData), P, c_int64, c_int32,
+                                           POINTER(AdamTensor), c_int32, POINTER(AdamHparams), P, P, P, P, c_size_t, P,
+                                           POINTER(NllBounds)]),
+        "mbrl_train_epoch_nll_clipped": (c_int32, [POINTER(TrainModel), c_int32, POINTER(TrainData), P, c_int64, c_int32,
+                                                   POINTER(AdamTensor), c_int32, POINTER(AdamHparams), P, P, P, P,
+                                                   c_size_t, P, POINTER(NllBounds), POINTER(GradClip)]),
+        "mbrl_eval_members_nll": (c_int32, [POINTER(TrainModel), c_int32, POINTER(TrainData), P, c_int64,
+                                            POINTER(NllBounds), P, P, P, P, P]),
         "mbrl_eval_members": (c_int32, [POINTER(TrainModel), c_int32, POINTER(TrainData), P, c_int64, P, P, P, P]),
         "mbrl_eval_members_open_loop": (c_int32, [POINTER(TrainModel), c_int32, POINTER(TrainData), P, c_int64, P, P, P, P,
                                                   P]),
@@ -490,5 +509,5 @@ __all__ = ["load", "check", "ptr", "stream_handle", "MlpShape", "Norm", "Cost", 
            "EXPORTED", "MBRL_NAN_LAST", "MBRL_NAN_FIRST", "MBRL_COST_GOAL_STATE", "MBRL_COST_MODEL_REWARD",
            "ABI_VERSION", "c_int64", "MBRL_PRECISION_F32", "MBRL_PRECISION_F16X3", "MBRL_PRECISION_F16X6",
            "precision_code", "load_other", "option", "OPTIONS", "AdamTensor", "AdamHparams",
-           "TrainModel", "TrainData", "TRAIN_MAX_LAYERS", "TRAIN_MAX_MEMBERS", "HostStaging", "CopyTensor",
+           "TrainModel", "TrainData", "NllBounds", "TRAIN_MAX_LAYERS", "TRAIN_MAX_MEMBERS", "HostStaging", "CopyTensor",
            "StackField", "StatsField"]

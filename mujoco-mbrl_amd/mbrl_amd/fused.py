@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .models import CoshLoss, EnsembleModel, Model, ModelWithReward, SmoothAbsLoss
+from .models import CoshLoss, EnsembleModel, Model, ModelWithReward, ProbabilisticModel, SmoothAbsLoss
 
 
 # ------------------------------------------------------------------------------------------------
@@ -75,11 +75,16 @@ def _reward_layers(module):
 def _linear_layers(module):
     """(members, L, W, s, a) for a recognised dynamics module, else None. members = list of lists of
     nn.Linear. Accepts this package's Model / EnsembleModel and the reference's models.Model
-    (duck-typed: linear1..linear3 + ReLU activation_fn + noise None)."""
+    (duck-typed: linear1..linear3 + ReLU activation_fn + noise None). A ProbabilisticModel is the deterministic
+    model of its trunk and its head's mean rows (mean_linears: the head's first s rows, in place)."""
     if isinstance(module, EnsembleModel):
-        members = [m.linears() for m in module.members]
+        members = [m.mean_linears() if isinstance(m, ProbabilisticModel) else m.linears() for m in module.members]
         m0 = module.members[0]
         return members, m0.n_hidden, m0.hidden_units, m0.state_dim, m0.action_dim
+    if isinstance(module, ProbabilisticModel):
+        if module.n_hidden < 1:
+            return None
+        return [module.mean_linears()], module.n_hidden, module.hidden_units, module.state_dim, module.action_dim
     if isinstance(module, Model):
         if module.noise is not None or module.n_hidden < 1:
             return None

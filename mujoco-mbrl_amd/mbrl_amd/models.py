@@ -188,12 +188,16 @@ class _NativeGrads:
         _NATIVE_CACHE.pop(model, None)
 
     @staticmethod
-    def supported(model, dataset, ins, outs, criterion):
+    def supported(model, dataset, ins, outs, criterion, probabilistic=False):
+        """False / True (the reward head) when the native entries take the model, else None. probabilistic: the
+        caller's entry reads a ProbabilisticModel (the NLL entries its whole head, the evaluation its mean rows)."""
         if not NATIVE_TRAINING or type(criterion) is not torch.nn.MSELoss or criterion.reduction != "mean":
             return None
         if type(model) is Model:
             if model.noise is not None:
                 return None
+            reward = False
+        elif type(model) is ProbabilisticModel and probabilistic:
             reward = False
         elif type(model) is ModelWithReward:
             reward = True
@@ -583,8 +587,103 @@ class LinearModel(DynamicsModel):
         return x if self.noise is None else x + torch.randn_like(x) * self.noise
 
 
+def _softplus(x):
+    """max(x, 0) + log1p(exp(-|x|)): the form csrc/train_nll.hip evaluates."""
+    return torch.clamp(x, min=0) + torch.log1p(torch.exp(-x.abs()))
+
+
+def bounded_logvar(raw, min_logvar, max_logvar):
+    """The PETS bound on a raw log-variance: max - softplus(max - raw), then min + softplus(. - min)."""
+    u = max_logvar - _softplus(max_logvar - raw)
+    return min_logvar + _softplus(u - min_logvar)
+
+
+def gaussian_nll(mean, logvar, target):
+    """The project's Gaussian NLL of one horizon step: sum_{b, j} [(m - y)^2 exp(-lv) + lv] / (B s), MSELoss's scale
+    (mbrl_cem.h, mbrl_train_grads_nll: the constant and the factor 1/2 of the density are left out)."""
+    return (((mean - target) ** 2) * torch.exp(-logvar) + logvar).sum() / mean.numel()
+
+
+class _MeanRows:
+    """The mean rows of a ProbabilisticModel's head as the nn.Linear the packer and the evaluation read: weight
+    [s, W] and bias [s] are views of the head's first s rows (the same storage, so the same pointers)."""
+
+    def __init__(self, head, s):
+        self._head, self._s = head, s
+
+    @property
+    def _parameters(self):                # (fused._param_key: the live Parameters' pointers and versions)
+        return self._head._parameters
+
+    @property
+    def weight(self):
+        return self._head.weight[:self._s]
+
+    @property
+    def bias(self):
+        return self._head.bias[:self._s]
+
+
+class ProbabilisticModel(DynamicsModel):
+    """A PETS-style probabilistic member (not in the reference): Model's trunk of `n_hidden` Linear-ReLU layers and
+    one head Linear(hidden_units -> 2 * state_dim) whose rows [0, s) are the predicted mean and rows [s, 2 s) the
+    raw log-variance, bounded per dimension by bounded_logvar(raw, min_logvar, max_logvar). The bounds are [s]
+    float32 buffers: not parameters, and not trained here. No reward head and no noise injection: forward() and
+    the planners use the mean (EnsembleModel.train_members(loss="nll") trains both halves)."""
+
+    def __init__(self, state_dim, action_dim, hidden_units=200, n_hidden=2, min_logvar=-10.0, max_logvar=0.5):
+        super().__init__()
+        self.state_dim, self.action_dim = state_dim, action_dim
+        self.hidden_units, self.n_hidden = hidden_units, n_hidden
+        dims = [state_dim + action_dim] + [hidden_units] * n_hidden + [2 * state_dim]
+        for i, (fi, fo) in enumerate(zip(dims[:-1], dims[1:])):
+            setattr(self, f"linear{i + 1}", nn.Linear(fi, fo))
+        self.activation_fn = nn.ReLU()
+        self.noise = None
+        self.register_buffer("min_logvar", torch.full((state_dim,), float(min_logvar), dtype=torch.float32))
+        self.register_buffer("max_logvar", torch.full((state_dim,), float(max_logvar), dtype=torch.float32))
+
+    def linears(self):
+        m = self._modules
+        return [m[f"linear{i + 1}"] for i in range(self.n_hidden + 1)]
+
+    def mean_linears(self):
+        """The layers of the deterministic model this one is for the planners and the held-out MSE: the trunk and
+        the head's mean rows."""
+        lins = self.linears()
+        return lins[:-1] + [_MeanRows(lins[-1], self.state_dim)]
+
+    def _head(self, x):
+        lins = self.linears()
+        for lin in lins[:-1]:
+            x = self.activation_fn(lin(x))
+        return lins[-1](x)
+
+    def _forward(self, x):
+        return self._head(x)[..., :self.state_dim]
+
+    def _dist(self, x):
+        """(mean, bounded log-variance) of the concatenated (state, action) rows x, in the space the model is
+        trained in."""
+        out = self._head(x)
+        s = self.state_dim
+        return out[..., :s], bounded_logvar(out[..., s:], self.min_logvar, self.max_logvar)
+
+    def predict_dist(self, state, action, normalize_action=None, normalize_state=None, unnormalize_state=None):
+        """forward()'s arguments; returns (mean, logvar): forward()'s mean and the bounded per-dimension
+        log-variance of the normalised next state (it is not rescaled by unnormalize_state)."""
+        if normalize_action:
+            action = normalize_action(action)
+        if normalize_state:
+            state = normalize_state(state)
+        mean, logvar = self._dist(torch.cat([state, action], dim=1))
+        if unnormalize_state:
+            mean = unnormalize_state(mean)
+        return mean, logvar
+
+
 class EnsembleModel(DynamicsModel):
-    """PETS-style ensemble of E `Model`s (not in the reference; BASELINE.json config 5).
+    """PETS-style ensemble of E `Model`s, or of E `ProbabilisticModel`s (not in the reference; BASELINE.json config 5).
 
     The CEM planner rolls every member out on the same actions and scores a candidate by the mean
     of the members' returns. Called directly, forward() returns the member-mean next state."""
@@ -594,9 +693,10 @@ class EnsembleModel(DynamicsModel):
         self.members = nn.ModuleList(members)
         m0 = self.members[0]
         for m in self.members:
-            if not isinstance(m, Model) or (m.state_dim, m.action_dim, m.hidden_units, m.n_hidden) != \
+            if not isinstance(m, (Model, ProbabilisticModel)) or type(m) is not type(m0) or \
+                    (m.state_dim, m.action_dim, m.hidden_units, m.n_hidden) != \
                     (m0.state_dim, m0.action_dim, m0.hidden_units, m0.n_hidden):
-                raise ValueError("EnsembleModel members must be Models of one shape")
+                raise ValueError("EnsembleModel members must be Models (or ProbabilisticModels) of one shape")
         self.state_dim, self.action_dim = m0.state_dim, m0.action_dim
         self.hidden_units, self.n_hidden = m0.hidden_units, m0.n_hidden
         self.noise = None
@@ -645,12 +745,20 @@ class EnsembleModel(DynamicsModel):
         (csrc/grad_clip.hip: two launches more per batch) under the same support test; the fallbacks call
         clip_grad_norm_. With a writer each batch's pre-clip norm goes to grad_norm/member{e}/{iteration}; the
         native path keeps the norms on the device through the epoch and copies them out with the losses. Anything
-        but None or a positive number is a ValueError before any work."""
-        if loss not in ("one_step", "open_loop"):
-            raise ValueError(f'train_members: loss must be "one_step" or "open_loop", got {loss!r}')
+        but None or a positive number is a ValueError before any work.
+
+        loss="nll" (an ensemble of ProbabilisticModels; any other member type is a ValueError): each member
+        minimises the Gaussian negative log-likelihood of next_states[i, h] under its predicted mean and bounded
+        log-variance, teacher forced, summed over the horizon steps on MSELoss's scale (gaussian_nll;
+        include/mbrl_cem.h, mbrl_train_grads_nll). The shared launches are one mbrl_train_epoch_nll(_clipped) call
+        per epoch (csrc/train_nll.hip) when the members' bounds are equal; the fallback is the same loss under
+        autograd. `criterion` is not used. The writer gets the NLL under loss/state/member{e}/{iteration}."""
+        if loss not in ("one_step", "open_loop", "nll"):
+            raise ValueError(f'train_members: loss must be "one_step", "open_loop" or "nll", got {loss!r}')
         max_grad_norm = _check_max_grad_norm("train_members", max_grad_norm)
         open_loop = loss == "open_loop"
         members = list(self.members)
+        _check_nll_members("train_members", members, loss)
         opts = [optimizers(m) for m in members] if callable(optimizers) else list(optimizers)
         if len(opts) != len(members):
             raise ValueError(f"train_members needs one optimizer per member ({len(members)}), got {len(opts)}")
@@ -660,14 +768,16 @@ class EnsembleModel(DynamicsModel):
         if n > 0 and num_epochs > 0 and _device_of(self).type == "cuda":
             with torch.cuda.device(_device_of(self)):
                 first = _train_members_native(self, members, opts, dataset, batch_size, num_epochs, bootstrap, seed,
-                                              criterion, writer, open_loop=open_loop, max_grad_norm=max_grad_norm)
-        if open_loop and n > 0 and first < num_epochs:
+                                              criterion, writer, open_loop=open_loop, max_grad_norm=max_grad_norm,
+                                              nll=loss == "nll")
+        if loss != "one_step" and n > 0 and first < num_epochs:
+            torch_epochs = _train_open_loop_torch if open_loop else _train_nll_torch
             for e, (m, opt) in enumerate(zip(members, opts)):
                 if first > 0:
                     m.train_iterations -= 1
-                _train_open_loop_torch(m, e, dataset, opt, batch_size, num_epochs - first, criterion, writer,
-                                       lambda k, e=e: member_order(seed, e, first + k, n, bootstrap),
-                                       first * ((n + batch_size - 1) // batch_size), max_grad_norm)
+                torch_epochs(m, e, dataset, opt, batch_size, num_epochs - first, criterion, writer,
+                             lambda k, e=e: member_order(seed, e, first + k, n, bootstrap),
+                             first * ((n + batch_size - 1) // batch_size), max_grad_norm)
                 m.train_iterations += 1
         elif first < num_epochs or n == 0 or num_epochs <= 0:
             for e, (m, opt) in enumerate(zip(members, opts)):
@@ -685,7 +795,7 @@ class EnsembleModel(DynamicsModel):
         self.train_iterations += 1
         return first
 
-    def evaluate_members(self, dataset, rows=None, open_loop=False, predictions=False):
+    def evaluate_members(self, dataset, rows=None, open_loop=False, predictions=False, nll=False):
         """Every member's error on rows `rows` of dataset.stacked() (default: all of them; indices may repeat):
         dict(loss [E], per_step [E, horizon], row_err [E, R, horizon]) on the ensemble's device, with
             row_err[e, r, h] = sum_j (member e's predicted next state - next_states[rows[r], h])_j ** 2,
@@ -699,16 +809,27 @@ class EnsembleModel(DynamicsModel):
         On a GPU, when train_members' support test passes for every member, one mbrl_eval_members /
         mbrl_eval_members_open_loop call (csrc/eval.hip) with no host synchronisation -- pass `rows` as a
         device tensor to keep its upload out as well; otherwise (CPU, `noise`, more than 8 members) the same
-        definitions in torch."""
+        definitions in torch. ProbabilisticModel members are evaluated on their mean (the head's first s rows).
+
+        nll=True (ProbabilisticModel members, teacher forced only): the Gaussian negative log-likelihood
+        train_members(loss="nll") minimises. The dict then holds row_nll [E, R, horizon] = sum_j [(m - y)^2
+        exp(-lv) + lv], per_step and loss from row_nll on the same scale, row_err as above, and mse [E] and
+        mean_logvar [E]: the same sums of row_err and of sum_j lv (mbrl_eval_members_nll, csrc/train_nll.hip, or
+        the same definitions in torch)."""
         if predictions and not open_loop:
             raise ValueError("evaluate_members returns predictions of an open-loop evaluation only (open_loop=True)")
+        if nll and open_loop:
+            raise ValueError("evaluate_members: the NLL is teacher forced (nll=True excludes open_loop=True)")
         members = list(self.members)
+        _check_nll_members("evaluate_members", members, "nll" if nll else None)
         dev = _device_of(self)
         _, ins, outs = dataset.stacked(dev)
         rows = _holdout_rows(dataset, dev, rows)
         R, H = int(rows.shape[0]), dataset.horizon
         if R < 1:
             raise ValueError("evaluate_members needs at least one row")
+        if nll:
+            return _evaluate_members_nll(members, dataset, ins, outs, rows, dev)
         pred = None
         if _NativeEval.supported(members, dataset, ins, outs):
             with torch.cuda.device(dev):
@@ -754,6 +875,10 @@ class EnsembleModel(DynamicsModel):
         holdout_loss="open_loop" the members are trained on, and picked by, the loss a planner's rollout
         meets). Any other string is a ValueError before any work.
 
+        "nll" for either (ProbabilisticModel members; any other member type is a ValueError): the epochs minimise,
+        or the members are scored and kept by, the Gaussian negative log-likelihood (train_members(loss="nll"),
+        evaluate_members(nll=True)); val_loss then holds the NLL.
+
         max_grad_norm: train_members' per-member gradient clipping for the epochs (None: none).
 
         patience: after each epoch k with (k + 1) % check_every == 0 the host reads the members' `stale`
@@ -766,13 +891,16 @@ class EnsembleModel(DynamicsModel):
         Returns, and keeps as self.holdout_report, dict(val_loss [epochs_run, E], best_loss [E],
         best_epoch [E] (CPU tensors), epochs_run, native_epochs: the epochs that trained in the shared
         launches, native_eval: whether the held-out losses came from the C entry, holdout_loss). Writer tags: train_members', and loss/holdout/member{e}/{iteration} per epoch."""
-        if holdout_loss not in ("one_step", "open_loop"):
-            raise ValueError(f'fit_members: holdout_loss must be "one_step" or "open_loop", got {holdout_loss!r}')
-        if train_loss not in ("one_step", "open_loop"):
-            raise ValueError(f'fit_members: train_loss must be "one_step" or "open_loop", got {train_loss!r}')
+        if holdout_loss not in ("one_step", "open_loop", "nll"):
+            raise ValueError('fit_members: holdout_loss must be "one_step", "open_loop" or "nll", '
+                             f'got {holdout_loss!r}')
+        if train_loss not in ("one_step", "open_loop", "nll"):
+            raise ValueError(f'fit_members: train_loss must be "one_step", "open_loop" or "nll", got {train_loss!r}')
         max_grad_norm = _check_max_grad_norm("fit_members", max_grad_norm)
         open_loop = train_loss == "open_loop"
         members = list(self.members)
+        _check_nll_members("fit_members", members, train_loss)
+        _check_nll_members("fit_members", members, holdout_loss)
         opts = [optimizers(m) for m in members] if callable(optimizers) else list(optimizers)
         if len(opts) != len(members):
             raise ValueError(f"fit_members needs one optimizer per member ({len(members)}), got {len(opts)}")
@@ -783,7 +911,8 @@ class EnsembleModel(DynamicsModel):
         max_epochs = max(int(max_epochs), 0) if n > 0 else 0
         iteration = [m.train_iterations for m in members]
         with torch.cuda.device(dev) if dev.type == "cuda" else contextlib.nullcontext():
-            tracker = _Holdout(members, holdout, max_epochs, open_loop=holdout_loss == "open_loop")
+            tracker = _Holdout(members, holdout, max_epochs, open_loop=holdout_loss == "open_loop",
+                               nll=holdout_loss == "nll")
             stopped = []
 
             def after_epoch(k):
@@ -795,7 +924,7 @@ class EnsembleModel(DynamicsModel):
             if max_epochs > 0 and dev.type == "cuda":
                 first = _train_members_native(self, members, opts, dataset, batch_size, max_epochs, bootstrap, seed,
                                               criterion, writer, after_epoch=after_epoch, open_loop=open_loop,
-                                              max_grad_norm=max_grad_norm)
+                                              max_grad_norm=max_grad_norm, nll=train_loss == "nll")
             batches = (n + batch_size - 1) // max(batch_size, 1)
             for k in range(tracker.epochs, 0 if stopped else max_epochs):
                 for e, (m, opt) in enumerate(zip(members, opts)):
@@ -804,10 +933,10 @@ class EnsembleModel(DynamicsModel):
                         return [criterion(m.forward(states, actions, normalize_action=None, normalize_state=None,
                                                     unnormalize_state=None), next_states)]
                     m.train_iterations = iteration[e]         # (one call's worth of epochs: one iteration)
-                    if open_loop:
-                        _train_open_loop_torch(m, e, dataset, opt, batch_size, 1, criterion, writer,
-                                               lambda _, e=e, k=k: member_order(seed, e, k, n, bootstrap), k * batches,
-                                               max_grad_norm)
+                    if train_loss != "one_step":
+                        (_train_open_loop_torch if open_loop else _train_nll_torch)(
+                            m, e, dataset, opt, batch_size, 1, criterion, writer,
+                            lambda _, e=e, k=k: member_order(seed, e, k, n, bootstrap), k * batches, max_grad_norm)
                         continue
                     _train_loop(m, dataset, opt, batch_size, 1, step_loss, writer, [f"loss/state/member{e}/{{}}"],
                                 criterion, order_fn=lambda _, e=e, k=k: member_order(seed, e, k, n, bootstrap),
@@ -859,6 +988,12 @@ def _check_max_grad_norm(what, max_grad_norm):
     if isinstance(max_grad_norm, bool) or not isinstance(max_grad_norm, (int, float)) or not max_grad_norm > 0:
         raise ValueError(f"{what}: max_grad_norm must be None or a positive number, got {max_grad_norm!r}")
     return float(max_grad_norm)
+
+
+def _check_nll_members(what, members, loss):
+    """The NLL needs a log-variance: ProbabilisticModel members only."""
+    if loss == "nll" and not all(isinstance(m, ProbabilisticModel) for m in members):
+        raise ValueError(f'{what}: the "nll" loss needs an ensemble of ProbabilisticModel members')
 
 
 def member_order(seed, e, k, n, bootstrap=True):
@@ -926,6 +1061,10 @@ class _NativeEnsemble:
             _NATIVE_ENS_CACHE.pop(owner, None)
         return obj
 
+    def _extra_args(self):
+        """What the entry takes between the stream and the clip struct."""
+        return ()
+
     def epoch(self, orders, rows, batch_size, adams):
         """One epoch of every member over the device orders [E * rows]. Returns the losses
         [batches, E, 3] (device), or None when an optimizer's state does not allow the whole-epoch
@@ -968,6 +1107,7 @@ class _NativeEnsemble:
                 int(batch_size), table, count, ctypes.byref(hp), ctypes.c_void_p(ss.ctypes.data),
                 ctypes.c_void_p(bc.ctypes.data), ctypes.c_void_p(losses.data_ptr()), ctypes.c_void_p(self.ws.data_ptr()),
                 self.ws.numel(), self._lib.stream_handle(self.dev))
+        args += self._extra_args()
         if max_norm is None:
             self._lib.check(getattr(self.lib, self.EPOCH)(*args), self.EPOCH)
         else:
@@ -990,6 +1130,71 @@ class _NativeEnsembleOpenLoop(_NativeEnsemble):
 
     WORKSPACE, EPOCH = "mbrl_train_open_loop_workspace_bytes", "mbrl_train_epoch_open_loop"
     CLIPPED = "mbrl_train_epoch_open_loop_clipped"
+
+
+class _NativeEnsembleNll(_NativeEnsemble):
+    """mbrl_train_epoch_nll: ProbabilisticModel members (each head one [2 s, W] tensor), the Gaussian NLL
+    (csrc/train_nll.hip). The entry takes one pair of bounds for all members: member 0's buffers, read live."""
+
+    WORKSPACE, EPOCH = "mbrl_train_nll_workspace_bytes", "mbrl_train_epoch_nll"
+    CLIPPED = "mbrl_train_epoch_nll_clipped"
+
+    def __init__(self, members, ins, outs, horizon, batch_size):
+        super().__init__(members, ins, outs, horizon, batch_size)
+        self.bound_t = (members[0].min_logvar, members[0].max_logvar)
+        self.bounds = self._lib.NllBounds(self.bound_t[0].data_ptr(), self.bound_t[1].data_ptr())
+        if members[0].action_dim == 0:
+            self.data.actions = None
+
+    @staticmethod
+    def bounds_shared(members):
+        m0 = members[0]
+        return all(b.dtype == torch.float32 and b.is_contiguous() and b.device == m.linear1.weight.device
+                   for m in members for b in (m.min_logvar, m.max_logvar)) and \
+            all(torch.equal(m.min_logvar, m0.min_logvar) and torch.equal(m.max_logvar, m0.max_logvar)
+                for m in members[1:])
+
+    def _extra_args(self):
+        if (self.bounds.min_logvar, self.bounds.max_logvar) != tuple(t.data_ptr() for t in self.bound_t):
+            raise RuntimeError("the log-variance bounds moved during training")
+        return (ctypes.byref(self.bounds),)
+
+
+def _nll_batch_loss(m, states, actions, next_states, idx, horizon):
+    """train_members(loss="nll")'s loss of one batch in torch: gaussian_nll of every step, summed."""
+    st, ac, ns = (x.index_select(0, idx) for x in (states, actions, next_states))
+    loss = 0
+    for h in range(horizon):
+        mean, logvar = m._dist(torch.cat([st[:, h], ac[:, h]], dim=1))
+        loss = loss + gaussian_nll(mean, logvar, ns[:, h])
+    return loss
+
+
+def _train_nll_torch(m, e, dataset, opt, batch_size, num_epochs, criterion, writer, order_fn, iter0,
+                     max_grad_norm=None):
+    """train_members(loss="nll") for one member in torch (_train_open_loop_torch's loop, teacher forced, the
+    Gaussian NLL; `criterion` is not used). It is the baseline tools/train_nll_bench.py times."""
+    dev = _device_of(m)
+    _, ins, outs = dataset.stacked(dev)
+    (states, actions), (_, next_states) = ins, outs
+    fast = AdamStep.maybe(opt) if dev.type == "cuda" else None
+    it = iter0
+    with torch.cuda.device(dev) if dev.type == "cuda" else contextlib.nullcontext():
+        for k in range(num_epochs):
+            order = torch.from_numpy(order_fn(k)).to(dev)
+            for i in range(0, int(order.shape[0]), batch_size):
+                opt.zero_grad()
+                loss = _nll_batch_loss(m, states, actions, next_states, order[i:i + batch_size], dataset.horizon)
+                loss.backward()
+                if max_grad_norm is not None:
+                    norm = torch.nn.utils.clip_grad_norm_(m.parameters(), max_grad_norm)
+                if fast is None or not fast.step():
+                    opt.step()
+                it += 1
+                if writer is not None:
+                    writer.add_scalar(f"loss/state/member{e}/{m.train_iterations}", loss, it)
+                    if max_grad_norm is not None:
+                        writer.add_scalar(f"grad_norm/member{e}/{m.train_iterations}", norm, it)
 
 
 def _train_open_loop_torch(m, e, dataset, opt, batch_size, num_epochs, criterion, writer, order_fn, iter0,
@@ -1027,7 +1232,7 @@ def _train_open_loop_torch(m, e, dataset, opt, batch_size, num_epochs, criterion
 
 
 def _train_members_native(owner, members, opts, dataset, batch_size, num_epochs, bootstrap, seed, criterion, writer,
-                          after_epoch=None, open_loop=False, max_grad_norm=None):
+                          after_epoch=None, open_loop=False, max_grad_norm=None, nll=False):
     """The epochs of train_members the shared launches can take, from the first: returns how many ran
     (0: not supported here; the caller trains the rest member by member). Orders are staged as
     _train_loop_on stages them: epoch k + 1's rows are drawn into a pinned ring row while epoch k
@@ -1041,14 +1246,16 @@ def _train_members_native(owner, members, opts, dataset, batch_size, num_epochs,
     if E > _lib.TRAIN_MAX_MEMBERS or len({id(m) for m in members}) != E:
         return 0
     _, ins, outs = dataset.stacked(dev)
-    if any(_NativeGrads.supported(m, dataset, ins, outs, criterion) is not False for m in members):
+    if any(_NativeGrads.supported(m, dataset, ins, outs, criterion, probabilistic=nll) is not False for m in members):
+        return 0
+    if nll and not _NativeEnsembleNll.bounds_shared(members):
         return 0
     adams = [AdamStep.maybe(opt) for opt in opts]
     if any(a is None for a in adams):
         return 0
     n = dataset.num_transitions()
-    native = (_NativeEnsembleOpenLoop if open_loop else _NativeEnsemble).cached(owner, members, ins, outs,
-                                                                                dataset.horizon, batch_size)
+    kind = _NativeEnsembleNll if nll else _NativeEnsembleOpenLoop if open_loop else _NativeEnsemble
+    native = kind.cached(owner, members, ins, outs, dataset.horizon, batch_size)
     ring = _order_ring(dev, E * n)
     main = torch.cuda.current_stream(dev)
 
@@ -1112,6 +1319,40 @@ def _eval_members_torch(members, ins, outs, rows):
         return torch.stack([((m._forward(x) - target) ** 2).sum(1).reshape(R, H) for m in members])
 
 
+def _eval_members_nll_torch(members, ins, outs, rows):
+    """mbrl_eval_members_nll's definitions in torch: (row_nll, row_err, row_lv), each [E, R, horizon]."""
+    (states, actions), (_, next_states) = ins, outs
+    with torch.no_grad():
+        st, ac, ns = (x.index_select(0, rows) for x in (states, actions, next_states))
+        R, H = st.shape[0], st.shape[1]
+        x = torch.cat([st.reshape(R * H, -1), ac.reshape(R * H, -1)], dim=1)
+        target = ns.reshape(R * H, -1)
+        out = [[], [], []]
+        for m in members:
+            mean, lv = m._dist(x)
+            d2 = (mean - target) ** 2
+            for acc, v in zip(out, (d2 * torch.exp(-lv) + lv, d2, lv)):
+                acc.append(v.sum(1).reshape(R, H))
+        return tuple(torch.stack(v) for v in out)
+
+
+def _evaluate_members_nll(members, dataset, ins, outs, rows, dev):
+    """evaluate_members(nll=True): the native entry where it takes the members, else torch."""
+    E, R, H, s = len(members), int(rows.shape[0]), dataset.horizon, members[0].state_dim
+    if _NativeEval.supported(members, dataset, ins, outs) and _NativeEnsembleNll.bounds_shared(members):
+        with torch.cuda.device(dev):
+            row = torch.empty((3, E, R, H), dtype=torch.float32, device=dev)
+            loss3 = torch.empty((E, 3), dtype=torch.float32, device=dev)
+            _NativeEval(members, ins, outs, H).run_nll(rows, row, loss3)
+        row_nll, row_err, row_lv = row[0], row[1], row[2]
+        loss, mse, mean_lv = loss3[:, 0], loss3[:, 1], loss3[:, 2]
+    else:
+        row_nll, row_err, row_lv = _eval_members_nll_torch(members, ins, outs, rows)
+        loss, mse, mean_lv = ((v.sum(1) / (R * s)).sum(1) for v in (row_nll, row_err, row_lv))
+    per_step = row_nll.sum(1) / (R * s)
+    return dict(loss=loss, per_step=per_step, row_err=row_err, row_nll=row_nll, mse=mse, mean_logvar=mean_lv)
+
+
 def _eval_members_open_loop_torch(members, ins, outs, rows):
     """mbrl_eval_members_open_loop's definitions in torch: from states[rows, 0] every member's own _forward is
     fed back as the next state, horizon times. Returns (row_err [E, R, horizon], pred [E, R, horizon, s])."""
@@ -1139,6 +1380,8 @@ class _NativeEval:
         self._lib, self.lib = _lib, _native_lib()
         self.dev = _device_of(members[0])
         self.E, self.horizon = len(members), int(horizon)
+        self.members0 = members[0]
+        # (a ProbabilisticModel's head is read through the same pointers: its mean rows are its first s rows)
         self.params = [[t for lin in m.linears() for t in (lin.weight, lin.bias)] for m in members]
         self.models = (_lib.TrainModel * self.E)()
         for m, model, params in zip(self.models, members, self.params):
@@ -1162,7 +1405,7 @@ class _NativeEval:
         if _device_of(members[0]).type != "cuda" or len(members) > _lib.TRAIN_MAX_MEMBERS:
             return False
         mse = torch.nn.MSELoss()
-        return all(_NativeGrads.supported(m, dataset, ins, outs, mse) is False for m in members)
+        return all(_NativeGrads.supported(m, dataset, ins, outs, mse, probabilistic=True) is False for m in members)
 
     def run(self, rows, row_err, loss):
         """Enqueue the evaluation of the device rows `rows` into row_err [E, R, horizon] and loss [E, 3]."""
@@ -1172,6 +1415,18 @@ class _NativeEval:
         self._lib.check(self.lib.mbrl_eval_members(self.models, self.E, ctypes.byref(self.data), P(rows.data_ptr()),
                                                    int(rows.shape[0]), P(row_err.data_ptr()), None, P(loss.data_ptr()),
                                                    self._lib.stream_handle(self.dev)), "mbrl_eval_members")
+
+    def run_nll(self, rows, row, loss):
+        """mbrl_eval_members_nll on ProbabilisticModel members of equal bounds (member 0's are passed): row
+        [3, E, R, horizon] receives row_nll, row_err and row_lv, loss [E, 3] (nll, mse, mean_lv)."""
+        if [t.data_ptr() for params in self.params for t in params] != self.ptrs:
+            raise RuntimeError("model parameters moved during evaluation")
+        P = ctypes.c_void_p
+        bounds = self._lib.NllBounds(self.members0.min_logvar.data_ptr(), self.members0.max_logvar.data_ptr())
+        self._lib.check(self.lib.mbrl_eval_members_nll(
+            self.models, self.E, ctypes.byref(self.data), P(rows.data_ptr()), int(rows.shape[0]), ctypes.byref(bounds),
+            P(row[0].data_ptr()), P(row[1].data_ptr()), P(row[2].data_ptr()), P(loss.data_ptr()),
+            self._lib.stream_handle(self.dev)), "mbrl_eval_members_nll")
 
     def run_open_loop(self, rows, row_err, loss, pred=None):
         """The same with the members' predictions fed back (mbrl_eval_members_open_loop); pred: [E, R, horizon, s]
@@ -1196,8 +1451,8 @@ class _Holdout:
     snapshot of each member's parameters at its best epoch. On the native path (mbrl_eval_members and
     mbrl_keep_best on the training stream) the host reads nothing unless a patience asks for `stale`."""
 
-    def __init__(self, members, holdout, max_epochs, open_loop=False):
-        self.members, self.open_loop = members, open_loop
+    def __init__(self, members, holdout, max_epochs, open_loop=False, nll=False):
+        self.members, self.open_loop, self.nll = members, open_loop, nll
         dev = self.dev = _device_of(members[0])
         _, self.ins, self.outs = holdout.stacked(dev)
         self.rows = _holdout_rows(holdout, dev, None)
@@ -1214,10 +1469,11 @@ class _Holdout:
         self.stale = torch.zeros(E, dtype=torch.int32, device=dev)
         self.epochs = 0
         self.native = None
-        if _NativeEval.supported(members, holdout, self.ins, self.outs):
+        if _NativeEval.supported(members, holdout, self.ins, self.outs) and \
+                (not nll or _NativeEnsembleNll.bounds_shared(members)):
             from . import _lib
             self.native = _NativeEval(members, self.ins, self.outs, H)
-            self.row_err = torch.empty((E, R, H), dtype=torch.float32, device=dev)
+            self.row_err = torch.empty((3, E, R, H) if nll else (E, R, H), dtype=torch.float32, device=dev)
             count = len(self.params[0])
             self.table = (_lib.CopyTensor * (E * count))()
             for e in range(E):
@@ -1231,7 +1487,9 @@ class _Holdout:
         E = len(self.members)
         if self.native is not None:
             nat, P = self.native, ctypes.c_void_p
-            if self.open_loop:
+            if self.nll:
+                nat.run_nll(self.rows, self.row_err, self.val[k])
+            elif self.open_loop:
                 nat.run_open_loop(self.rows, self.row_err, self.val[k])
             else:
                 nat.run(self.rows, self.row_err, self.val[k])
@@ -1239,7 +1497,9 @@ class _Holdout:
                                                   P(self.best_epoch.data_ptr()), P(self.stale.data_ptr()), self.table,
                                                   self.count, nat._lib.stream_handle(self.dev)), "mbrl_keep_best")
         else:
-            if self.open_loop:
+            if self.nll:
+                row_err = _eval_members_nll_torch(self.members, self.ins, self.outs, self.rows)[0]
+            elif self.open_loop:
                 row_err = _eval_members_open_loop_torch(self.members, self.ins, self.outs, self.rows)[0]
             else:
                 row_err = _eval_members_torch(self.members, self.ins, self.outs, self.rows)
