@@ -51,7 +51,8 @@ extern "C" {
  * mbrl_train_epoch_open_loop_clipped), and the device-resident transitions (mbrl_stack_field, mbrl_dataset_stack,
  * mbrl_stats_field, mbrl_dataset_stats_workspace_bytes, mbrl_dataset_stats), and probabilistic members trained on
  * the Gaussian negative log-likelihood (mbrl_nll_bounds, mbrl_train_nll_workspace_bytes, mbrl_train_grads_nll,
- * mbrl_train_epoch_nll, mbrl_train_epoch_nll_clipped, mbrl_eval_members_nll). */
+ * mbrl_train_epoch_nll, mbrl_train_epoch_nll_clipped, mbrl_eval_members_nll), and trajectory-sampling rollouts on
+ * them (mbrl_ts_params, mbrl_rollout_cost_ts, mbrl_cem_ts_workspace_bytes, mbrl_cem_plan_ts). */
 #define MBRL_ABI_VERSION 13
 
 typedef struct ihipStream_t* mbrl_stream_t; /* == hipStream_t */
@@ -1109,6 +1110,76 @@ int mbrl_train_epoch_nll_clipped(const mbrl_train_model* members, int32_t E, con
 int mbrl_eval_members_nll(const mbrl_train_model* members, int32_t E, const mbrl_train_data* data,
                           const int64_t* rows, int64_t R, const mbrl_nll_bounds* bounds, float* row_nll,
                           float* row_err, float* row_lv, float* loss_out, mbrl_stream_t stream);
+
+/* ---- trajectory-sampling rollouts: CEM plans on sampled ensemble particles (PETS' TS-inf; added within ABI v13,
+ * additively: no existing entry, struct, option id or version number changes). The members are the
+ * probabilistic members above (mbrl_eval_members_nll's struct: live nn.Linear pointers, a head of 2 s rows,
+ * reward_head == 0; the gradient pointers are not read and `horizon` only has to be >= 1). Every candidate is rolled
+ * out as Q = E * particles rows; row q = e * particles + p is particle p of member e and stays on that member for
+ * the whole horizon. Per row q, candidate n < N and step t < H, with s_0 = s0 (s0[n] with s0_per_candidate), fp32
+ * throughout, round to nearest, no contraction, in this order:
+ *   1. x       = (normalize_state(s_t), normalize_action(a_t)), state first, each if its flag is set:
+ *                (v - mean) / std as written (oracle/cem.py model_input)
+ *   2. (m, r)  = the head on the trunk: mbrl_eval_members' k-ordered fma chains, one chain per output element
+ *   3. lv_j    = min_lv_j + softplus(u_j - min_lv_j), u_j = max_lv_j - softplus(max_lv_j - r_j): the bounded
+ *                log-variance of mbrl_train_grads_nll, softplus(x) = max(x, 0) + log1p(exp(-|x|))
+ *   4. sd_j    = expf(0.5f * lv_j) * noise_scale
+ *   5. eps_j   = element j & 3 of the four normals (two Box-Muller pairs, as the proposal draw makes them) of
+ *                Philox4x32-10 with counter (n + n_offset, t, q, (iteration << 8) | (j >> 2)) and the key
+ *                (low, high) half of noise_seed
+ *   6. z_j     = m_j + sd_j * eps_j: the noise is added in the space the members were trained in
+ *   7. s_{t+1} = z * obs_std + obs_mean if unnormalize_state, else z; this state is fed back
+ *   8. c_t     = sum_j (sqrt(((s_{t+1,j} - goal_j) * weights_j)^2 + alpha_state^2) - alpha_state), j ascending
+ *                (0 without has_state_cost), plus alpha_action^2 * ((sum_d (cosh(a_{t,d} / alpha_action) - 1), d
+ *                ascending) / a) on the raw action (0 without has_action_cost): MBRL_COST_GOAL_STATE
+ *   9. costs[q][n] = sum_t c_t, t ascending from 0.
+ * With noise_scale == 0 the states are the mean rollout's: states_out[e * particles + p][t][n] then equals
+ * mbrl_eval_members_open_loop's pred_out[e][n][t] byte for byte where norm is NULL (the same chains).
+ * mbrl_rollout_cost_ts: one launch, grid (ceil(N / 16), Q), no workspace, no atomics, no workgroup waits on another;
+ * stream-ordered and capturable. The bytes of a (row, candidate) depend on that candidate's s0 and actions, its
+ * member's parameters, the bounds and its counter words alone: not on N, its position in a tile, its neighbours (a
+ * non-finite one included), the other members, particles (given q) or whether states_out is NULL.
+ * actions [H][N][a] (required: the proposal draw stays mbrl_sample_actions); costs [Q][N] (required); states_out
+ * [Q][H][N][s] or NULL; norm may be NULL (no flag set); cost NULL: every c_t is 0. iteration keys the noise only.
+ * Before any launch (the outputs stay untouched): the argument checks and codes of mbrl_eval_members_nll, and
+ * MBRL_EINVAL for a NULL s0, actions, ts or costs, N < 1, H < 1, n_offset < 0, E > MBRL_TRAIN_MAX_MEMBERS,
+ * particles < 1, Q > MBRL_TS_MAX_ROWS, iteration outside [0, 2^24), a negative or non-finite noise_scale,
+ * action_dim < 1, MBRL_COST_MODEL_REWARD, a state cost without weights or goal, or a set normaliser flag with NULL
+ * statistics; MBRL_EUNSUPPORTED beyond the NLL entries' LDS envelope (above) or for an unknown cost kind.
+ *
+ * mbrl_cem_plan_ts: mbrl_cem_plan's loop with this rollout in place of the deterministic one. Per iteration `it`:
+ * the proposals (mbrl_sample_actions' values), mbrl_rollout_cost_ts with iteration = it (ts->iteration is not
+ * read, so every iteration's noise is fresh) into costs [Q][N], then the selection and refit of mbrl_cem_plan over
+ * those Q rows (returns[n] = (sum_q costs[q][n]) / Q, sequential in q): bit for bit mbrl_sample_actions,
+ * mbrl_rollout_cost_ts, mbrl_cem_update (or mbrl_select_elites + mbrl_cem_refit) with E = Q. states_out [H][s] is
+ * mbrl_trajectory's member mean for the final actions: deterministic, on the packed mean rows -- hence both
+ * shape / packed (mbrl_mlp_pack of the same members; ensemble = E, reward_head = 0, MBRL_PRECISION_F32) and
+ * members [shape->ensemble] / bounds. Records (NULL = off): cost_hist [I][Q][N], returns_hist [I][N], elite_hist
+ * [I][K]. ws: >= mbrl_cem_ts_workspace_bytes bytes (0 for bad arguments), any bytes on entry. Every argument check
+ * runs before the first launch. Out of scope for this entry: column-split pairs, sharding, batches, the
+ * receding-horizon and coloured-noise inputs, MPPI and the f16 precisions.
+ * Measured on the MI355X (s = 17, a = 6, E = 5, N = 4096, H = 30): 10.67 ms per launch at P = 1 and
+ * 36.96 ms at P = 4 for 2 x 512 members (0.21 / 0.25 of the fp32 MFMA peak), 19.82 / 61.32 ms for 3 x 512 (0.22 /
+ * 0.28); the deterministic mbrl_rollout_cost takes 2.69 / 4.91 ms for the 5 mean rows. The 16-candidate tile
+ * streams the live weights from L2 and is 3.1-4.0x slower per row than the packed-stream rollout kernel. */
+#define MBRL_TS_MAX_ROWS 256   /* Q = E * particles (PETS uses 20) */
+typedef struct {
+    int32_t particles;     /* P >= 1 per member */
+    int32_t iteration;     /* < 2^24; keys the noise (mbrl_cem_plan_ts passes its own) */
+    uint64_t noise_seed;
+    float noise_scale;     /* >= 0, finite; 1: the members' own variance, 0: the mean rollout */
+} mbrl_ts_params;
+int mbrl_rollout_cost_ts(const mbrl_train_model* members, int32_t E, const mbrl_nll_bounds* bounds,
+                         const mbrl_norm* norm, const mbrl_cost* cost, const float* s0, int32_t s0_per_candidate,
+                         const float* actions, int32_t N, int32_t H, int32_t n_offset, const mbrl_ts_params* ts,
+                         float* costs, float* states_out, mbrl_stream_t stream);
+size_t mbrl_cem_ts_workspace_bytes(const mbrl_mlp_shape* shape, const mbrl_cem_params* params,
+                                   const mbrl_ts_params* ts);
+int mbrl_cem_plan_ts(const mbrl_mlp_shape* shape, const void* packed, const mbrl_train_model* members,
+                     const mbrl_nll_bounds* bounds, const mbrl_norm* norm, const mbrl_cost* cost, const float* s0,
+                     const mbrl_cem_params* params, const mbrl_ts_params* ts, float* mu, float* sigma,
+                     float* actions_out, float* states_out, float* cost_hist, float* returns_hist,
+                     int64_t* elite_hist, void* ws, size_t ws_bytes, mbrl_stream_t stream);
 
 /* Keep-best snapshots: per member e, v = loss[e * loss_stride] (device) against best_loss[e] AS IT WAS ON
  * ENTRY. If v < best_loss[e] (a NaN is never better): best_loss[e] = v, best_epoch[e] = epoch,

@@ -83,6 +83,7 @@ EXPORTED = (
     "mbrl_dataset_stack", "mbrl_dataset_stats_workspace_bytes", "mbrl_dataset_stats",
     "mbrl_train_nll_workspace_bytes", "mbrl_train_grads_nll", "mbrl_train_epoch_nll", "mbrl_train_epoch_nll_clipped",
     "mbrl_eval_members_nll",
+    "mbrl_rollout_cost_ts", "mbrl_cem_ts_workspace_bytes", "mbrl_cem_plan_ts",
 )
 
 
@@ -174,6 +175,15 @@ class GradClip(ctypes.Structure):
 class NllBounds(ctypes.Structure):
     """mbrl_nll_bounds (include/mbrl_cem.h; added within ABI v13): the log-variance bounds of the NLL entries."""
     _fields_ = [("min_logvar", c_void_p), ("max_logvar", c_void_p)]
+
+
+TS_MAX_ROWS = 256          # MBRL_TS_MAX_ROWS: particle rows E * particles of the trajectory-sampling entries
+
+
+class TsParams(ctypes.Structure):
+    """mbrl_ts_params (include/mbrl_cem.h; added within ABI v13): the trajectory-sampling entries' particles and
+    noise key."""
+    _fields_ = [("particles", c_int32), ("iteration", c_int32), ("noise_seed", c_uint64), ("noise_scale", c_float)]
 
 
 class StackField(ctypes.Structure):
@@ -281,6 +291,14 @@ def load():
                                                    c_size_t, P, POINTER(NllBounds), POINTER(GradClip)]),
         "mbrl_eval_members_nll": (c_int32, [POINTER(TrainModel), c_int32, POINTER(TrainData), P, c_int64,
                                             POINTER(NllBounds), P, P, P, P, P]),
+        # trajectory-sampling rollouts on the probabilistic members
+        "mbrl_rollout_cost_ts": (c_int32, [POINTER(TrainModel), c_int32, POINTER(NllBounds), POINTER(Norm),
+                                           POINTER(Cost), P, c_int32, P, c_int32, c_int32, c_int32, POINTER(TsParams), P,
+                                           P, P]),
+        "mbrl_cem_ts_workspace_bytes": (c_size_t, [POINTER(MlpShape), POINTER(CemParams), POINTER(TsParams)]),
+        "mbrl_cem_plan_ts": (c_int32, [POINTER(MlpShape), P, POINTER(TrainModel), POINTER(NllBounds), POINTER(Norm),
+                                       POINTER(Cost), P, POINTER(CemParams), POINTER(TsParams), P, P, P, P, P, P, P, P,
+                                       c_size_t, P]),
         "mbrl_eval_members": (c_int32, [POINTER(TrainModel), c_int32, POINTER(TrainData), P, c_int64, P, P, P, P]),
         "mbrl_eval_members_open_loop": (c_int32, [POINTER(TrainModel), c_int32, POINTER(TrainData), P, c_int64, P, P, P, P,
                                                   P]),
@@ -510,4 +528,4 @@ __all__ = ["load", "check", "ptr", "stream_handle", "MlpShape", "Norm", "Cost", 
            "ABI_VERSION", "c_int64", "MBRL_PRECISION_F32", "MBRL_PRECISION_F16X3", "MBRL_PRECISION_F16X6",
            "precision_code", "load_other", "option", "OPTIONS", "AdamTensor", "AdamHparams",
            "TrainModel", "TrainData", "NllBounds", "TRAIN_MAX_LAYERS", "TRAIN_MAX_MEMBERS", "HostStaging", "CopyTensor",
-           "StackField", "StatsField"]
+           "StackField", "StatsField", "TsParams", "TS_MAX_ROWS"]

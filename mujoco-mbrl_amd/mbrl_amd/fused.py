@@ -565,6 +565,77 @@ def rollout(prob, s0, N, H, *, actions=None, sampler=None, n_offset=0, s0_per_ca
     return costs
 
 
+class TsMembers:
+    """The trajectory-sampling entries' member table for an EnsembleModel of ProbabilisticModels on `device`: the
+    live weights and biases (the way models._NativeEval binds them, no gradients) and member 0's log-variance
+    bounds. Raises NotImplementedError for anything else."""
+
+    def __init__(self, module, device):
+        members = getattr(module, "members", None)
+        if not isinstance(module, EnsembleModel) or not all(isinstance(m, ProbabilisticModel) for m in members):
+            raise NotImplementedError("particles: the model must be an EnsembleModel of ProbabilisticModels")
+        m0 = members[0]
+        if len(members) > _lib.TRAIN_MAX_MEMBERS:
+            raise NotImplementedError(f"particles: at most {_lib.TRAIN_MAX_MEMBERS} members")
+        if not all(torch.equal(m.min_logvar, m0.min_logvar) and torch.equal(m.max_logvar, m0.max_logvar)
+                   for m in members):
+            raise NotImplementedError("particles: the members' log-variance bounds differ")
+        self.params = [[t for lin in m.linears() for t in (lin.weight, lin.bias)] for m in members]
+        tensors = [t for params in self.params for t in params] + [m0.min_logvar, m0.max_logvar]
+        if not all(t.device == torch.device(device) and t.dtype == torch.float32 and t.is_contiguous() for t in tensors):
+            raise NotImplementedError("particles: the members' parameters and bounds must be contiguous float32 "
+                                      f"tensors on {device}")
+        self.E = len(members)
+        self.models = (_lib.TrainModel * self.E)()
+        for m, model, params in zip(self.models, members, self.params):
+            m.state_dim, m.action_dim, m.hidden = model.state_dim, model.action_dim, model.hidden_units
+            m.n_hidden, m.reward_head, m.horizon = model.n_hidden, 0, 1
+            for i in range(len(params) // 2):
+                m.weight[i], m.bias[i] = params[2 * i].data_ptr(), params[2 * i + 1].data_ptr()
+        self._bound_t = (m0.min_logvar, m0.max_logvar)
+        self.bounds = _lib.NllBounds(m0.min_logvar.data_ptr(), m0.max_logvar.data_ptr())
+        self.refs = (self.models, ctypes_ref(self.bounds))
+
+
+_TS_MEMBERS = weakref.WeakKeyDictionary()   # module -> (key, TsMembers)
+
+
+def ts_members(module, device):
+    """Cached TsMembers, keyed like the packed weights (_param_key: the Parameters' pointers and versions, so
+    training between two plans is seen) and by every member's bounds."""
+    members = getattr(module, "members", None) or []
+    key = (_param_key([m.linears() for m in members if hasattr(m, "linears")], device),
+           tuple(_tensor_key(getattr(m, b, None)) for m in members for b in ("min_logvar", "max_logvar")))
+    hit = _TS_MEMBERS.get(module)
+    if hit is not None and hit[0] == key:
+        return hit[1]
+    table = TsMembers(module, device)
+    _TS_MEMBERS[module] = (key, table)
+    return table
+
+
+def ts_params(particles, iteration, noise_seed, noise_scale):
+    return _lib.TsParams(int(particles), int(iteration), int(noise_seed) & (2 ** 64 - 1), float(noise_scale))
+
+
+def rollout_ts(prob, s0, actions, *, particles, noise_seed, noise_scale=1.0, iteration=0, n_offset=0,
+               s0_per_candidate=False, costs=None, states_out=None):
+    """mbrl_rollout_cost_ts: the sampled rollout of `actions` [H, N, a] on particles rows per member of prob's
+    probabilistic ensemble. Returns costs [E * particles, N]; states_out: [E * particles, H, N, s] or None."""
+    lib = _lib.load()
+    dev = prob.device
+    table = ts_members(prob.mdesc["module"], dev)
+    H, N = int(actions.shape[0]), int(actions.shape[1])
+    if costs is None:
+        costs = torch.empty((table.E * int(particles), N), dtype=torch.float32, device=dev)
+    ts = ts_params(particles, iteration, noise_seed, noise_scale)
+    _lib.check(lib.mbrl_rollout_cost_ts(table.models, table.E, ctypes_ref(table.bounds), ctypes_ref(prob.norm),
+                                        ctypes_ref(prob.cost), _lib.ptr(s0), int(s0_per_candidate), _lib.ptr(actions),
+                                        N, H, n_offset, ctypes_ref(ts), _lib.ptr(costs), _lib.ptr(states_out),
+                                        _lib.stream_handle(dev)), "mbrl_rollout_cost_ts")
+    return costs
+
+
 def select(costs, K, nan_policy=_lib.MBRL_NAN_LAST, returns_out=None, workspace=None):
     """costs: [E, N] device tensor -> elite indices [K] (int64, ascending)."""
     lib = _lib.load()

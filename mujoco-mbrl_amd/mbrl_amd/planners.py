@@ -357,11 +357,23 @@ class CEMPlanner(ModelPlanner):
         unit norm keep sigma's meaning). Every entry finite, checked on the host. Naming both raises ValueError.
     Either routes the plan to the receding-horizon path (the unfused update), with or without a warm start
     or kept rows; horizon <= 64. The same refusals as the receding-horizon kwargs apply, and MPPIPlanner and
-    RandomShootingPlanner refuse them too."""
+    RandomShootingPlanner refuse them too.
+
+    Trajectory sampling (mbrl_cem_plan_ts; PETS' TS-inf, off by default): every candidate is rolled out as
+    `particles` sampled particles per ensemble member and scored by the mean over all of them.
+    particles (0): P. 0 is the plan above, byte for byte. P >= 1 needs an EnsembleModel of ProbabilisticModels
+        with equal log-variance bounds on the fused path and the goal-state cost; each particle stays on its
+        member and draws every next state from the member's predicted Gaussian (include/mbrl_cem.h).
+    particle_noise (1.0): the factor on the predicted standard deviation (0: the mean rollout on every particle).
+    particle_seed (None -> derived from seed): the key of the particles' noise.
+    plan_detailed(record=True) returns costs as [I, E * P, N]. The final predicted states stay the deterministic
+    member mean of the final actions. A negative value raises ValueError; with particles >= 1, distributed=True,
+    plan_batch, the receding-horizon and coloured-noise kwargs, a precision other than "f32", a CPU device and
+    callables or models the fused path does not recognise raise NotImplementedError."""
     defaults = dict(num_candidates=1000, num_elites=None, num_iterations=5, alpha=0.1, seed=None, init_std=None,
                     action_bounds=None, distributed=False, return_device=False, precision="f32",
                     warm_start=False, shift=1, warm_std=None, keep_elites=0, carry=None, noise_beta=0.0,
-                    noise_mix=None)
+                    noise_mix=None, particles=0, particle_noise=1.0, particle_seed=None)
 
     @staticmethod
     def plan(initial_state, model, cost, sample_action, horizon, initial_trajectory=None, **kwargs):
@@ -374,6 +386,7 @@ class CEMPlanner(ModelPlanner):
         """B plans at once, one per row of initial_states [B, s] (see cem_plan_batch)."""
         _rh_refuse(kwargs, "CEMPlanner.plan_batch")
         _noise_refuse(kwargs, "CEMPlanner.plan_batch")
+        _ts_refuse(kwargs, "CEMPlanner.plan_batch")
         return cem_plan_batch(initial_states, model, cost, sample_action, horizon, **kwargs)
 
     _SETTINGS = {}
@@ -421,6 +434,8 @@ class CEMPlanner(ModelPlanner):
     def plan_detailed(initial_state, model, cost, sample_action, horizon, initial_trajectory=None, **kwargs):
         """plan() plus diagnostics: dict(states, actions, mu, sigma[, costs, returns, elites per iteration]
         [, carry, carry_returns[, kept_hist]])."""
+        # (a plan that names no particle kwarg takes the paths below with nothing added to its host turn)
+        ts = _ts_inputs(kwargs) if any(k in kwargs for k in _TS_KWARGS) else None
         if kwargs.get("distributed", False):
             _rh_refuse(kwargs, "CEMPlanner with distributed=True")   # (before anything needs a device)
             _noise_refuse(kwargs, "CEMPlanner with distributed=True")
@@ -440,8 +455,13 @@ class CEMPlanner(ModelPlanner):
             if rh is not None and (mdesc is None or cdesc is None):
                 _rh_refuse(kwargs, "CEMPlanner with callables the fused path does not recognise")
                 _noise_refuse(kwargs, "CEMPlanner with callables the fused path does not recognise")
+            if ts is not None and (mdesc is None or cdesc is None):
+                raise NotImplementedError(f"CEMPlanner with callables the fused path does not recognise: particles="
+                                          f"{ts['P']} is not implemented (trajectory sampling runs on the fused path)")
             if mdesc is not None and cdesc is not None:
-                if rh is not None:
+                if ts is not None:
+                    res = _cem_fused_ts(prob, initial_state, st, ts)
+                elif rh is not None:
                     res = _cem_fused_rh(prob, initial_state, st, rh)
                 elif ws is None:
                     res = _cem_fused_single(prob, initial_state, st)
@@ -470,6 +490,64 @@ def _rh_refuse(kwargs, where):
         if v is not None and v is not False and not (k == "keep_elites" and not isinstance(v, bool) and v == 0):
             raise NotImplementedError(f"{where}: {k}={v!r} is not implemented (receding-horizon CEM plans are "
                                       "single-GPU, fused-path plans; batched: cem_plan_batch_rh)")
+
+
+_TS_KWARGS = ("particles", "particle_noise", "particle_seed")
+
+
+def _ts_values(kwargs):
+    """(particles, particle_noise, particle_seed) of kwargs, checked: ValueError for a negative, fractional or
+    non-finite value, before any work."""
+    d = CEMPlanner.defaults
+    P, noise, seed = (kwargs.get(k, d[k]) for k in _TS_KWARGS)
+    if isinstance(P, bool) or not isinstance(P, (int, np.integer)) or P < 0:
+        raise ValueError(f"particles={P!r}: need an integer >= 0")
+    if isinstance(noise, bool) or not np.isfinite(noise) or noise < 0:
+        raise ValueError(f"particle_noise={noise!r}: need a finite number >= 0")
+    if seed is not None and (isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or seed < 0):
+        raise ValueError(f"particle_seed={seed!r}: need None or an integer >= 0")
+    return int(P), float(noise), None if seed is None else int(seed)
+
+
+def _ts_refuse(kwargs, where):
+    """NotImplementedError naming `particles` where it is switched on: `where` has no trajectory-sampling form."""
+    if any(k in kwargs for k in _TS_KWARGS):
+        P = _ts_values(kwargs)[0]
+        if P >= 1:
+            raise NotImplementedError(f"{where}: particles={P} is not implemented (trajectory-sampling CEM plans "
+                                      "are single-GPU, single-problem, fused-path plans: CEMPlanner.plan)")
+
+
+def _ts_inputs(kwargs):
+    """The checked particle kwargs of CEMPlanner.plan_detailed as dict(P, noise, seed), or None with particles=0
+    (today's plan). With P >= 1, every kwarg the sampled plan has no form for raises NotImplementedError naming it,
+    before anything needs a device."""
+    P, noise, seed = _ts_values(kwargs)
+    if P == 0:
+        return None
+    where = f"CEMPlanner with particles={P}"
+    if kwargs.get("distributed", False):
+        raise NotImplementedError(f"{where}: distributed=True is not implemented")
+    _rh_refuse(kwargs, where)
+    _noise_refuse(kwargs, where)
+    precision = kwargs.get("precision", CEMPlanner.defaults["precision"])
+    if precision != "f32":
+        raise NotImplementedError(f"{where}: precision={precision!r} is not implemented (the sampled rollout is fp32)")
+    dev = kwargs.get("device")
+    if dev is not None and torch.device(dev).type != "cuda":
+        raise NotImplementedError(f"{where}: device={str(dev)!r} is not implemented (the sampled rollout is a HIP "
+                                  "kernel)")
+    return dict(P=P, noise=noise, seed=seed)
+
+
+def _ts_seed(seed):
+    """particle_seed=None: a key derived from the plan's seed (splitmix64's first output), so that the particles'
+    noise is not the proposals' Philox stream."""
+    m = (1 << 64) - 1
+    z = (int(seed) + 0x9E3779B97F4A7C15) & m
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & m
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & m
+    return z ^ (z >> 31)
 
 
 _NOISE_KWARGS = ("noise_beta", "noise_mix")
@@ -670,6 +748,7 @@ def cem_plan_batch(initial_states, model, cost, sample_action, horizon, **kwargs
     Closures the fused path does not recognise fall back to one CEMPlanner.plan per row."""
     _rh_refuse(kwargs, "cem_plan_batch")
     _noise_refuse(kwargs, "cem_plan_batch")
+    _ts_refuse(kwargs, "cem_plan_batch")
     dev = _device(kwargs)
     st = CEMPlanner._settings(sample_action, horizon, kwargs)
     B = int(initial_states.shape[0])
@@ -781,6 +860,7 @@ def cem_plan_batch_rh(initial_states, model, cost, sample_action, horizon, initi
     touches the device; closures the fused path does not recognise raise NotImplementedError."""
     if kwargs.get("distributed", False):
         raise NotImplementedError("cem_plan_batch_rh: distributed=True is not implemented")
+    _ts_refuse(kwargs, "cem_plan_batch_rh")
     noise = _noise_inputs(kwargs, int(horizon))
     for k, lists in (("carry", "carries"), ("prev_sigma", "prev_sigmas")):
         if kwargs.get(k) is not None:
@@ -1049,6 +1129,45 @@ def _cem_fused_single(prob, initial_state, st):
                                  _lib.stream_handle(dev)), "mbrl_cem_plan")
     _mark(pev, 1)
     if rec:
+        out.update(costs=cost_hist, returns=ret_hist, elites=elite_hist)
+    return out
+
+
+def _cem_fused_ts(prob, initial_state, st, ts):
+    """One C-ABI call: mbrl_cem_plan_ts, the plan on ts["P"] sampled particles per member. record=True returns the
+    costs as [I, E * P, N]."""
+    lib = _lib.load()
+    dev = prob.device
+    md = prob.mdesc
+    P = ts["P"]
+    where = f"CEMPlanner with particles={P}"
+    if md.get("reward") or prob.cdesc["kind"] != _lib.MBRL_COST_GOAL_STATE:
+        raise NotImplementedError(f"{where}: only the goal-state cost is implemented")
+    table = fused.ts_members(md["module"], dev)      # (NotImplementedError for any other model)
+    N, K, H, I = st["N"], st["K"], st["H"], st["I"]
+    a, s, Q = md["a"], md["s"], table.E * P
+    if Q > _lib.TS_MAX_ROWS:
+        raise NotImplementedError(f"{where}: {table.E} members x {P} particles exceed {_lib.TS_MAX_ROWS} rows")
+    seed = int(st["seed"]) & 0xFFFFFFFFFFFFFFFF
+    tsp = fused.ts_params(P, 0, _ts_seed(seed) if ts["seed"] is None else ts["seed"], ts["noise"])
+    pkey = ("ts", P, N, H, K, I, st["alpha"], st["lo"], st["hi"], st["init_std"], seed)
+    params, pref, need = _plan_params(prob, pkey, lambda: _cem_params(st, seed), lib.mbrl_cem_ts_workspace_bytes,
+                                      fused.ctypes_ref(tsp))
+    if need == 0:
+        raise RuntimeError(f"mbrl_cem_ts_workspace_bytes: {lib.mbrl_last_error().decode()}")
+    ws = _workspace(("cem_ts", str(dev)), need, dev)
+    s0 = initial_state.to(device=dev, dtype=torch.float32).contiguous()
+    out = _device_outputs(dev, H, s, a)
+    cost_hist, ret_hist, elite_hist = _cem_record_buffers(dev, st["record"], I, Q, N, K)
+    shape_ref, packed, norm_ref, cost_ref = prob.refs
+    pev = st["plan_events"]
+    _mark(pev, 0)
+    _lib.check(lib.mbrl_cem_plan_ts(shape_ref, packed, *table.refs, norm_ref, cost_ref, _lib.ptr(s0), pref,
+                                    fused.ctypes_ref(tsp), *_output_ptrs(out), _lib.ptr(cost_hist), _lib.ptr(ret_hist),
+                                    _lib.ptr(elite_hist), _lib.ptr(ws), ws.numel(), _lib.stream_handle(dev)),
+               "mbrl_cem_plan_ts")
+    _mark(pev, 1)
+    if st["record"]:
         out.update(costs=cost_hist, returns=ret_hist, elites=elite_hist)
     return out
 
