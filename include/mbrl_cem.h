@@ -1141,6 +1141,8 @@ int mbrl_eval_members_nll(const mbrl_train_model* members, int32_t E, const mbrl
  * non-finite one included), the other members, particles (given q) or whether states_out is NULL.
  * actions [H][N][a] (required: the proposal draw stays mbrl_sample_actions); costs [Q][N] (required); states_out
  * [Q][H][N][s] or NULL; norm may be NULL (no flag set); cost NULL: every c_t is 0. iteration keys the noise only.
+ * The group j >> 2 fits the eight bits beside it: the LDS envelope bounds s at 632 (2 * 16 * (2 * 632 + 4) * 4
+ * bytes <= 160 KiB), hence at most 158 groups.
  * Before any launch (the outputs stay untouched): the argument checks and codes of mbrl_eval_members_nll, and
  * MBRL_EINVAL for a NULL s0, actions, ts or costs, N < 1, H < 1, n_offset < 0, E > MBRL_TRAIN_MAX_MEMBERS,
  * particles < 1, Q > MBRL_TS_MAX_ROWS, iteration outside [0, 2^24), a negative or non-finite noise_scale,
@@ -1156,7 +1158,8 @@ int mbrl_eval_members_nll(const mbrl_train_model* members, int32_t E, const mbrl
  * shape / packed (mbrl_mlp_pack of the same members; ensemble = E, reward_head = 0, MBRL_PRECISION_F32) and
  * members [shape->ensemble] / bounds. Records (NULL = off): cost_hist [I][Q][N], returns_hist [I][N], elite_hist
  * [I][K]. ws: >= mbrl_cem_ts_workspace_bytes bytes (0 for bad arguments), any bytes on entry. Every argument check
- * runs before the first launch. Out of scope for this entry: column-split pairs, sharding, batches, the
+ * runs before the first launch. The packed shape bounds this entry at four hidden layers (mbrl_rollout_cost_ts
+ * alone runs eight). Out of scope for this entry: column-split pairs, sharding, batches, the
  * receding-horizon and coloured-noise inputs, MPPI and the f16 precisions.
  * Measured on the MI355X (s = 17, a = 6, E = 5, N = 4096, H = 30): 10.67 ms per launch at P = 1 and
  * 36.96 ms at P = 4 for 2 x 512 members (0.21 / 0.25 of the fp32 MFMA peak), 19.82 / 61.32 ms for 3 x 512 (0.22 /

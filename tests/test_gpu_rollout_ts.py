@@ -1,12 +1,13 @@
 """GPU: trajectory-sampling rollouts (csrc/rollout_ts.hip: mbrl_rollout_cost_ts, mbrl_cem_plan_ts) and
 CEMPlanner(particles=P) on top of them.
 
-Accuracy: over tests/rollout_ts_reference.py's cases, states_out and costs against the float64 restatement at the
-project's bar -- the tensor-relative error within 8 x max(the float32 CPU chain's error on that tensor, the
-table's median of it). Everything else is equality byte for byte: against mbrl_eval_members_open_loop without
+Accuracy: over tests/rollout_ts_reference.py's two tables (the ten cases and the envelope), states_out and costs
+against the float64 restatement at the project's bar -- the tensor-relative error within 8 x max(the float32 CPU
+chain's error on that tensor, the first table's median of it). Everything else is equality byte for byte: against mbrl_eval_members_open_loop without
 noise, across N, tile positions, neighbours, members, particle counts, NULL outputs and prior output bytes, and
 the whole plan against its step-by-step equivalent. measure_all() returns what profiles/rollout_ts/errors.json
 holds."""
+import collections
 import copy
 import ctypes
 import functools
@@ -40,7 +41,7 @@ def _t(x):
 @functools.lru_cache(maxsize=None)
 def device_members(name):
     """Per member the device tensors (w0, b0, w1, ..) of the case, the listed members 4 bytes off alignment."""
-    c, p = ref.CASES[name], ref.problem(name)
+    c, p = ref.case(name), ref.problem(name)
     out = []
     for e, layers in enumerate(p["members"]):
         params = [_t(x) for wb in layers for x in wb]
@@ -85,7 +86,7 @@ def run_ts(name, members=None, with_states=True, fill="nan", raw=False, **overri
     device tensors instead, whatever rc is."""
     from mbrl_amd import _lib
     lib = _lib.load()
-    c, p = ref.CASES[name], dict(ref.problem(name), **override)
+    c, p = ref.case(name), dict(ref.problem(name), **override)
     members = device_members(name) if members is None else members
     E, P = len(members), p["P"]
     H, N = p["actions"].shape[:2]
@@ -99,8 +100,9 @@ def run_ts(name, members=None, with_states=True, fill="nan", raw=False, **overri
     states = _filled((Q, H, N, c.s), fill) if with_states else None
     costs = _filled((Q, N), fill)
     rc = lib.mbrl_rollout_cost_ts(_table(members, c.s, c.a, c.W, c.L), E, ctypes.byref(bounds),
-                                  None if norm is None else ctypes.byref(norm), ctypes.byref(cost), _P(s0),
-                                  int(np.ndim(p["s0"]) == 2), _P(actions), N, H, p["n_offset"], ctypes.byref(ts), _P(costs),
+                                  None if norm is None else ctypes.byref(norm),
+                                  None if p.get("cost_null") else ctypes.byref(cost), _P(s0), int(np.ndim(p["s0"]) == 2),
+                                  _P(actions), N, H, ctypes.c_int32(p["n_offset"]), ctypes.byref(ts), _P(costs),
                                   None if states is None else _P(states), _lib.stream_handle(DEV))
     torch.cuda.synchronize()
     if raw:
@@ -126,14 +128,16 @@ def _shares(name):
 
 
 def measure_all():
-    """Per case and tensor: e(gpu), the float32 CPU chain's e32, the bar and e(gpu) / bar; and the largest share."""
+    """Per case of both tables and tensor: e(gpu), the float32 CPU chain's e32, the bar and e(gpu) / bar; and the
+    largest share of the first table and of the envelope."""
     out = {n: {k: dict(e_gpu=v[0], e32=v[1], bar=v[2], share=v[0] / v[2] if v[2] else 0.0) for k, v in _shares(n).items()}
-           for n in ref.NAMES}
+           for n in ref.ALL_NAMES}
     out["largest_share_of_the_bar"] = max(t["share"] for n in ref.NAMES for t in out[n].values())
+    out["largest_envelope_share_of_the_bar"] = max(t["share"] for n in ref.ENV_NAMES for t in out[n].values())
     return out
 
 
-@pytest.mark.parametrize("name", ref.NAMES)
+@pytest.mark.parametrize("name", ref.ALL_NAMES)
 def test_rollout_ts_matches_float64(name):
     failures = []
     for k, (e, own, bar) in _shares(name).items():
@@ -175,14 +179,21 @@ BIG = "n40_e5p4_state"      # N = 40 (three tiles, the last one partial), E = 5,
 
 def _slice(name, lo, hi):
     p = ref.problem(name)
+    if np.ndim(p["s0"]) == 1:
+        return dict(actions=np.ascontiguousarray(p["actions"][:, lo:hi]), n_offset=p["n_offset"] + lo)
     return dict(s0=p["s0"][lo:hi], actions=np.ascontiguousarray(p["actions"][:, lo:hi]), n_offset=p["n_offset"] + lo)
 
 
-@pytest.mark.parametrize("lo, hi", [(0, 17), (16, 40), (23, 24), (5, 40), (39, 40)])
-def test_a_candidate_does_not_depend_on_n_or_its_tile_position(lo, hi):
+_SLICES = [(BIG, 0, 17), (BIG, 16, 40), (BIG, 23, 24), (BIG, 5, 40), (BIG, 39, 40), ("e8p32", 5, 17), ("e1p256", 16, 17),
+           ("s632_n17", 3, 17), ("a48", 0, 16), ("key_n_offset", 8, 17)]
+
+
+@pytest.mark.parametrize("name, lo, hi", _SLICES,
+                         ids=[f"{lo}-{hi}" if n == BIG else f"{n}-{lo}-{hi}" for n, lo, hi in _SLICES])
+def test_a_candidate_does_not_depend_on_n_or_its_tile_position(name, lo, hi):
     """Candidates [lo, hi) alone, with n_offset = lo, are the full call's columns: another N, another position in
-    the tile, other neighbours; n_offset = k on [k, N) is the tail of the full call."""
-    full, part = default_run(BIG), run_ts(BIG, **_slice(BIG, lo, hi))
+    the tile, other neighbours; n_offset = k on [k, N) is the tail of the full call (key_n_offset: past 2^31)."""
+    full, part = default_run(name), run_ts(name, **_slice(name, lo, hi))
     assert part["states"].tobytes() == np.ascontiguousarray(full["states"][:, :, lo:hi]).tobytes()
     assert part["costs"].tobytes() == np.ascontiguousarray(full["costs"][:, lo:hi]).tobytes()
 
@@ -223,12 +234,19 @@ def test_a_row_depends_on_its_index_and_member_not_on_the_particle_count():
         assert all(other["states"][q].tobytes() != base["states"][q].tobytes() for q in range(6)), change
 
 
-@pytest.mark.parametrize("name", [BIG, "n1_s33_null", "w1024", "no_cost_half_noise"])
+@pytest.mark.parametrize("name", [BIG, "n1_s33_null", "w1024", "no_cost_half_noise", "e8p32", "e1p256", "s632_n17", "a48",
+                                  "a1023"])
 def test_prior_output_bytes_and_a_null_states_out_never_matter(name):
     base = default_run(name)
     assert all(np.all(np.isfinite(v)) for v in base.values())          # NaN-filled outputs were fully written
     assert _same(base, run_ts(name, fill="ff")) and _same(base, run_ts(name))
     assert base["costs"].tobytes() == run_ts(name, with_states=False)["costs"].tobytes()
+
+
+def test_a_null_cost_is_zero_cost_and_the_states_of_both_flags_off():
+    got, flags_off = default_run("cost_null"), run_ts("cost_null", cost_null=False)
+    assert got["costs"].tobytes() == np.zeros_like(got["costs"]).tobytes()       # exactly +0.0
+    assert _same(got, flags_off) and np.all(np.isfinite(got["states"]))
 
 
 def _bad_calls():
@@ -289,6 +307,10 @@ def test_struct_level_argument_errors():
     null_layer = _table(mems, c.s, c.a, c.W, c.L)
     null_layer[1].bias[c.L] = None
     wide = _table(mems, 640, c.a, c.W, c.L)                      # 2 s = 1280: 32 x 1284 floats exceed 160 KiB
+    # the largest head is s = 632 (the s632 cases run it): 2 x 16 x (1264 + 4) x 4 = 162304 <= 160 KiB = 163840 bytes;
+    # s = 633 rounds 2 s = 1266 up to 1280 columns: 2 x 16 x 1284 x 4 = 164352
+    s633 = _table(mems, 633, 1, 16, 1)
+    deep = _table(mems, c.s, c.a, c.W, 9)                        # n_hidden <= MBRL_TRAIN_MAX_LAYERS - 2 = 8 (case l8)
     for label, rc, want in (
             ("NULL bounds", call(bounds=None), EINVAL), ("NULL bound array", call(bounds=(lo, None)), EINVAL),
             ("NULL s0", call(s0_=None), EINVAL), ("NULL actions", call(actions_=None), EINVAL),
@@ -298,7 +320,8 @@ def test_struct_level_argument_errors():
             ("reward head", call(tms=reward), EINVAL), ("member shapes differ", call(tms=differs), EINVAL),
             ("action_dim < 1", call(tms=no_action), EINVAL), ("NULL layer", call(tms=null_layer), EINVAL),
             ("MODEL_REWARD", call(cost_kind=1), EINVAL), ("unknown cost kind", call(cost_kind=7), EUNSUPPORTED),
-            ("beyond the LDS envelope", call(tms=wide), EUNSUPPORTED)):
+            ("beyond the LDS envelope", call(tms=wide), EUNSUPPORTED), ("s = 633", call(tms=s633), EUNSUPPORTED),
+            ("n_hidden = 9", call(tms=deep), EUNSUPPORTED)):
         assert rc == want, (label, rc, lib.mbrl_last_error())
     torch.cuda.synchronize()
     assert bool(torch.isnan(states).all()) and bool(torch.isnan(costs).all())
@@ -332,16 +355,35 @@ def _closures(ens, s, a, seed=5):
     return model_fn, cost_fn, env.sample_action_fn(env.BoundedActionSpec(a, LO, HI)), torch.randn(s, generator=g)
 
 
-# N ceil(a / 4) below the fused draw's 65536 limit (the update draws the next proposals) and above it (a draw launch)
-@pytest.mark.parametrize("N, H, I", [(300, 3, 3), (30000, 2, 2)])
-def test_plan_equals_its_step_by_step_equivalent(N, H, I):
+_Plan = collections.namedtuple("_Plan", "N H I K E P s a W L pseed unfused", defaults=(2, 2, 5, 12, 33, 2, 123456789, 0))
+PLANS = {
+    # N ceil(a / 4) below the fused draw's 65536 limit (the update draws the next proposals) and above it (a draw launch)
+    "300-3-3": _Plan(300, 3, 3, 30), "30000-2-2": _Plan(30000, 2, 2, 3000),
+    # Q = 256 rows through the fused update, and through the selection and the refit
+    "q256": _Plan(64, 2, 2, 6, E=8, P=32, s=3, a=17, W=16, L=1),
+    "q256_unfused": _Plan(64, 2, 2, 6, E=8, P=32, s=3, a=17, W=16, L=1, unfused=1),
+    "k1": _Plan(300, 3, 2, 1, E=3), "k_is_n": _Plan(64, 2, 2, 64, E=3),
+    # the plan's deepest trunk: its final trajectory runs on the packed members, which hold four hidden layers
+    "l4_w17": _Plan(64, 2, 2, 6, W=17, L=4),
+    "seed64": _Plan(64, 2, 2, 6, pseed=ref.SEED64),
+}
+
+
+@pytest.mark.parametrize("plan", list(PLANS))
+def test_plan_equals_its_step_by_step_equivalent(plan):
+    from mbrl_amd import _lib
+    with _lib.option("unfused_update", PLANS[plan].unfused):
+        _plan_equals_its_step_by_step_equivalent(*PLANS[plan][:-1])
+
+
+def _plan_equals_its_step_by_step_equivalent(N, H, I, K, E, P, s, a, W, L, pseed):
     from mbrl_amd import CEMPlanner, fused, planners
-    s, a, E, P, K, alpha, seed, pseed = 5, 12, 2, 2, max(1, N // 10), 0.1, 77, 123456789
-    ens = _prob_ensemble(E, s, a, 33, 2, seed=3)
+    alpha, seed = 0.1, 77
+    ens = _prob_ensemble(E, s, a, W, L, seed=3)
     model_fn, cost_fn, sample, s0 = _closures(ens, s, a)
-    res = CEMPlanner.plan_detailed(s0, model_fn, cost_fn, sample, H, num_candidates=N, num_iterations=I, seed=seed,
-                                   particles=P, particle_seed=pseed, particle_noise=0.75, record=True, return_device=True,
-                                   device=str(DEV))
+    kw = dict(num_candidates=N, num_iterations=I, num_elites=K, seed=seed, particles=P, particle_noise=0.75, device=str(DEV))
+    res = CEMPlanner.plan_detailed(s0, model_fn, cost_fn, sample, H, particle_seed=pseed, record=True, return_device=True,
+                                   **kw)
     assert res["costs"].shape == (I, E * P, N) and res["returns"].shape == (I, N) and res["elites"].shape == (I, K)
     _, _, prob = fused.describe_problem(model_fn, cost_fn, DEV, 0)
     s0d = s0.to(DEV)
@@ -369,22 +411,39 @@ def test_plan_equals_its_step_by_step_equivalent(N, H, I):
     assert torch.equal(mu, res["mu"]) and torch.equal(sg, res["sigma"])
     assert torch.equal(actions, res["actions"]) and torch.equal(states, res["states"])
     # the derived noise key, and host tensors by default
-    auto = CEMPlanner.plan_detailed(s0, model_fn, cost_fn, sample, H, num_candidates=N, num_iterations=I, seed=seed,
-                                    particles=P, particle_noise=0.75, device=str(DEV))
-    same = CEMPlanner.plan_detailed(s0, model_fn, cost_fn, sample, H, num_candidates=N, num_iterations=I, seed=seed,
-                                    particles=P, particle_noise=0.75, particle_seed=planners._ts_seed(seed), device=str(DEV))
+    auto = CEMPlanner.plan_detailed(s0, model_fn, cost_fn, sample, H, **kw)
+    same = CEMPlanner.plan_detailed(s0, model_fn, cost_fn, sample, H, particle_seed=planners._ts_seed(seed), **kw)
     assert not auto["actions"].is_cuda and torch.equal(auto["actions"], same["actions"])
-    assert not torch.equal(auto["mu"].cpu(), res["mu"].cpu())
+    assert K == N or not torch.equal(auto["mu"].cpu(), res["mu"].cpu())   # (K = N: every candidate is an elite)
+    if pseed >> 32:                             # the key's second word reaches the plan's noise
+        low = CEMPlanner.plan_detailed(s0, model_fn, cost_fn, sample, H, particle_seed=pseed & 0xFFFFFFFF, record=True, **kw)
+        assert not torch.equal(low["costs"][0].cpu(), res["costs"][0].cpu())
+        assert not torch.equal(low["mu"].cpu(), res["mu"].cpu())
 
 
-@pytest.mark.parametrize("unfused", [0, 1])
-def test_the_plan_does_not_depend_on_its_workspaces_prior_bytes(unfused):
+def test_a_trunk_deeper_than_the_packed_members_is_refused_by_the_plan():
+    """mbrl_rollout_cost_ts runs n_hidden = 8 (case l8); the plan also needs the packed members for its final
+    trajectory, and those hold at most four hidden layers."""
+    from mbrl_amd import CEMPlanner
+    ens = _prob_ensemble(2, 5, 12, 17, 8, seed=3)
+    model_fn, cost_fn, sample, s0 = _closures(ens, 5, 12)
+    with pytest.raises(RuntimeError, match="unsupported MLP shape"):
+        CEMPlanner.plan_detailed(s0, model_fn, cost_fn, sample, 2, num_candidates=64, num_iterations=1, seed=1, particles=2,
+                                 device=str(DEV))
+
+
+_Q6, _Q256 = (5, 12, 3, 2, 300, 3, 30, 33, 2), (3, 17, 8, 32, 64, 2, 6, 16, 1)
+
+
+@pytest.mark.parametrize("unfused, s, a, E, P, N, H, K, W, L", [(0, *_Q6), (1, *_Q6), (0, *_Q256), (1, *_Q256)],
+                         ids=["0", "1", "q256-0", "q256-1"])
+def test_the_plan_does_not_depend_on_its_workspaces_prior_bytes(unfused, s, a, E, P, N, H, K, W, L):
     """mbrl_cem_plan_ts with exactly mbrl_cem_ts_workspace_bytes bytes holding zeros, 0xFF and NaNs: every output and
     record the same bytes, with the fused update and with separate select and refit launches."""
     from mbrl_amd import _lib, fused
     lib = _lib.load()
-    s, a, E, P, N, H, K, I = 5, 12, 3, 2, 300, 3, 30, 2
-    ens = _prob_ensemble(E, s, a, 33, 2, seed=6)
+    I = 2
+    ens = _prob_ensemble(E, s, a, W, L, seed=6)
     model_fn, cost_fn, _, s0 = _closures(ens, s, a)
     _, _, prob = fused.describe_problem(model_fn, cost_fn, DEV, 0)
     table = fused.ts_members(ens, DEV)
