@@ -52,7 +52,9 @@ extern "C" {
  * mbrl_stats_field, mbrl_dataset_stats_workspace_bytes, mbrl_dataset_stats), and probabilistic members trained on
  * the Gaussian negative log-likelihood (mbrl_nll_bounds, mbrl_train_nll_workspace_bytes, mbrl_train_grads_nll,
  * mbrl_train_epoch_nll, mbrl_train_epoch_nll_clipped, mbrl_eval_members_nll), and trajectory-sampling rollouts on
- * them (mbrl_ts_params, mbrl_rollout_cost_ts, mbrl_cem_ts_workspace_bytes, mbrl_cem_plan_ts). */
+ * them (mbrl_ts_params, mbrl_rollout_cost_ts, mbrl_cem_ts_workspace_bytes, mbrl_cem_plan_ts), then the per-step
+ * member draw and the receding-horizon plans on sampled rows (mbrl_ts_rows, mbrl_rollout_cost_ts_rows,
+ * mbrl_cem_ts_rh_workspace_bytes, mbrl_cem_plan_ts_rh, mbrl_cem_plan_ts_rh_batch). */
 #define MBRL_ABI_VERSION 13
 
 typedef struct ihipStream_t* mbrl_stream_t; /* == hipStream_t */
@@ -1183,6 +1185,69 @@ int mbrl_cem_plan_ts(const mbrl_mlp_shape* shape, const void* packed, const mbrl
                      const mbrl_cem_params* params, const mbrl_ts_params* ts, float* mu, float* sigma,
                      float* actions_out, float* states_out, float* cost_hist, float* returns_hist,
                      int64_t* elite_hist, void* ws, size_t ws_bytes, mbrl_stream_t stream);
+
+/* ---- sampled rows for the control loop: a per-step member draw (PETS' TS-1), and the receding-horizon plan on
+ * sampled rows, single and batched (added within ABI v13, additively: no existing entry, struct, option id or
+ * version number changes).
+ * Member modes of the sampled rollout -- only step 2's member of the nine steps above changes:
+ *   MBRL_TS_MEMBER_FIXED (0):     the rows above. Q = E * particles, row q stays on member q / particles.
+ *   MBRL_TS_MEMBER_RESAMPLED (1): Q = particles rows in all, 1 <= Q <= MBRL_TS_MAX_ROWS, independent of E. Row q at
+ *       step t runs member e(q, t) = (uint64(w.x) * E) >> 32, w = Philox4x32-10 of counter
+ *       (0, t, q, (iteration << 8) | 0xFF) with the key (low, high) half of noise_seed. The state noise uses the
+ *       groups j >> 2 < 158, so group byte 0xFF collides with no noise counter, whatever n + n_offset is. The draw
+ *       is shared by all candidates, by design: every candidate's row q sees the same member sequence, so return
+ *       differences between candidates carry no member-assignment noise. Every other step is unchanged, the noise
+ *       counter (n + n_offset, t, q, (iteration << 8) | g) included.
+ * mbrl_rollout_cost_ts_rows: mbrl_rollout_cost_ts with the mode and one more output; FIXED returns that entry's
+ * bytes. members_out [Q][H] int32 or NULL: the member each row ran at each step (q / particles in FIXED mode, the
+ * draw in RESAMPLED mode), written by the tile-0 workgroups only: a diagnostic. The launch, its independence
+ * properties (a (row, candidate) also does not depend on whether members_out is NULL) and costs / states_out are
+ * mbrl_rollout_cost_ts's with Q as above. Before any launch, the outputs untouched: that entry's checks and codes;
+ * NULL rows or an unknown member_mode: MBRL_EINVAL; in RESAMPLED mode the Q bound applies to particles itself.
+ *
+ * mbrl_cem_plan_ts_rh / mbrl_cem_plan_ts_rh_batch: mbrl_cem_plan_rh / mbrl_cem_plan_rh_batch with the sampled
+ * rollout (iteration = it, rows->ts.iteration is not read) in place of the deterministic one. Inputs, outputs,
+ * flags and records are the siblings' with three differences: no events, no mix, and cost_hist has Q rows
+ * ([I][Q][N], batched [I][Q][B N]). Every plan runs the kept-rows loop (the selections and the staged refit over
+ * Q rows; returns[n] = (sum_q costs[q][n]) / Q), whatever keep is: with keep == 0, no rows and FIXED mode the
+ * outputs and cost_hist are mbrl_cem_plan_ts's byte for byte. Problem b's candidate n has Philox index b N + n for
+ * the proposals and the particle noise alike (the rollout is one launch over B N candidates with per-candidate
+ * start states, n_offset 0); problem 0 of a batch and a B == 1 batch are the single plan byte for byte.
+ * states_out is the deterministic member-mean trajectory on the packed mean rows, as in mbrl_cem_plan_ts.
+ * ws: >= mbrl_cem_ts_rh_workspace_bytes(shape, params, rows, B) (B = 1 also serves the single plan; 0 for bad
+ * arguments), any bytes on entry. Every check runs before the first launch: mbrl_cem_plan_ts's and the
+ * receding-horizon siblings', each with its sibling's code (a small workspace: MBRL_EINVAL from the single plan,
+ * MBRL_EWORKSPACE from the batch). Out of scope: coloured noise, sharding, column-split pairs, MPPI, the f16
+ * precisions and a reward-head cost.
+ * Measured on the MI355X: DESIGN.md §9f. */
+#define MBRL_TS_MEMBER_FIXED 0
+#define MBRL_TS_MEMBER_RESAMPLED 1
+typedef struct {
+    mbrl_ts_params ts;     /* RESAMPLED: ts.particles is Q */
+    int32_t member_mode;   /* MBRL_TS_MEMBER_* */
+    int32_t _pad;
+} mbrl_ts_rows;
+int mbrl_rollout_cost_ts_rows(const mbrl_train_model* members, int32_t E, const mbrl_nll_bounds* bounds,
+                              const mbrl_norm* norm, const mbrl_cost* cost, const float* s0, int32_t s0_per_candidate,
+                              const float* actions, int32_t N, int32_t H, int32_t n_offset, const mbrl_ts_rows* rows,
+                              float* costs, float* states_out, int32_t* members_out, mbrl_stream_t stream);
+size_t mbrl_cem_ts_rh_workspace_bytes(const mbrl_mlp_shape* shape, const mbrl_cem_rh_params* params,
+                                      const mbrl_ts_rows* rows, int32_t B);
+int mbrl_cem_plan_ts_rh(const mbrl_mlp_shape* shape, const void* packed, const mbrl_train_model* members,
+                        const mbrl_nll_bounds* bounds, const mbrl_norm* norm, const mbrl_cost* cost, const float* s0,
+                        const mbrl_cem_rh_params* params, const mbrl_ts_rows* rows, const float* init_mu_rows,
+                        const float* init_sigma_rows, const float* carry_in, float* mu, float* sigma,
+                        float* actions_out, float* states_out, float* carry_out, float* carry_returns_out,
+                        float* cost_hist, float* returns_hist, int64_t* elite_hist, float* kept_hist, void* ws,
+                        size_t ws_bytes, mbrl_stream_t stream);
+int mbrl_cem_plan_ts_rh_batch(const mbrl_mlp_shape* shape, const void* packed, const mbrl_train_model* members,
+                              const mbrl_nll_bounds* bounds, const mbrl_norm* norm, const mbrl_cost* cost,
+                              const float* s0, int32_t B, const mbrl_cem_rh_params* params, const mbrl_ts_rows* rows,
+                              const float* init_mu_rows, const float* init_sigma_rows, const float* carry_in,
+                              const int32_t* input_flags, float* mu, float* sigma, float* actions_out,
+                              float* states_out, float* carry_out, float* carry_returns_out, float* cost_hist,
+                              float* returns_hist, int64_t* elite_hist, float* kept_hist, void* ws, size_t ws_bytes,
+                              mbrl_stream_t stream);
 
 /* Keep-best snapshots: per member e, v = loss[e * loss_stride] (device) against best_loss[e] AS IT WAS ON
  * ENTRY. If v < best_loss[e] (a NaN is never better): best_loss[e] = v, best_epoch[e] = epoch,

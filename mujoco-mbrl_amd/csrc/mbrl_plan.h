@@ -79,4 +79,46 @@ int final_trajectory(const Geometry& g, const void* packed, const mbrl_norm* nor
                      const float* actions, int H, float* states_out, float* member_scratch, const TrajScratch& ts,
                      hipStream_t stream, int prezeroed, float* member_out = nullptr);
 
+// A sampled-rollout source for the receding-horizon loop (rollout_ts.hip): the checked launch arguments of
+// mbrl_rollout_cost_ts_rows and its row count Q. ts_source_rollout runs iteration `it`'s launch over BN candidates
+// with per-candidate start states (candidate n has Philox index n: problem b's are b N + n) into costs [Q][BN].
+struct TsLaunch;
+struct TsSource {
+    const TsLaunch* launch;
+    int Q;
+};
+int ts_source_rollout(const TsSource& ts, const float* s0, const float* actions, int BN, int it, float* costs,
+                      hipStream_t stream);
+
+// One receding-horizon entry's arguments. The single entries: B = 1, no flags; the batched ones: no events;
+// the white ones (and a mixed one called without a mix): mix NULL. ts (NULL: none): the sampled-rollout source of
+// mbrl_cem_plan_ts_rh / mbrl_cem_plan_ts_rh_batch -- no events, no mix, Q cost rows.
+struct RhCall {
+    const char* name;   // the entry, for the messages
+    bool batched;       // mbrl_cem_plan_rh_batch's layouts, and s0 checked with the other pointers
+    const mbrl_mlp_shape* shape;
+    const void* packed;
+    const mbrl_norm* norm;
+    const mbrl_cost* cost;
+    const float* s0;
+    int B;
+    const mbrl_cem_rh_params* rp;
+    const float *mu_rows, *sigma_rows, *carry_in;
+    const int32_t* flags;
+    const float* mix;
+    float *mu, *sigma, *actions_out, *states_out, *carry_out, *carry_returns_out, *cost_hist, *returns_hist;
+    int64_t* elite_hist;
+    float* kept_hist;
+    mbrl_event_t* events;
+    void* workspace;
+    size_t ws_bytes;
+    mbrl_stream_t stream;
+    const TsSource* ts = nullptr;
+};
+
+// The receding-horizon entries' one body (plan.hip): every check, then the loop. rh_ts_workspace_bytes: what a
+// call with a source of Q rows demands (0 for a bad shape, bad params or B < 1).
+int rh_plan(const RhCall& c);
+size_t rh_ts_workspace_bytes(const mbrl_mlp_shape* shape, const mbrl_cem_rh_params* rp, int Q, int B);
+
 }  // namespace mbrl

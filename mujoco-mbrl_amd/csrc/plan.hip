@@ -1074,8 +1074,10 @@ struct RhBatchWs {
     size_t bytes;
 };
 
-// mixed: the staged elites and the returns also with keep == 0.
-static RhBatchWs rh_batch_ws(const Geometry& g, const mbrl_cem_rh_params* rp, int B, void* base, bool mixed = false) {
+// mixed: the staged elites and the returns also with keep == 0. ts_rows (a sampled-rollout source's Q, else 0):
+// the layout of a mixed plan, then cost rows [Q][B N] of its own in place of the E rows.
+static RhBatchWs rh_batch_ws(const Geometry& g, const mbrl_cem_rh_params* rp, int B, void* base, bool mixed = false,
+                             int ts_rows = 0) {
     RhBatchWs w{};
     const mbrl_cem_params* p = &rp->cem;
     w.plan = batch_ws(g, p, B, base);
@@ -1086,6 +1088,7 @@ static RhBatchWs rh_batch_ws(const Geometry& g, const mbrl_cem_rh_params* rp, in
     w.kept[0] = c.take<float>(kb); w.kept[1] = c.take<float>(kb);
     w.best = c.take<int64_t>((size_t)B * rp->keep * 8);
     w.rets = c.take<float>(rp->keep || mixed ? (size_t)B * p->N * 4 : 0);
+    if (ts_rows) w.plan.costs = c.take<float>((size_t)ts_rows * B * p->N * 4);
     w.bytes = c.off;
     return w;
 }
@@ -1126,43 +1129,20 @@ size_t mbrl_cem_rh_mixed_workspace_bytes(const mbrl_mlp_shape* shape, const mbrl
     return mixed_ws_bytes(g, params, B);
 }
 
-// One receding-horizon entry's arguments. The single entries: B = 1, no flags; the batched ones: no events;
-// the white ones (and a mixed one called without a mix): mix NULL.
-struct RhCall {
-    const char* name;   // the entry, for the messages
-    bool batched;       // mbrl_cem_plan_rh_batch's layouts, and s0 checked with the other pointers
-    const mbrl_mlp_shape* shape;
-    const void* packed;
-    const mbrl_norm* norm;
-    const mbrl_cost* cost;
-    const float* s0;
-    int B;
-    const mbrl_cem_rh_params* rp;
-    const float *mu_rows, *sigma_rows, *carry_in;
-    const int32_t* flags;
-    const float* mix;
-    float *mu, *sigma, *actions_out, *states_out, *carry_out, *carry_returns_out, *cost_hist, *returns_hist;
-    int64_t* elite_hist;
-    float* kept_hist;
-    mbrl_event_t* events;
-    void* workspace;
-    size_t ws_bytes;
-    mbrl_stream_t stream;
-};
-
 // Every refusal of the four entries, before any launch, in this order: the shape, B, the parameters, a carry
 // without kept rows, NULL arguments, the mix's horizon, N, B N, then -- where the plan runs the kept-rows loop
-// (keep > 0 or a mix) -- B (the selections run one workgroup per problem, the staged refit a (H, B) grid) and
+// (keep > 0, a mix or a sampled-rollout source) -- B (the selections run one workgroup per problem, the staged refit a (H, B) grid) and
 // the staged refit's K x a, the workspace (the single entries answer MBRL_EINVAL, the batched ones
 // MBRL_EWORKSPACE) and, for the single plan, a forced pair kernel that does not apply. On MBRL_OK the entry's
-// workspace is carved: *single or *batch.
+// workspace is carved: *single or *batch. A call with a source carves the batched layout whichever entry it is
+// (the single one keeps its codes) and has no pair kernel to force.
 static int rh_entry_check(const RhCall& c, Geometry* g, RhWs* single, RhBatchWs* batch) {
     int rc = shape_geometry(c.shape, g);
     if (rc) return rc;
     if (c.B < 1) return fail(MBRL_EINVAL, "%s: B=%d", c.name, c.B);
     if ((rc = rh_params_check(c.rp))) return rc;
     const mbrl_cem_params* p = &c.rp->cem;
-    const bool kept_loop = c.rp->keep > 0 || c.mix;
+    const bool kept_loop = c.rp->keep > 0 || c.mix || c.ts;
     if (c.carry_in && c.rp->keep == 0) return fail(MBRL_EINVAL, "%s: carry_in given with keep == 0", c.name);
     if (!c.packed || (c.batched && !c.s0) || !c.actions_out || !c.states_out || !c.workspace)
         return fail(MBRL_EINVAL, "%s: packed/%sactions_out/states_out/workspace NULL", c.name, c.batched ? "s0/" : "");
@@ -1173,12 +1153,13 @@ static int rh_entry_check(const RhCall& c, Geometry* g, RhWs* single, RhBatchWs*
     if (kept_loop && c.B > 65535) return fail(MBRL_EUNSUPPORTED, "%s: B=%d exceeds 65535", c.name, c.B);
     if (kept_loop && (rc = refit_staged_check(g->a, p->K))) return rc;
     // the entry's workspace carved (*single or *batch) and its size: a mixed plan demands what its query answers
-    size_t need = c.batched ? (*batch = rh_batch_ws(*g, c.rp, c.B, c.workspace, c.mix != nullptr)).bytes
-                            : (*single = rh_ws(*g, c.rp, c.workspace, c.mix != nullptr)).bytes;
+    size_t need = c.ts        ? (*batch = rh_batch_ws(*g, c.rp, c.B, c.workspace, true, c.ts->Q)).bytes
+                  : c.batched ? (*batch = rh_batch_ws(*g, c.rp, c.B, c.workspace, c.mix != nullptr)).bytes
+                              : (*single = rh_ws(*g, c.rp, c.workspace, c.mix != nullptr)).bytes;
     if (c.mix) need = mixed_ws_bytes(*g, c.rp, c.B);
     if (c.ws_bytes < need)
         return fail(c.batched ? MBRL_EWORKSPACE : MBRL_EINVAL, "%s: workspace %zu < %zu", c.name, c.ws_bytes, need);
-    return c.batched ? MBRL_OK : pair_forced_check(*g, p->N);
+    return c.batched || c.ts ? MBRL_OK : pair_forced_check(*g, p->N);
 }
 
 // What the kept-rows loop of the single plan and of a batch differ in: where the buffers live and how the
@@ -1257,10 +1238,12 @@ static RhDrawArgs rh_draw_args(const Geometry& g, const RhCall& c, const RhLoop&
 // the workspace's two buffers. Then each problem's final mean rolled out, one trajectory launch each.
 // mix (NULL: none): the same loop for any keep >= 0 with the first launch, the gather and the draw coloured
 // (cem_noise.hip); the Kc selection runs only when Kc > 0.
+// c.ts (NULL: none): the same white loop for any keep >= 0 with the sampled rollout of iteration `it` in place of
+// the deterministic one; the cost rows, the selections and the returns then run over its Q rows.
 static int cem_plan_rh_kept(const Geometry& g, const RhCall& c, const RhLoop& L, hipStream_t stream) {
     const mbrl_cem_params* p = &c.rp->cem;
     const float* mix = c.mix;
-    const int B = c.B, Kc = c.rp->keep, BN = B * p->N;
+    const int B = c.B, Kc = c.rp->keep, BN = B * p->N, rows = c.ts ? c.ts->Q : g.E;
     const size_t kept_floats = (size_t)B * Kc * p->H * g.a;
     auto kept_at = [&](int i) { return c.kept_hist ? c.kept_hist + (size_t)i * kept_floats : L.kept[i & 1]; };
     int rc;
@@ -1270,17 +1253,20 @@ static int cem_plan_rh_kept(const Geometry& g, const RhCall& c, const RhLoop& L,
     const size_t keys_bytes = align256((size_t)BN * 4);
     int cur = 0;
     for (int it = 0; it < p->iterations; ++it) {
-        float* costs = c.cost_hist ? c.cost_hist + (size_t)it * g.E * BN : L.costs;
+        float* costs = c.cost_hist ? c.cost_hist + (size_t)it * rows * BN : L.costs;
         int64_t* elites = c.elite_hist ? c.elite_hist + (size_t)it * B * p->K : L.elites;
         float* rets = c.returns_hist ? c.returns_hist + (size_t)it * BN : L.rets;
         if ((rc = record_rollout_event(c.events, 2 * it, stream))) return rc;
-        rc = rollout_impl(g, c.packed, c.norm, c.cost, L.s0_ws, L.s0_per_cand, L.actions, nullptr, BN, p->H, 0, costs,
-                          nullptr, nullptr, stream, L.pair, L.zero.ptr[0] ? &pair_epoch : nullptr);
+        if (c.ts)
+            rc = ts_source_rollout(*c.ts, L.s0_ws, L.actions, BN, it, costs, stream);
+        else
+            rc = rollout_impl(g, c.packed, c.norm, c.cost, L.s0_ws, L.s0_per_cand, L.actions, nullptr, BN, p->H, 0, costs,
+                              nullptr, nullptr, stream, L.pair, L.zero.ptr[0] ? &pair_epoch : nullptr);
         if (rc) return rc;
         if ((rc = record_rollout_event(c.events, 2 * it + 1, stream))) return rc;
-        if ((rc = select_impl(costs, g.E, p->N, p->K, MBRL_NAN_LAST, elites, rets, L.keys, keys_bytes, stream, B)))
+        if ((rc = select_impl(costs, rows, p->N, p->K, MBRL_NAN_LAST, elites, rets, L.keys, keys_bytes, stream, B)))
             return rc;
-        if (Kc && (rc = select_impl(costs, g.E, p->N, Kc, MBRL_NAN_LAST, L.best, nullptr, L.keys, keys_bytes, stream, B)))
+        if (Kc && (rc = select_impl(costs, rows, p->N, Kc, MBRL_NAN_LAST, L.best, nullptr, L.keys, keys_bytes, stream, B)))
             return rc;
         const RhGatherArgs G = rh_gather_args(g, c, L, it, cur, rets, elites, kept_at(it), kept_at(it + 1));
         if ((rc = hip_check(mix ? launch_noise_gather(G, mix, stream) : launch_rh_gather(G, stream), "gather launch")))
@@ -1303,17 +1289,19 @@ static int cem_plan_rh_kept(const Geometry& g, const RhCall& c, const RhLoop& L,
 }
 
 // The four entries: the checks, then the fused-update loops where no rows are kept and no mix is given
-// (cem_plan_run / cem_batch_run with the initial distribution's rows), else the kept-rows loop.
-static int rh_plan(const RhCall& c) {
+// (cem_plan_run / cem_batch_run with the initial distribution's rows), else the kept-rows loop. A call with a
+// sampled-rollout source always takes the kept-rows loop, on the batched layout.
+static int rh_plan_run(const RhCall& c) {
     hipStream_t stream = reinterpret_cast<hipStream_t>(c.stream);
     Geometry g;
     RhWs w;
     RhBatchWs bw;
     if (int rc = rh_entry_check(c, &g, &w, &bw)) return rc;
     const mbrl_cem_params* p = &c.rp->cem;
-    const bool kept_loop = c.rp->keep > 0 || c.mix;
+    const bool kept_loop = c.rp->keep > 0 || c.mix || c.ts;
     if (kept_loop)
-        return cem_plan_rh_kept(g, c, c.batched ? rh_loop_batch(bw, p->N, c.s0) : rh_loop_single(g, p->N, w), stream);
+        return cem_plan_rh_kept(g, c, c.batched || c.ts ? rh_loop_batch(bw, p->N, c.s0) : rh_loop_single(g, p->N, w),
+                                stream);
     if (c.batched)
         return cem_batch_run(g, c.packed, c.norm, c.cost, c.s0, c.B, p, c.mu_rows, c.sigma_rows, c.flags, c.mu, c.sigma,
                              c.actions_out, c.states_out, c.cost_hist, c.returns_hist, c.elite_hist, bw.plan, stream);
@@ -1328,7 +1316,7 @@ int mbrl_cem_plan_rh_mixed(const mbrl_mlp_shape* shape, const void* packed, cons
                            float* carry_out, float* carry_returns_out, float* cost_hist, float* returns_hist,
                            int64_t* elite_hist, float* kept_hist, mbrl_event_t* rollout_events, void* workspace,
                            size_t ws_bytes, mbrl_stream_t stream) {
-    return rh_plan({noise_mix ? "cem_plan_rh_mixed" : "cem_plan_rh", false, shape, packed, norm, cost, s0_in, 1, rp,
+    return rh_plan_run({noise_mix ? "cem_plan_rh_mixed" : "cem_plan_rh", false, shape, packed, norm, cost, s0_in, 1, rp,
                     init_mu_rows, init_sigma_rows, carry_in, nullptr, noise_mix, mu, sigma, actions_out, states_out,
                     carry_out, carry_returns_out, cost_hist, returns_hist, elite_hist, kept_hist, rollout_events,
                     workspace, ws_bytes, stream});
@@ -1352,7 +1340,7 @@ int mbrl_cem_plan_rh_batch_mixed(const mbrl_mlp_shape* shape, const void* packed
                                  float* actions_out, float* states_out, float* carry_out, float* carry_returns_out,
                                  float* cost_hist, float* returns_hist, int64_t* elite_hist, float* kept_hist,
                                  void* workspace, size_t ws_bytes, mbrl_stream_t stream) {
-    return rh_plan({noise_mix ? "cem_plan_rh_batch_mixed" : "cem_plan_rh_batch", true, shape, packed, norm, cost, s0, B,
+    return rh_plan_run({noise_mix ? "cem_plan_rh_batch_mixed" : "cem_plan_rh_batch", true, shape, packed, norm, cost, s0, B,
                     rp, init_mu_rows, init_sigma_rows, carry_in, input_flags, noise_mix, mu, sigma, actions_out,
                     states_out, carry_out, carry_returns_out, cost_hist, returns_hist, elite_hist, kept_hist, nullptr,
                     workspace, ws_bytes, stream});
@@ -1372,3 +1360,15 @@ int mbrl_cem_plan_rh_batch(const mbrl_mlp_shape* shape, const void* packed, cons
 }
 
 }  // extern "C"
+
+namespace mbrl {
+
+int rh_plan(const RhCall& c) { return rh_plan_run(c); }
+
+size_t rh_ts_workspace_bytes(const mbrl_mlp_shape* shape, const mbrl_cem_rh_params* rp, int Q, int B) {
+    Geometry g;
+    if (shape_geometry(shape, &g) != MBRL_OK || rh_params_check(rp) != MBRL_OK || B < 1 || Q < 1) return 0;
+    return rh_batch_ws(g, rp, B, nullptr, true, Q).bytes;
+}
+
+}  // namespace mbrl

@@ -19,8 +19,16 @@
 // with atomics, there is no workspace: the bytes of a (row, candidate) depend on its own inputs, its member's
 // parameters and its counter words alone.
 //
+// Member modes (mbrl_rollout_cost_ts_rows): FIXED is the row layout above. RESAMPLED is PETS' TS-1: Q rows in all,
+// independent of E, and row q runs, at step t, the member drawn from Philox counter (0, t, q, (iteration << 8) |
+// 0xFF) -- a group byte no state-noise counter has. The draw has workgroup-uniform inputs: every wave computes it
+// once per step and indexes the member table the launch already carries. No wait, atomic or workspace is added.
+//
 // mbrl_cem_plan_ts: mbrl_cem_plan's loop (plan.hip cem_plan_run) with the sampled rollout in place of
 // rollout_impl and Q cost rows in place of E; the plan-loop helpers are mbrl_plan.h's.
+//
+// mbrl_cem_plan_ts_rh / mbrl_cem_plan_ts_rh_batch: the receding-horizon loop of plan.hip (rh_plan) with this
+// rollout as its source (mbrl_plan.h TsSource): warm start, kept rows and batches on sampled rows.
 #include <math.h>
 
 #include "eval_mlp.h"
@@ -43,10 +51,12 @@ struct TsLaunch {
     const float* actions;                      // [H][N][a]
     float* costs;                              // [Q][N]
     float* states_out;                         // [Q][H][N][s] or NULL
+    int32_t* members_out;                      // [Q][H] or NULL: the member each row ran at each step
     uint64_t noise_seed;
     float noise_scale, alpha_s, alpha_s2, alpha_a, alpha_a2;
     int norm_s, unnorm_s, norm_a, has_sc, has_ac, s0_per_cand;
     int s, a, W, L, ld, N, H, n_offset, P, iteration;
+    int E, resampled;                          // resampled: MBRL_TS_MEMBER_RESAMPLED (P is then not read)
 };
 
 // max(x, 0) + log1p(exp(-|x|)): train_nll.hip's nll_softplus
@@ -54,11 +64,10 @@ __device__ __forceinline__ float ts_softplus(float x) { return fmaxf(x, 0.0f) + 
 
 __global__ __launch_bounds__(TS_THREADS) void rollout_ts_kernel(const TsLaunch T) {
     extern __shared__ __attribute__((aligned(16))) float ts_lds[];
-    const int ld = T.ld, tid = threadIdx.x, row_q = blockIdx.y, e = row_q / T.P, s = T.s, a = T.a;
+    const int ld = T.ld, tid = threadIdx.x, row_q = blockIdx.y, s = T.s, a = T.a;
     float* buf[2] = {ts_lds, ts_lds + TS_TM * ld};
     const int64_t n0 = (int64_t)blockIdx.x * TS_TM;
     const int nvalid = (int)min((int64_t)TS_TM, (int64_t)T.N - n0);
-    const EvalMember& M = T.m[e];
     const int K0 = s + a, K0p = (K0 + 15) & ~15, tail = K0p - s, G = (s + 3) >> 2;
     // x_0: normalize_state(s0); candidates past N run on zeros and store nothing
     for (int idx = tid; idx < TS_TM * s; idx += TS_THREADS) {
@@ -73,6 +82,15 @@ __global__ __launch_bounds__(TS_THREADS) void rollout_ts_kernel(const TsLaunch T
     int cur = 0;
     float total = 0.0f;                                   // lanes tid < nvalid: their candidate's return
     for (int t = 0; t < T.H; ++t) {
+        // this step's member: the row's own, or the step's draw (uniform over the workgroup, kept in a scalar)
+        int e = T.resampled ? 0 : row_q / T.P;
+        if (T.resampled) {
+            const u32x4 w = philox4x32_10(u32x4{0u, (uint32_t)t, (uint32_t)row_q, ((uint32_t)T.iteration << 8) | 0xFFu},
+                                          (uint32_t)T.noise_seed, (uint32_t)(T.noise_seed >> 32));
+            e = __builtin_amdgcn_readfirstlane((int)__umulhi(w.x, (uint32_t)T.E));
+        }
+        const EvalMember& M = T.m[e];
+        if (T.members_out && blockIdx.x == 0 && tid == 0) T.members_out[(int64_t)row_q * T.H + t] = e;
         // columns s .. K0p - 1 of the input: normalize_action(a_t), then zeros (over the raw log-variances and
         // whatever an earlier layer left there)
         for (int idx = tid; idx < TS_TM * tail; idx += TS_THREADS) {
@@ -155,18 +173,26 @@ static int ts_ld(const TrainShape& t) {
     return ((widest + 15) & ~15) + EVAL_PAD;
 }
 
-// Every argument check of mbrl_rollout_cost_ts (all before any launch) and the launch arguments.
+// Every argument check of mbrl_rollout_cost_ts (all before any launch) and the launch arguments. member_mode:
+// mbrl_rollout_cost_ts_rows' (FIXED: the entry above). *Q: the launch's row count.
 static int ts_prepare(const char* what, const mbrl_train_model* members, int32_t E, const mbrl_nll_bounds* bounds,
                       const mbrl_norm* norm, const mbrl_cost* cost, const float* s0, int s0_per_cand,
                       const float* actions, int N, int H, int n_offset, const mbrl_ts_params* ts, float* costs,
-                      float* states_out, TsLaunch& T) {
+                      float* states_out, TsLaunch& T, int member_mode = MBRL_TS_MEMBER_FIXED,
+                      int32_t* members_out = nullptr, int* Q = nullptr) {
     if (!members || !s0 || !actions || !ts || !costs)
         return fail(MBRL_EINVAL, "%s: NULL members, s0, actions, ts or costs", what);
     if (N < 1 || H < 1 || n_offset < 0) return fail(MBRL_EINVAL, "%s: N = %d, H = %d, n_offset = %d", what, N, H, n_offset);
     if (E < 1 || E > MBRL_TRAIN_MAX_MEMBERS)
         return fail(MBRL_EINVAL, "%s: E = %d members outside [1, MBRL_TRAIN_MAX_MEMBERS = %d]", what, E,
                     MBRL_TRAIN_MAX_MEMBERS);
-    if (ts->particles < 1 || (int64_t)E * ts->particles > MBRL_TS_MAX_ROWS)
+    if (member_mode != MBRL_TS_MEMBER_FIXED && member_mode != MBRL_TS_MEMBER_RESAMPLED)
+        return fail(MBRL_EINVAL, "%s: member_mode %d", what, member_mode);
+    const bool resampled = member_mode == MBRL_TS_MEMBER_RESAMPLED;
+    if (resampled && (ts->particles < 1 || ts->particles > MBRL_TS_MAX_ROWS))
+        return fail(MBRL_EINVAL, "%s: %d resampled rows outside [1, MBRL_TS_MAX_ROWS = %d]", what, ts->particles,
+                    MBRL_TS_MAX_ROWS);
+    if (!resampled && (ts->particles < 1 || (int64_t)E * ts->particles > MBRL_TS_MAX_ROWS))
         return fail(MBRL_EINVAL, "%s: %d members x %d particles outside [1, MBRL_TS_MAX_ROWS = %d] rows", what, E,
                     ts->particles, MBRL_TS_MAX_ROWS);
     if (ts->iteration < 0 || ts->iteration >= (1 << 24))
@@ -216,6 +242,8 @@ static int ts_prepare(const char* what, const mbrl_train_model* members, int32_t
     T.noise_seed = ts->noise_seed; T.noise_scale = ts->noise_scale;
     T.s = t.s; T.a = t.a; T.W = t.W; T.L = t.L; T.ld = ts_ld(t);
     T.N = N; T.H = H; T.n_offset = n_offset; T.P = ts->particles; T.iteration = ts->iteration;
+    T.E = E; T.resampled = resampled; T.members_out = members_out;
+    if (Q) *Q = resampled ? ts->particles : E * ts->particles;
     return MBRL_OK;
 }
 
@@ -268,6 +296,58 @@ static int ts_plan_sizes(const mbrl_mlp_shape* shape, const mbrl_cem_params* p, 
     return MBRL_OK;
 }
 
+// The receding-horizon plans' checks that need no buffer: mbrl_cem_plan_ts's, with the row bound of the mode.
+static int ts_rh_sizes(const mbrl_mlp_shape* shape, const mbrl_cem_rh_params* rp, const mbrl_ts_rows* rows, Geometry* g,
+                       int* Q) {
+    if (int rc = shape_geometry(shape, g)) return rc;
+    if (!rp || !rows) return fail(MBRL_EINVAL, "cem_plan_ts_rh: NULL params or rows");
+    if (int rc = cem_params_check(&rp->cem)) return rc;
+    if (shape->reward_head || shape->precision != MBRL_PRECISION_F32)
+        return fail(MBRL_EUNSUPPORTED, "cem_plan_ts_rh: fp32 members without a reward head only");
+    if (rows->member_mode != MBRL_TS_MEMBER_FIXED && rows->member_mode != MBRL_TS_MEMBER_RESAMPLED)
+        return fail(MBRL_EINVAL, "cem_plan_ts_rh: member_mode %d", rows->member_mode);
+    const int P = rows->ts.particles;
+    const int64_t q = rows->member_mode == MBRL_TS_MEMBER_RESAMPLED ? P : (int64_t)g->E * P;
+    if (g->E > MBRL_TRAIN_MAX_MEMBERS || P < 1 || q > MBRL_TS_MAX_ROWS)
+        return fail(MBRL_EINVAL, "cem_plan_ts_rh: %d members, %d particles: rows outside [1, MBRL_TS_MAX_ROWS = %d] (E <= %d)",
+                    g->E, P, MBRL_TS_MAX_ROWS, MBRL_TRAIN_MAX_MEMBERS);
+    *Q = (int)q;
+    return MBRL_OK;
+}
+
+// mbrl_cem_plan_ts_rh and its batch: the sampled rollout's checks (on placeholder buffers: the loop sets the ones
+// that move), then the receding-horizon entry's own, then its loop with the source.
+static int ts_rh_plan(RhCall c, const mbrl_train_model* members, const mbrl_nll_bounds* bounds, const mbrl_ts_rows* rows) {
+    Geometry g;
+    int Q = 0, rc;
+    if ((rc = ts_rh_sizes(c.shape, c.rp, rows, &g, &Q))) return rc;
+    const mbrl_cem_params* p = &c.rp->cem;
+    if (!c.packed || !members || !c.actions_out || !c.states_out || !c.workspace || !c.s0)
+        return fail(MBRL_EINVAL, "%s: NULL packed, members, actions_out, states_out, workspace or s0", c.name);
+    if (c.B < 1) return fail(MBRL_EINVAL, "%s: B=%d", c.name, c.B);
+    if ((rc = rollout_validate(g, c.norm, c.cost))) return rc;   // (the final trajectories' checks)
+    TsLaunch T{};
+    mbrl_ts_params tp = rows->ts;
+    tp.iteration = 0;
+    float* const placeholder = static_cast<float*>(c.workspace);
+    if ((rc = ts_prepare(c.name, members, g.E, bounds, c.norm, c.cost, placeholder, 1, placeholder, p->N, p->H, 0, &tp,
+                         placeholder, nullptr, T, rows->member_mode)))
+        return rc;
+    if (T.s != g.s || T.a != g.a || T.W != g.W || T.L != g.L)
+        return fail(MBRL_EINVAL, "%s: the members' shape differs from the packed shape", c.name);
+    if (p->iterations > (1 << 24)) return fail(MBRL_EINVAL, "%s: iterations %d above 2^24", c.name, p->iterations);
+    const TsSource src{&T, Q};
+    c.ts = &src;
+    return rh_plan(c);
+}
+
+int ts_source_rollout(const TsSource& ts, const float* s0, const float* actions, int BN, int it, float* costs,
+                      hipStream_t stream) {
+    TsLaunch T = *ts.launch;
+    T.s0 = s0; T.s0_per_cand = 1; T.actions = actions; T.costs = costs; T.N = BN; T.iteration = it;
+    return ts_launch("cem_plan_ts_rh", T, ts.Q, stream);
+}
+
 }  // namespace mbrl
 
 using namespace mbrl;
@@ -284,6 +364,55 @@ int mbrl_rollout_cost_ts(const mbrl_train_model* members, int32_t E, const mbrl_
                             costs, states_out, T))
         return rc;
     return ts_launch(what, T, E * ts->particles, reinterpret_cast<hipStream_t>(stream));
+}
+
+int mbrl_rollout_cost_ts_rows(const mbrl_train_model* members, int32_t E, const mbrl_nll_bounds* bounds,
+                              const mbrl_norm* norm, const mbrl_cost* cost, const float* s0, int32_t s0_per_candidate,
+                              const float* actions, int32_t N, int32_t H, int32_t n_offset, const mbrl_ts_rows* rows,
+                              float* costs, float* states_out, int32_t* members_out, mbrl_stream_t stream) {
+    const char* what = "rollout_cost_ts_rows";
+    if (!rows) return fail(MBRL_EINVAL, "%s: NULL rows", what);
+    TsLaunch T{};
+    int Q = 0;
+    if (int rc = ts_prepare(what, members, E, bounds, norm, cost, s0, s0_per_candidate, actions, N, H, n_offset,
+                            &rows->ts, costs, states_out, T, rows->member_mode, members_out, &Q))
+        return rc;
+    return ts_launch(what, T, Q, reinterpret_cast<hipStream_t>(stream));
+}
+
+size_t mbrl_cem_ts_rh_workspace_bytes(const mbrl_mlp_shape* shape, const mbrl_cem_rh_params* params,
+                                      const mbrl_ts_rows* rows, int32_t B) {
+    Geometry g;
+    int Q = 0;
+    if (ts_rh_sizes(shape, params, rows, &g, &Q) != MBRL_OK) return 0;
+    return rh_ts_workspace_bytes(shape, params, Q, B);
+}
+
+int mbrl_cem_plan_ts_rh(const mbrl_mlp_shape* shape, const void* packed, const mbrl_train_model* members,
+                        const mbrl_nll_bounds* bounds, const mbrl_norm* norm, const mbrl_cost* cost, const float* s0,
+                        const mbrl_cem_rh_params* params, const mbrl_ts_rows* rows, const float* init_mu_rows,
+                        const float* init_sigma_rows, const float* carry_in, float* mu, float* sigma,
+                        float* actions_out, float* states_out, float* carry_out, float* carry_returns_out,
+                        float* cost_hist, float* returns_hist, int64_t* elite_hist, float* kept_hist, void* ws,
+                        size_t ws_bytes, mbrl_stream_t stream) {
+    return ts_rh_plan({"cem_plan_ts_rh", false, shape, packed, norm, cost, s0, 1, params, init_mu_rows, init_sigma_rows,
+                       carry_in, nullptr, nullptr, mu, sigma, actions_out, states_out, carry_out, carry_returns_out,
+                       cost_hist, returns_hist, elite_hist, kept_hist, nullptr, ws, ws_bytes, stream},
+                      members, bounds, rows);
+}
+
+int mbrl_cem_plan_ts_rh_batch(const mbrl_mlp_shape* shape, const void* packed, const mbrl_train_model* members,
+                              const mbrl_nll_bounds* bounds, const mbrl_norm* norm, const mbrl_cost* cost,
+                              const float* s0, int32_t B, const mbrl_cem_rh_params* params, const mbrl_ts_rows* rows,
+                              const float* init_mu_rows, const float* init_sigma_rows, const float* carry_in,
+                              const int32_t* input_flags, float* mu, float* sigma, float* actions_out,
+                              float* states_out, float* carry_out, float* carry_returns_out, float* cost_hist,
+                              float* returns_hist, int64_t* elite_hist, float* kept_hist, void* ws, size_t ws_bytes,
+                              mbrl_stream_t stream) {
+    return ts_rh_plan({"cem_plan_ts_rh_batch", true, shape, packed, norm, cost, s0, B, params, init_mu_rows,
+                       init_sigma_rows, carry_in, input_flags, nullptr, mu, sigma, actions_out, states_out, carry_out,
+                       carry_returns_out, cost_hist, returns_hist, elite_hist, kept_hist, nullptr, ws, ws_bytes, stream},
+                      members, bounds, rows);
 }
 
 size_t mbrl_cem_ts_workspace_bytes(const mbrl_mlp_shape* shape, const mbrl_cem_params* params,

@@ -12,8 +12,8 @@ from .models import (CoshLoss, CostModel, DynamicsModel, EnsembleModel, LinearMo
                      ModelWithReward, QuadraticCost, SmoothAbsLoss, compose, goal_state_cost, member_order,
                      state_action_cost)
 from .planners import (BatchedMPPIPlanner, CEMPlanner, GradientDescentPlanner, ModelPlanner, MPPIPlanner,  # noqa: F401
-                       RandomShootingPlanner, RecedingHorizonCEMPlanner, cem_plan_batch_rh, cem_shift_carry,
-                       mppi_plan_batch)
+                       RandomShootingPlanner, RecedingHorizonCEMPlanner, TrajectorySamplingCEMPlanner,
+                       cem_plan_batch_rh, cem_shift_carry, mppi_plan_batch)
 
 
 def load_extension():

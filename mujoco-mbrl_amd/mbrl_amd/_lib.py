@@ -84,6 +84,7 @@ EXPORTED = (
     "mbrl_train_nll_workspace_bytes", "mbrl_train_grads_nll", "mbrl_train_epoch_nll", "mbrl_train_epoch_nll_clipped",
     "mbrl_eval_members_nll",
     "mbrl_rollout_cost_ts", "mbrl_cem_ts_workspace_bytes", "mbrl_cem_plan_ts",
+    "mbrl_rollout_cost_ts_rows", "mbrl_cem_ts_rh_workspace_bytes", "mbrl_cem_plan_ts_rh", "mbrl_cem_plan_ts_rh_batch",
 )
 
 
@@ -184,6 +185,16 @@ class TsParams(ctypes.Structure):
     """mbrl_ts_params (include/mbrl_cem.h; added within ABI v13): the trajectory-sampling entries' particles and
     noise key."""
     _fields_ = [("particles", c_int32), ("iteration", c_int32), ("noise_seed", c_uint64), ("noise_scale", c_float)]
+
+
+TS_MEMBER_FIXED, TS_MEMBER_RESAMPLED = 0, 1   # MBRL_TS_MEMBER_*
+TS_MEMBER_MODES = {"fixed": TS_MEMBER_FIXED, "resampled": TS_MEMBER_RESAMPLED}
+
+
+class TsRows(ctypes.Structure):
+    """mbrl_ts_rows (include/mbrl_cem.h; added within ABI v13): a TsParams and the member mode of its rows
+    (RESAMPLED: ts.particles is the row count Q)."""
+    _fields_ = [("ts", TsParams), ("member_mode", c_int32), ("_pad", c_int32)]
 
 
 class StackField(ctypes.Structure):
@@ -299,6 +310,18 @@ def load():
         "mbrl_cem_plan_ts": (c_int32, [POINTER(MlpShape), P, POINTER(TrainModel), POINTER(NllBounds), POINTER(Norm),
                                        POINTER(Cost), P, POINTER(CemParams), POINTER(TsParams), P, P, P, P, P, P, P, P,
                                        c_size_t, P]),
+        # the per-step member draw and the receding-horizon plans on sampled rows
+        "mbrl_rollout_cost_ts_rows": (c_int32, [POINTER(TrainModel), c_int32, POINTER(NllBounds), POINTER(Norm),
+                                                POINTER(Cost), P, c_int32, P, c_int32, c_int32, c_int32, POINTER(TsRows),
+                                                P, P, P, P]),
+        "mbrl_cem_ts_rh_workspace_bytes": (c_size_t, [POINTER(MlpShape), POINTER(CemRhParams), POINTER(TsRows), c_int32]),
+        "mbrl_cem_plan_ts_rh": (c_int32, [POINTER(MlpShape), P, POINTER(TrainModel), POINTER(NllBounds), POINTER(Norm),
+                                          POINTER(Cost), P, POINTER(CemRhParams), POINTER(TsRows), P, P, P, P, P, P, P,
+                                          P, P, P, P, P, P, P, c_size_t, P]),
+        "mbrl_cem_plan_ts_rh_batch": (c_int32, [POINTER(MlpShape), P, POINTER(TrainModel), POINTER(NllBounds),
+                                                POINTER(Norm), POINTER(Cost), P, c_int32, POINTER(CemRhParams),
+                                                POINTER(TsRows), P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, c_size_t,
+                                                P]),
         "mbrl_eval_members": (c_int32, [POINTER(TrainModel), c_int32, POINTER(TrainData), P, c_int64, P, P, P, P]),
         "mbrl_eval_members_open_loop": (c_int32, [POINTER(TrainModel), c_int32, POINTER(TrainData), P, c_int64, P, P, P, P,
                                                   P]),
@@ -528,4 +551,5 @@ __all__ = ["load", "check", "ptr", "stream_handle", "MlpShape", "Norm", "Cost", 
            "ABI_VERSION", "c_int64", "MBRL_PRECISION_F32", "MBRL_PRECISION_F16X3", "MBRL_PRECISION_F16X6",
            "precision_code", "load_other", "option", "OPTIONS", "AdamTensor", "AdamHparams",
            "TrainModel", "TrainData", "NllBounds", "TRAIN_MAX_LAYERS", "TRAIN_MAX_MEMBERS", "HostStaging", "CopyTensor",
-           "StackField", "StatsField", "TsParams", "TS_MAX_ROWS"]
+           "StackField", "StatsField", "TsParams", "TS_MAX_ROWS", "TsRows", "TS_MEMBER_FIXED", "TS_MEMBER_RESAMPLED",
+           "TS_MEMBER_MODES"]

@@ -618,14 +618,34 @@ def ts_params(particles, iteration, noise_seed, noise_scale):
     return _lib.TsParams(int(particles), int(iteration), int(noise_seed) & (2 ** 64 - 1), float(noise_scale))
 
 
+def ts_rows(particles, iteration, noise_seed, noise_scale, member_mode):
+    """mbrl_ts_rows; member_mode: "fixed" / "resampled" or an MBRL_TS_MEMBER_* value."""
+    mode = _lib.TS_MEMBER_MODES[member_mode] if isinstance(member_mode, str) else int(member_mode)
+    return _lib.TsRows(ts_params(particles, iteration, noise_seed, noise_scale), mode, 0)
+
+
 def rollout_ts(prob, s0, actions, *, particles, noise_seed, noise_scale=1.0, iteration=0, n_offset=0,
-               s0_per_candidate=False, costs=None, states_out=None):
+               s0_per_candidate=False, costs=None, states_out=None, member_mode=None, members_out=None):
     """mbrl_rollout_cost_ts: the sampled rollout of `actions` [H, N, a] on particles rows per member of prob's
-    probabilistic ensemble. Returns costs [E * particles, N]; states_out: [E * particles, H, N, s] or None."""
+    probabilistic ensemble. Returns costs [E * particles, N]; states_out: [E * particles, H, N, s] or None.
+    member_mode ("fixed" / "resampled" or an MBRL_TS_MEMBER_* value) or members_out ([Q, H] int32: the member each
+    row ran at each step) make the call mbrl_rollout_cost_ts_rows; "resampled" has Q = particles rows in all, each
+    drawing its member afresh at every step."""
     lib = _lib.load()
     dev = prob.device
     table = ts_members(prob.mdesc["module"], dev)
     H, N = int(actions.shape[0]), int(actions.shape[1])
+    if member_mode is not None or members_out is not None:
+        rows = ts_rows(particles, iteration, noise_seed, noise_scale, "fixed" if member_mode is None else member_mode)
+        if costs is None:
+            Q = int(particles) * (1 if rows.member_mode == _lib.TS_MEMBER_RESAMPLED else table.E)
+            costs = torch.empty((Q, N), dtype=torch.float32, device=dev)
+        _lib.check(lib.mbrl_rollout_cost_ts_rows(table.models, table.E, ctypes_ref(table.bounds), ctypes_ref(prob.norm),
+                                                 ctypes_ref(prob.cost), _lib.ptr(s0), int(s0_per_candidate),
+                                                 _lib.ptr(actions), N, H, n_offset, ctypes_ref(rows), _lib.ptr(costs),
+                                                 _lib.ptr(states_out), _lib.ptr(members_out), _lib.stream_handle(dev)),
+                   "mbrl_rollout_cost_ts_rows")
+        return costs
     if costs is None:
         costs = torch.empty((table.E * int(particles), N), dtype=torch.float32, device=dev)
     ts = ts_params(particles, iteration, noise_seed, noise_scale)

@@ -956,6 +956,166 @@ class RecedingHorizonCEMPlanner(CEMPlanner):
         return res["states"], res["actions"], out
 
 
+def _ts_rh_inputs(kwargs):
+    """The checked particle kwargs of TrajectorySamplingCEMPlanner as dict(P, noise, seed, mode): ValueError for a
+    bad particle_mode or particle value, NotImplementedError naming every kwarg the sampled plans have no form for,
+    before anything needs a device."""
+    mode = kwargs.get("particle_mode", TrajectorySamplingCEMPlanner.ts_defaults["particle_mode"])
+    if not isinstance(mode, str) or mode not in _lib.TS_MEMBER_MODES:
+        raise ValueError(f"particle_mode={mode!r}: need one of {sorted(_lib.TS_MEMBER_MODES)}")
+    P, noise, seed = _ts_values(kwargs)
+    if P < 1:
+        raise ValueError(f"particles={P!r}: TrajectorySamplingCEMPlanner needs an integer >= 1")
+    where = f"TrajectorySamplingCEMPlanner with particles={P}"
+    if kwargs.get("distributed", False):
+        raise NotImplementedError(f"{where}: distributed=True is not implemented")
+    _noise_refuse(kwargs, where)
+    precision = kwargs.get("precision", CEMPlanner.defaults["precision"])
+    if precision != "f32":
+        raise NotImplementedError(f"{where}: precision={precision!r} is not implemented (the sampled rollout is fp32)")
+    dev = kwargs.get("device")
+    if dev is not None and torch.device(dev).type != "cuda":
+        raise NotImplementedError(f"{where}: device={str(dev)!r} is not implemented (the sampled rollout is a HIP "
+                                  "kernel)")
+    return dict(P=P, noise=noise, seed=seed, mode=mode)
+
+
+def _cem_ts_rh(kwargs, st, ts, rh, initial_states, model, cost, B):
+    """One C-ABI call: mbrl_cem_plan_ts_rh (B None: initial_states [s]) or mbrl_cem_plan_ts_rh_batch (initial_states
+    [B, s]). rh: _rh_inputs' / _rh_batch_inputs' dict. Returns the result dict on the device: states, actions, mu,
+    sigma, with kept rows carry and carry_returns, with record=True costs ([I, Q, N] or [I, Q, B N]), returns, elites
+    and kept_hist."""
+    dev = _device(kwargs)
+    batched = B is not None
+    with _on_device(dev):
+        mdesc, cdesc, prob = fused.describe_problem(model, cost, dev, st["precision"])
+        if mdesc is None or cdesc is None:
+            raise NotImplementedError(f"CEMPlanner with callables the fused path does not recognise: particles="
+                                      f"{ts['P']} is not implemented (trajectory sampling runs on the fused path)")
+        lib = _lib.load()
+        resampled = ts["mode"] == "resampled"
+        table = _ts_table(prob, ts["P"], resampled)
+        N, K, H, I, Kc = st["N"], st["K"], st["H"], st["I"], rh["Kc"]
+        a, s = mdesc["a"], mdesc["s"]
+        Q = ts["P"] if resampled else table.E * ts["P"]
+        nb = B if batched else 1
+        _held, ins, _, _ = _rh_call_inputs(lib, rh, a, dev, None, batched)   # (the uploads, held to the call)
+        seed = int(st["seed"]) & 0xFFFFFFFFFFFFFFFF
+        rows = fused.ts_rows(ts["P"], 0, _ts_seed(seed) if ts["seed"] is None else ts["seed"], ts["noise"], ts["mode"])
+        pkey = ("ts_rh", ts["P"], ts["mode"], nb, N, H, K, I, Kc, st["alpha"], st["lo"], st["hi"], st["init_std"], seed)
+        _, pref, need = _plan_params(prob, pkey, lambda: _lib.CemRhParams(_cem_params(st, seed), Kc, 0),
+                                     lib.mbrl_cem_ts_rh_workspace_bytes, fused.ctypes_ref(rows), nb)
+        if need == 0:
+            _lib.check(_lib.MBRL_EINVAL, "mbrl_cem_ts_rh_workspace_bytes")
+        ws = _workspace(("cem_ts_rh", str(dev)), need, dev)
+        lead = (B,) if batched else ()
+        s0 = initial_states.to(device=dev, dtype=torch.float32).reshape(*lead, s).contiguous()
+        e = lambda *sh, dt=torch.float32: torch.empty(sh, dtype=dt, device=dev)  # noqa: E731
+        if batched:
+            out = dict(states=e(B, H, s), actions=e(B, H, a), mu=e(B, H, a), sigma=e(B, H, a))
+        else:
+            out = _device_outputs(dev, H, s, a)
+        rec = st["record"]
+        if Kc:
+            out.update(carry=e(*lead, Kc, H, a), carry_returns=e(*lead, Kc))
+        if rec:
+            out.update(costs=e(I, Q, nb * N), returns=e(I, *lead, N), elites=e(I, *lead, K, dt=torch.int64))
+            if Kc:
+                out.update(kept_hist=e(I + 1, *lead, Kc, H, a))
+        g = lambda k: _lib.ptr(out.get(k))  # noqa: E731
+        shape_ref, packed, norm_ref, cost_ref = prob.refs
+        head = (shape_ref, packed, *table.refs, norm_ref, cost_ref, _lib.ptr(s0)) + ((B,) if batched else ())
+        call = lib.mbrl_cem_plan_ts_rh_batch if batched else lib.mbrl_cem_plan_ts_rh
+        pev = st["plan_events"]
+        _mark(pev, 0)
+        _lib.check(call(*head, pref, fused.ctypes_ref(rows), *ins, g("mu"), g("sigma"), g("actions"), g("states"),
+                        g("carry"), g("carry_returns"), g("costs"), g("returns"), g("elites"), g("kept_hist"),
+                        _lib.ptr(ws), ws.numel(), _lib.stream_handle(dev)), call.__name__)
+        _mark(pev, 1)
+        return out
+
+
+class TrajectorySamplingCEMPlanner(ModelPlanner):
+    """CEM on sampled ensemble particles for the control loop (mbrl_cem_plan_ts_rh, mbrl_cem_plan_ts_rh_batch):
+    CEMPlanner(particles=P)'s sampled rollout with the receding-horizon inputs CEMPlanner refuses beside it -- warm
+    start, kept rows, batches -- and PETS' second propagation mode.
+
+    kwargs: CEMPlanner's own (num_candidates, num_elites, num_iterations, alpha, seed, init_std, action_bounds,
+    return_device, record) and, with CEMPlanner's meaning and checks, warm_start (True here), shift, warm_std,
+    keep_elites (0.3 here), carry, particle_noise and particle_seed.
+    particles (1): P >= 1.
+    particle_mode ("fixed"): "fixed" rolls every candidate out as P particles per member, each on its member for the
+        whole horizon (TS-inf: E * P rows); "resampled" as P rows in all, each drawing its member afresh at every
+        step (TS-1: the row count no longer depends on the ensemble's size). Anything else raises ValueError.
+    The model and cost requirements are CEMPlanner(particles=P)'s; distributed=True, the coloured-noise kwargs, a
+    precision other than "f32" and a CPU device raise NotImplementedError.
+
+    plan_detailed returns dict(states, actions, mu, sigma[, carry, carry_returns]); record=True adds costs
+    [I, Q, N], returns, elites and kept_hist. plan_batch answers B problems with one call and hands back one memo per
+    problem, exactly as RecedingHorizonCEMPlanner.plan_batch does."""
+    ts_defaults = dict(particles=1, particle_mode="fixed", warm_start=True, keep_elites=0.3)
+    # the planner service passes each rollout's previous plan (initial_trajectories) and its memo (memos)
+    warm_starts = True
+    plan_memo = True
+
+    @staticmethod
+    def _kwargs(kwargs):
+        return dict(TrajectorySamplingCEMPlanner.ts_defaults, **kwargs)
+
+    @staticmethod
+    def plan(initial_state, model, cost, sample_action, horizon, initial_trajectory=None, **kwargs):
+        res = TrajectorySamplingCEMPlanner.plan_detailed(initial_state, model, cost, sample_action, horizon,
+                                                         initial_trajectory, **kwargs)
+        return res["states"], res["actions"]
+
+    @staticmethod
+    def plan_detailed(initial_state, model, cost, sample_action, horizon, initial_trajectory=None, **kwargs):
+        kw = TrajectorySamplingCEMPlanner._kwargs(kwargs)
+        ts = _ts_rh_inputs(kw)
+        st = CEMPlanner._settings(sample_action, horizon, kw)
+        rh = _rh_inputs(st, initial_trajectory, kw) or dict(mu_rows=None, sigma_rows=None, carry=None, Kc=0)
+        res = _cem_ts_rh(kw, st, ts, rh, initial_state, model, cost, None)
+        if st["record"]:
+            for k, src in (("init_mu", "mu_rows"), ("init_sigma", "sigma_rows")):
+                if rh[src] is not None:
+                    res[k] = torch.from_numpy(rh[src])
+        return _finish(res, st["keep"])
+
+    @staticmethod
+    def plan_batch(initial_states, model, cost, sample_action, horizon, initial_trajectories=None, memos=None,
+                   **kwargs):
+        """B plans at once; returns (states [B, H, s], actions [B, H, a], memos) -- memos[b] = dict(carry
+        [Kc, H, a] or None, sigma [H, a]) of problem b's plan, host tensors, to pass back at its next step."""
+        res = TrajectorySamplingCEMPlanner.plan_batch_detailed(initial_states, model, cost, sample_action, horizon,
+                                                               initial_trajectories, memos, **kwargs)
+        B = int(initial_states.shape[0])
+        carry = res["carry"].cpu() if "carry" in res else None
+        sigma = res["sigma"].cpu()
+        out = [dict(carry=None if carry is None else carry[b], sigma=sigma[b]) for b in range(B)]
+        return res["states"], res["actions"], out
+
+    @staticmethod
+    def plan_batch_detailed(initial_states, model, cost, sample_action, horizon, initial_trajectories=None, memos=None,
+                            **kwargs):
+        """plan_batch's one call as its result dict (cem_plan_batch_rh's layouts, costs [I, Q, B N])."""
+        kw = TrajectorySamplingCEMPlanner._kwargs(kwargs)
+        ts = _ts_rh_inputs(kw)
+        for k in ("carry", "prev_sigma"):
+            if kw.get(k) is not None:
+                raise TypeError(f"TrajectorySamplingCEMPlanner.plan_batch takes per-problem memos, not {k}=")
+        kw = {k: v for k, v in kw.items() if k not in ("carry", "prev_sigma")}
+        st = CEMPlanner._settings(sample_action, horizon, kw)
+        rs = _rh_settings(kw, st["K"])
+        B = int(initial_states.shape[0])
+        if B < 1:
+            raise ValueError("TrajectorySamplingCEMPlanner.plan_batch needs at least one initial state")
+        carries, sigmas = RecedingHorizonCEMPlanner._memo_inputs(memos, B, rs["shift"], st["lo"], st["hi"])
+        rh = _rh_batch_inputs(st, B, initial_trajectories, carries if rs["Kc"] else None,
+                              sigmas if rs["warm_std"] == "keep" else None, kw)
+        res = _cem_ts_rh(kw, st, ts, rh, initial_states, model, cost, B)
+        return {k: _to_host(v, st["keep"]) for k, v in res.items()}
+
+
 _WS = threading.local()
 
 
@@ -1133,6 +1293,21 @@ def _cem_fused_single(prob, initial_state, st):
     return out
 
 
+def _ts_table(prob, P, resampled=False):
+    """The sampled plans' model and cost requirements: the goal-state cost, an EnsembleModel of ProbabilisticModels
+    (fused.ts_members raises NotImplementedError for any other model) and at most TS_MAX_ROWS rows -- E * P of them,
+    or P where every row draws its member per step. Returns the member table."""
+    where = f"CEMPlanner with particles={P}"
+    if prob.mdesc.get("reward") or prob.cdesc["kind"] != _lib.MBRL_COST_GOAL_STATE:
+        raise NotImplementedError(f"{where}: only the goal-state cost is implemented")
+    table = fused.ts_members(prob.mdesc["module"], prob.device)
+    if resampled and P > _lib.TS_MAX_ROWS:
+        raise NotImplementedError(f"{where}: {P} resampled rows exceed {_lib.TS_MAX_ROWS} rows")
+    if not resampled and table.E * P > _lib.TS_MAX_ROWS:
+        raise NotImplementedError(f"{where}: {table.E} members x {P} particles exceed {_lib.TS_MAX_ROWS} rows")
+    return table
+
+
 def _cem_fused_ts(prob, initial_state, st, ts):
     """One C-ABI call: mbrl_cem_plan_ts, the plan on ts["P"] sampled particles per member. record=True returns the
     costs as [I, E * P, N]."""
@@ -1140,14 +1315,9 @@ def _cem_fused_ts(prob, initial_state, st, ts):
     dev = prob.device
     md = prob.mdesc
     P = ts["P"]
-    where = f"CEMPlanner with particles={P}"
-    if md.get("reward") or prob.cdesc["kind"] != _lib.MBRL_COST_GOAL_STATE:
-        raise NotImplementedError(f"{where}: only the goal-state cost is implemented")
-    table = fused.ts_members(md["module"], dev)      # (NotImplementedError for any other model)
+    table = _ts_table(prob, P)
     N, K, H, I = st["N"], st["K"], st["H"], st["I"]
     a, s, Q = md["a"], md["s"], table.E * P
-    if Q > _lib.TS_MAX_ROWS:
-        raise NotImplementedError(f"{where}: {table.E} members x {P} particles exceed {_lib.TS_MAX_ROWS} rows")
     seed = int(st["seed"]) & 0xFFFFFFFFFFFFFFFF
     tsp = fused.ts_params(P, 0, _ts_seed(seed) if ts["seed"] is None else ts["seed"], ts["noise"])
     pkey = ("ts", P, N, H, K, I, st["alpha"], st["lo"], st["hi"], st["init_std"], seed)
